@@ -3,6 +3,7 @@ SIM latent force model at N = 16384 (BASELINE.json configs[1]: 64 genes x 256 ti
 fp64, one MLL evaluation per step), plus the fp64 Cholesky rate.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c2|c3|c4|c5]
+                    [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \\
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -37,8 +38,16 @@ shipping the RCCL unique id.
 
 Rank 0 prints ONE JSON line; ``value`` = work completed by all ranks / the slowest rank's
 wall time of the K timed steps. Every result of the timed steps must be finite and identical
-across steps, and (one rank) the GPU values are checked against the C++ CPU restatement on
-the same inputs in the cpu_baseline leg.
+across steps. A plain run does only that: set up, warm up, time the K steps, print the line.
+
+  --dump-outputs DIR  after the timed steps, write what the last timed step returned as
+      DIR/result.npy (fp64; c4 also a seeded sample of the filled rows, c5fit the fitted raw
+      parameters and loss histories). The inputs are seeded, so two builds run with the same
+      arguments can be compared output for output.
+  --full  everything else the line can carry: per-kernel HIP events in the timed region and the
+      roofline from them, the exchange's latency, the multi-rank and 16-round comparisons, and
+      (one rank) the cpu_baseline leg, in which the GPU values are checked against the C++ CPU
+      restatement on the same inputs.
 """
 
 from __future__ import annotations
@@ -109,6 +118,15 @@ def parse(argv=None):
                         "= 1 on one GPU (configs[4]'s step), 16 on several")
     p.add_argument("--fit-iters", type=int, default=150,
                    help="c5fit: Adam steps per fit (notebook.py:64 / main.py:54: 150)")
+    p.add_argument("--full", action="store_true",
+                   help="besides the headline figure: per-kernel HIP events and the roofline, the "
+                        "exchange's latency, the multi-rank and 16-round comparisons and the CPU "
+                        "baseline with its parity check (--no-profile / --no-cpu-baseline drop "
+                        "theirs again); a plain run sets up, warms up, times the steps and prints "
+                        "the line")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last timed step returned (and the "
+                        "arrays it filled) as DIR/<name>.npy, float32 / float64 (rank 0)")
     p.add_argument("--no-cpu-baseline", action="store_true")
     p.add_argument("--cpu-threads", type=int, default=0)
     p.add_argument("--no-profile", action="store_true",
@@ -699,7 +717,7 @@ def main(argv=None):
 
         if world == 1:
             def step():
-                fit_block()
+                step.raw = fit_block()
                 return fit_hist[-1].copy()  # each problem's final loss
         else:
             rec_len = 3 * gmax + 2 + iters
@@ -761,7 +779,7 @@ def main(argv=None):
     # event record between two dependent launches widens the dispatch gap, ≈ 0.5 ms per
     # evaluation with all step launches instrumented; one instrumented step of K costs
     # 0.5 / K ms); c4 in every step (one fill launch per step)
-    prof = not a.no_profile and a.workload in ("c2", "c4", "c5fit")
+    prof = a.full and not a.no_profile and a.workload in ("c2", "c4", "c5fit")
     prof_steps = (1 if a.workload == "c2" else a.steps) if prof else 0
     classes = {"c2": ["syrk", "gram_grid", "potrf", "syrk_side"], "c4": ["gram_grid", "tables"],
                "c5fit": ["small_grad"]}.get(a.workload)
@@ -800,7 +818,7 @@ def main(argv=None):
     # the exchange step alone (collective latency reported separately): the same
     # all-gather of this workload's NaN-padded slots, outside the timed region
     collective = None
-    if world > 1:
+    if a.full and world > 1:
         # this workload's own exchange size: the records of c5fit's fits, c5's rounds, c3's
         # restarts, one slot per rank for c2 / c4
         if a.workload == "c5fit":
@@ -825,7 +843,7 @@ def main(argv=None):
             collective["in_step"] = ("chained on the device: batch kernel -> ncclAllGather -> "
                                      "publish kernel, one bounded host wait "
                                      "(lfm_farm_batch_mll_f64)")
-    elif a.workload in ("c3", "c5"):
+    elif a.full and a.workload in ("c3", "c5"):
         # one GPU: the library's exchange path alone on a 1-rank RCCL communicator (staging
         # copies, enqueue, the bounded host wait; no xGMI transfer) — the floor the W > 1
         # all-gather adds to per step. Best effort: a box without RCCL just omits it.
@@ -877,10 +895,32 @@ def main(argv=None):
         raise SystemExit(f"non-finite result in the timed region: {res[~np.isfinite(res)][:4]}")
     if not np.all(res == res[0]):
         raise SystemExit("timed steps disagree (the same inputs gave different results)")
+    if a.dump_outputs and rank == 0:
+        # what the last timed step handed its caller (the inputs are seeded: the same
+        # arguments give the same problem in every run and build)
+        outs = {"result": np.asarray(timed[-1], np.float64)}
+        if a.workload == "c4":
+            # the fill's output is the N x N fp32 buffer (17 GB at the default size): a fixed
+            # seeded sample of its rows, the first and the last among them, each up to its
+            # diagonal (the fill writes the lower triangle only; the rest is left 0 here)
+            rr = np.unique(np.concatenate([[0, n - 1], np.random.default_rng(4).integers(
+                0, n, min(n, 30))])).astype(np.int64)
+            got = c4_rows(rr)
+            got[np.arange(n)[None, :] > rr[:, None]] = 0.0
+            outs["gram_row_index"] = rr.astype(np.float64)
+            outs["gram_rows"] = got
+        elif a.workload == "c5fit" and world == 1:
+            outs["raw_params"] = np.asarray(step.raw, np.float64)
+            outs["loss_history"] = np.asarray(fit_hist, np.float64)
+        elif a.workload == "c5fit":
+            outs["fit_records"] = np.asarray(step.records, np.float64)
+        os.makedirs(a.dump_outputs, exist_ok=True)
+        for name, arr in outs.items():
+            np.save(os.path.join(a.dump_outputs, name + ".npy"), arr)
 
     # multi-rank farms, checked after the timed region on rank 0: the gathered results are the
     # bits of one rank doing the whole step alone (the same kernels on the same inputs)
-    if world > 1 and rank == 0 and a.workload == "c5":
+    if a.full and world > 1 and rank == 0 and a.workload == "c5":
         evl = farm.BatchEvaluator(ctx, datasets)
         try:
             local = evl.evaluate_packed(evl.pack(models))
@@ -888,7 +928,7 @@ def main(argv=None):
             evl.close()
         if not np.array_equal(local, res[0]):
             raise SystemExit("the gathered c5 rounds differ from one rank's evaluation of them")
-    if world > 1 and rank == 0 and a.workload == "c5fit":
+    if a.full and world > 1 and rank == 0 and a.workload == "c5fit":
         from dis_project_amd import trainer as TR
 
         evl = farm.BatchEvaluator(ctx, datasets, negative=True)
@@ -907,7 +947,7 @@ def main(argv=None):
                 not np.array_equal(want[~np.isnan(want)], step.records[~np.isnan(want)]):
             raise SystemExit("the gathered fits differ from one rank's fit of all 15")
     c5_rounds16 = None
-    if world == 1 and a.workload == "c5" and a.rounds == 1:
+    if a.full and world == 1 and a.workload == "c5" and a.rounds == 1:
         # the per-GPU capacity at the multi-GPU lines' round count (C5_ROUNDS_MULTI rounds of
         # the 15 in one launch): the W = 1 point of the weak-scaling curve over rounds
         m16, d16 = farm.workload("c5", rounds=C5_ROUNDS_MULTI)
@@ -1175,7 +1215,7 @@ def main(argv=None):
             }
             if tab.get("launches"):
                 line["roofline"]["tables_ms_per_fill"] = tab["total_ms"] / tab["launches"]
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline:
         thr = cpu_threads(a)
         if a.workload == "c2":
             cb = cpu_baseline_c2(work, thr, float(res[0][0]))

@@ -9,8 +9,8 @@ LFM_LIBRARY=ablibs/stamps/liblfm.so $S r06g_stamps 200 python -u scripts/small_s
 for r in 1 2; do
   for lib in ablibs/notw/liblfm.so dis_project_amd/liblfm.so; do
     tag=$(basename $(dirname $lib))
-    LFM_LIBRARY=$lib $S r06g_c5_${tag}_$r 120 python -u bench.py --workload c5 --steps 2000 --warmup 200 --no-cpu-baseline || exit $?
-    LFM_LIBRARY=$lib $S r06g_c5fit_${tag}_$r 120 python -u bench.py --workload c5fit --steps 30 --warmup 3 --no-cpu-baseline || exit $?
+    LFM_LIBRARY=$lib $S r06g_c5_${tag}_$r 120 python -u bench.py --full --workload c5 --steps 2000 --warmup 200 --no-cpu-baseline || exit $?
+    LFM_LIBRARY=$lib $S r06g_c5fit_${tag}_$r 120 python -u bench.py --full --workload c5fit --steps 30 --warmup 3 --no-cpu-baseline || exit $?
   done
 done
 $S r06g_tests 400 python -u -m pytest tests/test_farm.py tests/test_gpu_batch_grad.py tests/test_gpu_parity.py -m gpu -x -q --timeout 200 --timeout-method thread || exit $?

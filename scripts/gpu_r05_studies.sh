@@ -33,7 +33,7 @@ for study in "$@"; do
         -d gpurun_out/gram_trace_iso -o run --output-format csv -- python3 scripts/gram_ab.py ISO=200 || exit $?
       ;;
     gram_pmc)
-      B="python3 bench.py --no-cpu-baseline --workload c4"
+      B="python3 bench.py --full --no-cpu-baseline --workload c4"
       $S gram_pmc_sq 90 rocprofv3 --pmc SQ_WAVES SQ_INSTS_VMEM_WR SQ_WAIT_INST_ANY SQ_WAVE_CYCLES \
         SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_ACTIVE_INST_ANY GRBM_GUI_ACTIVE -d gpurun_out/gram_pmc_sq -o run \
         --output-format csv -- $B --steps 2 --warmup 1 --no-profile || exit $?
@@ -43,11 +43,11 @@ for study in "$@"; do
       ;;
     farm)
       $S farm_tests 300 python -u -m pytest tests/test_farm.py $T || exit $?
-      $S farm_c5 300 python -u bench.py --workload c5 --steps 2000 --warmup 200 --no-cpu-baseline || exit $?
-      LFM_FARM_GRAPH=0 $S farm_c5_nograph 300 python -u bench.py --workload c5 --steps 2000 --warmup 200 \
+      $S farm_c5 300 python -u bench.py --full --workload c5 --steps 2000 --warmup 200 --no-cpu-baseline || exit $?
+      LFM_FARM_GRAPH=0 $S farm_c5_nograph 300 python -u bench.py --full --workload c5 --steps 2000 --warmup 200 \
         --no-cpu-baseline || exit $?
       $S farm_c5_trace 180 rocprofv3 --kernel-trace --stats -d gpurun_out/farm_c5_trace -o run \
-        --output-format csv -- python3 bench.py --workload c5 --steps 300 --warmup 30 --no-cpu-baseline || exit $?
+        --output-format csv -- python3 bench.py --full --workload c5 --steps 300 --warmup 30 --no-cpu-baseline || exit $?
       ;;
     small)
       LFM_LIBRARY=ablibs/fitst/liblfm.so $S fit_stamps 120 python -u scripts/fit_stamps.py 150 || exit $?
@@ -55,15 +55,15 @@ for study in "$@"; do
       LFM_LIBRARY=ablibs/stamps/liblfm.so $S small_stamps 120 python -u scripts/small_stamps.py || exit $?
       $S fit_diag 200 python -u scripts/diag_fit.py || exit $?
       $S fit_pooled 200 python -u scripts/fit_pooled_time.py || exit $?
-      $S c5fit 300 python -u bench.py --workload c5fit --steps 20 --warmup 3 || exit $?
+      $S c5fit 300 python -u bench.py --full --workload c5fit --steps 20 --warmup 3 || exit $?
       ;;
     pipe)
       # the one-wave factor's pipelined LDL^T columns (LFM_SMALL_PIPE, default) against ablibs/nopipe
       # (make EXTRA=-DLFM_SMALL_PIPE=0): the MLL kernel's phase stamps, C5 lines interleaved
       LFM_LIBRARY=ablibs/stamps/liblfm.so $S pipe_stamps 120 python -u scripts/small_stamps.py || exit $?
       for i in 1 2; do
-        $S pipe_c5_on_$i 300 python -u bench.py --workload c5 --steps 3000 --warmup 300 --no-cpu-baseline || exit $?
-        LFM_LIBRARY=ablibs/nopipe/liblfm.so $S pipe_c5_off_$i 300 python -u bench.py --workload c5 \
+        $S pipe_c5_on_$i 300 python -u bench.py --full --workload c5 --steps 3000 --warmup 300 --no-cpu-baseline || exit $?
+        LFM_LIBRARY=ablibs/nopipe/liblfm.so $S pipe_c5_off_$i 300 python -u bench.py --full --workload c5 \
           --steps 3000 --warmup 300 --no-cpu-baseline || exit $?
       done
       $S pipe_split 200 python -u scripts/c5_host_split.py 3000 || exit $?

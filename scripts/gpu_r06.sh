@@ -29,16 +29,16 @@ for study in "$@"; do
       for r in 1 2; do
         for lib in ablibs/r05/liblfm.so ablibs/nohandoff/liblfm.so dis_project_amd/liblfm.so; do
           tag=$(basename "$(dirname "$lib")")
-          LFM_LIBRARY=$lib $S r06_handoff_c5_${tag}_$r 120 python -u bench.py --workload c5 --steps 3000 --warmup 300 --no-cpu-baseline || exit $?
-          LFM_LIBRARY=$lib $S r06_handoff_c5fit_${tag}_$r 120 python -u bench.py --workload c5fit --steps 30 --warmup 3 --no-cpu-baseline || exit $?
+          LFM_LIBRARY=$lib $S r06_handoff_c5_${tag}_$r 120 python -u bench.py --full --workload c5 --steps 3000 --warmup 300 --no-cpu-baseline || exit $?
+          LFM_LIBRARY=$lib $S r06_handoff_c5fit_${tag}_$r 120 python -u bench.py --full --workload c5fit --steps 30 --warmup 3 --no-cpu-baseline || exit $?
         done
       done
       ;;
     rehearse)
       R="python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1"
-      $S r06_reh_c5 300 $R --master-port 29532 bench.py --gpus 2 --workload c5 --steps 500 --warmup 50 \
+      $S r06_reh_c5 300 $R --master-port 29532 bench.py --full --gpus 2 --workload c5 --steps 500 --warmup 50 \
         --share-gpus --gather gloo --no-cpu-baseline || exit $?
-      $S r06_reh_c5fit 300 $R --master-port 29533 bench.py --gpus 2 --workload c5fit --steps 5 --warmup 1 \
+      $S r06_reh_c5fit 300 $R --master-port 29533 bench.py --full --gpus 2 --workload c5fit --steps 5 --warmup 1 \
         --share-gpus --gather gloo --no-cpu-baseline || exit $?
       ;;
     overlap)
@@ -48,7 +48,7 @@ for study in "$@"; do
       for r in 1 2; do
         for v in "LFM_OVERLAP=0" "LFM_OVERLAP=1" "LFM_OVL_AT=8192" "LFM_OVL_AT=4096" "LFM_OVL_RESERVE=32" "LFM_OVL_RESERVE=128"; do
           tag=${v//=/_}
-          env $v $S r06_ovl_${tag}_$r 300 python -u bench.py --workload c3 --steps 4 --warmup 1 --no-cpu-baseline || exit $?
+          env $v $S r06_ovl_${tag}_$r 300 python -u bench.py --full --workload c3 --steps 4 --warmup 1 --no-cpu-baseline || exit $?
         done
       done
       ;;
@@ -58,7 +58,7 @@ for study in "$@"; do
       for v in 0 1; do
         export LFM_OVERLAP=$v LFM_OVL_RESERVE=96
         $S r06_ovltrace_$v 300 rocprofv3 --kernel-trace --output-format csv -d gpurun_out/r06_ovltrace_$v -o run -- \
-          python3 bench.py --workload c3 --steps 2 --warmup 1 --no-cpu-baseline --no-profile || exit $?
+          python3 bench.py --full --workload c3 --steps 2 --warmup 1 --no-cpu-baseline --no-profile || exit $?
       done
       unset LFM_OVERLAP LFM_OVL_RESERVE
       ;;
@@ -66,14 +66,14 @@ for study in "$@"; do
       for r in 1 2; do
         for lib in ablibs/r05/liblfm.so dis_project_amd/liblfm.so; do
           tag=$(basename "$(dirname "$lib")")
-          LFM_LIBRARY=$lib $S r06_fitab_${tag}_$r 120 python -u bench.py --workload c5fit --steps 30 --warmup 3 --no-cpu-baseline || exit $?
+          LFM_LIBRARY=$lib $S r06_fitab_${tag}_$r 120 python -u bench.py --full --workload c5fit --steps 30 --warmup 3 --no-cpu-baseline || exit $?
         done
       done
       ;;
-    c2) $S r06_bench_c2 300 python -u bench.py --workload c2 --steps 20 --warmup 3 || exit $? ;;
-    c3) $S r06_bench_c3 400 python -u bench.py --workload c3 --steps 5 --warmup 1 --no-cpu-baseline || exit $? ;;
-    c5) $S r06_bench_c5 300 python -u bench.py --workload c5 --steps 3000 --warmup 300 || exit $? ;;
-    c5fit) $S r06_bench_c5fit 300 python -u bench.py --workload c5fit --steps 30 --warmup 3 || exit $? ;;
+    c2) $S r06_bench_c2 300 python -u bench.py --full --workload c2 --steps 20 --warmup 3 || exit $? ;;
+    c3) $S r06_bench_c3 400 python -u bench.py --full --workload c3 --steps 5 --warmup 1 --no-cpu-baseline || exit $? ;;
+    c5) $S r06_bench_c5 300 python -u bench.py --full --workload c5 --steps 3000 --warmup 300 || exit $? ;;
+    c5fit) $S r06_bench_c5fit 300 python -u bench.py --full --workload c5fit --steps 30 --warmup 3 || exit $? ;;
     *) echo "unknown study $study"; exit 2 ;;
   esac
 done

@@ -9,6 +9,6 @@ for lib in "$@"; do
   for c in FETCH_SIZE WRITE_SIZE; do
     LFM_LIBRARY=dis_project_amd/$lib.so LFM_S3_EVENTS=1 scripts/gpu_step.sh pmc_${lib}_$c 120 \
       rocprofv3 --pmc $c -d gpurun_out/pmc_${lib}_$c -o run --output-format csv -- \
-      python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-profile || exit $?
+      python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-profile || exit $?
   done
 done

@@ -21,7 +21,7 @@ set -u
 export TMPDIR=/tmp
 R=${1:-r05}
 mkdir -p gpurun_out
-B="python3 bench.py --no-cpu-baseline"
+B="python3 bench.py --full --no-cpu-baseline"
 S=scripts/gpu_step.sh
 $S prof_trace 300 rocprofv3 --kernel-trace --stats -d gpurun_out/prof_trace \
   -o run --output-format csv -- $B --steps 5 --warmup 2 || exit $?
@@ -48,11 +48,11 @@ PMC_T=127 PMC_KD=640 PMC_CIO=88 $S mfma_unit 120 rocprofv3 --kernel-trace \
 LFM_S3_EVENTS=2 $S mfma_bench 180 rocprofv3 --kernel-trace --pmc SQ_VALU_MFMA_BUSY_CYCLES \
   GRBM_GUI_ACTIVE -d gpurun_out/mfma_bench -o run --output-format csv -- \
   $B --steps 2 --warmup 1 --no-profile || exit $?
-$S bench_c2 300 python bench.py --steps 20 --warmup 5 || exit $?
-$S bench_c3 300 python bench.py --workload c3 --steps 5 --warmup 1 || exit $?
-$S bench_c4 300 python bench.py --workload c4 --steps 10 --warmup 2 || exit $?
-$S bench_c5 300 python bench.py --workload c5 --steps 2000 --warmup 200 || exit $?
-$S bench_c5fit 300 python bench.py --workload c5fit --steps 20 --warmup 3 || exit $?
+$S bench_c2 300 python bench.py --full --steps 20 --warmup 5 || exit $?
+$S bench_c3 300 python bench.py --full --workload c3 --steps 5 --warmup 1 || exit $?
+$S bench_c4 300 python bench.py --full --workload c4 --steps 10 --warmup 2 || exit $?
+$S bench_c5 300 python bench.py --full --workload c5 --steps 2000 --warmup 200 || exit $?
+$S bench_c5fit 300 python bench.py --full --workload c5fit --steps 20 --warmup 3 || exit $?
 $S prof_c5fit 300 rocprofv3 --kernel-trace --stats -d gpurun_out/prof_c5fit \
   -o run --output-format csv -- $B --workload c5fit --steps 10 --warmup 2 || exit $?
 $S timeline 180 python scripts/step_timeline.py --json gpurun_out/${R}_step_timeline.json || exit $?

@@ -41,7 +41,7 @@ def main():
     if os.path.exists(tb) and open(tb).read().strip():
         traced = json.loads(open(tb).read().strip().splitlines()[-1])
     evals_traced = (traced["steps"] + traced["warmup"]) if traced else None
-    lines = [f"# {rnd}: rocprofv3 --kernel-trace --stats, `bench.py --steps 5 --warmup 2 "
+    lines = [f"# {rnd}: rocprofv3 --kernel-trace --stats, `bench.py --full --steps 5 --warmup 2 "
              "--no-cpu-baseline` (7 evaluations at N = 16384)", "",
              "| kernel | calls | avg us | total ms | share % |", "|---|---|---|---|---|"]
     for r in rows:

@@ -58,6 +58,15 @@ def test_default_workload_follows_gpu_count():
     assert bench.parse(["--gpus", "8", "--workload", "c5", "--rounds", "4"]).rounds == 4
 
 
+def test_plain_run_is_lean_and_full_is_opt_in():
+    # a plain run times the steps only; the per-kernel events, the comparisons and the CPU
+    # baseline are behind --full, and the output dump is off unless a directory is named
+    a = bench.parse(["--gpus", "1", "--steps", "3", "--warmup", "1"])
+    assert (a.full, a.dump_outputs, a.steps, a.warmup) == (False, None, 3, 1)
+    a = bench.parse(["--full", "--dump-outputs", "out", "--no-cpu-baseline"])
+    assert a.full and a.dump_outputs == "out" and a.no_cpu_baseline and not a.no_profile
+
+
 def test_launcher_wires_every_rank(tmp_path, rank_script):
     out = tmp_path / "out"
     out.mkdir()
