@@ -9,8 +9,10 @@ from .dataset import Dataset, SyntheticP53Data, dataset_3d  # noqa: F401
 from .distributions import GaussianDistribution  # noqa: F401
 from .model import ExactLFM  # noqa: F401
 from .objectives import CustomConjMLL  # noqa: F401
+from .predict import BatchPredictor  # noqa: F401
 
 __all__ = [
+    "BatchPredictor",
     "CustomConjMLL",
     "Dataset",
     "ExactLFM",

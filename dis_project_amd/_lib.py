@@ -139,6 +139,8 @@ PRODUCT_SIGNATURES = [
     ("lfm_batch_fit_f64", c_int,
      [_c_ctx, c_void_p, POINTER(LfmAdam), c_int, c_int64, c_int64, _dptr, _dptr, _dptr, _dptr,
       _dptr]),
+    ("lfm_batch_posterior_f64", c_int,
+     [_c_ctx, c_void_p, _dptr, _dptr, _dptr, _dptr, _dptr, _dptr, _dptr, _dptr, _dptr]),
     ("lfm_log_prob_f64", c_int, [_c_ctx, _dptr, _dptr, c_int64, c_int64, _dptr, _dptr]),
     ("lfm_h_f64", c_int,
      [_c_ctx, POINTER(LfmHyp), POINTER(c_int64), POINTER(c_int64), _dptr, _dptr, c_int64, _dptr]),
@@ -188,7 +190,8 @@ DIAG_SIGNATURES = [
 
 # kernel classes in lfm_profile_read order (lfm_internal.h KClass)
 KCLASSES = ["tables", "gram_grid", "gram_direct", "augment", "potrf", "trsm", "syrk",
-            "finalize", "small_mll", "mean", "grad", "panel", "syrk_side", "small_grad"]
+            "finalize", "small_mll", "mean", "grad", "panel", "syrk_side", "small_grad",
+            "small_post"]
 
 _lib = None
 _diag = None

@@ -36,7 +36,7 @@ const char* const kClassName[K_NCLASS] = {"tables",   "gram_grid", "gram_direct"
                                           "augment",  "potrf",     "trsm",
                                           "syrk",     "finalize",  "small_mll",
                                           "mean",     "grad",      "panel",
-                                          "syrk_side", "small_grad"};
+                                          "syrk_side", "small_grad", "small_post"};
 
 int set_err(lfm_ctx* ctx, int code, const std::string& msg) {
   if (ctx) ctx->err = msg;
@@ -1839,6 +1839,113 @@ int lfm_batch_fit_f64(lfm_ctx* ctx, lfm_batch* batch, const lfm_adam* opt, int n
   if (worst)
     set_err(ctx, LFM_E_NOT_PD, "Cholesky failed during the fit of a batch problem (its loss "
                                "and parameters are NaN from that step on, as JAX's)");
+  return worst;
+}
+
+int lfm_batch_posterior_f64(lfm_ctx* ctx, lfm_batch* batch, const double* hyp,
+                            const double* diag_vec, const double* diag_add, const int64_t* m,
+                            const double* t, double* mean, double* var, double* cov,
+                            int* status) {
+  if (!ctx) return LFM_E_ARG;
+  if (!batch || !hyp || !diag_add || !m || !t || !mean)
+    return set_err(ctx, LFM_E_ARG, "batch / hyp / diag_add / m / t / mean is NULL");
+  if (!var && !cov) return set_err(ctx, LFM_E_ARG, "one of var / cov must be given");
+  if (batch->device != ctx->device) return set_err(ctx, LFM_E_ARG, "batch of another device");
+  const int64_t np = batch->nprob, nh = batch->nhyp;
+  if (batch->maxn > SMALL_GRAD_MAX || np > INT_MAX / 4)
+    return set_err(ctx, LFM_E_ARG, "lfm_batch_posterior_f64: every problem needs n <= 127; use "
+                                   "lfm_posterior_f64");
+  // per problem: its offsets in the packed arrays; one pass of the kernel covers `unit` test
+  // columns (64, or 256 when 64 would make more than 4096 workgroups)
+  std::vector<PostProb> pp((size_t)np);
+  int64_t sm = 0, sn = 0, sv = 0, sc = 0, ntiles = 0, wg64 = 0;
+  for (int64_t p = 0; p < np; ++p) {
+    const SmallProb& sp = batch->table[p];
+    if (m[p] < 1 || m[p] % sp.G != 0 || m[p] > (1 << 20))
+      return set_err(ctx, LFM_E_ARG, "lfm_batch_posterior_f64: m[p] must be a multiple of "
+                                     "num_genes in [1, 2^20] (mean_function, model.py:145-149)");
+    if (!small_post_cols(sp.n, sp.G, sp.T))
+      return set_err(ctx, LFM_E_ARG, "lfm_batch_posterior_f64: a problem's LDS map is past 160 KB");
+    const int64_t tb = (m[p] + 15) / 16;
+    pp[p] = PostProb{sm, sv, sc, (int)m[p], (int)sn, (int)ntiles, 0};
+    sm += m[p];
+    sn += sp.n;
+    sv += cov ? sp.n * m[p] : 0;
+    sc += cov ? m[p] * m[p] : 0;
+    ntiles += cov ? tb * (tb + 1) / 2 : 0;
+    wg64 += (m[p] + 63) / 64;
+    if (sm > ((int64_t)1 << 28) || sc > ((int64_t)1 << 29) || ntiles > INT_MAX / 2)
+      return set_err(ctx, LFM_E_ARG, "lfm_batch_posterior_f64: test inputs too large");
+  }
+  const int unit = wg64 <= 4096 ? 64 : 256;
+  int64_t nsplit = 1;
+  for (int64_t p = 0; p < np; ++p) {
+    const SmallProb& sp = batch->table[p];
+    const int u = std::min(unit, small_post_cols(sp.n, sp.G, sp.T));
+    nsplit = std::max(nsplit, (m[p] + u - 1) / u);
+  }
+  nsplit = std::min<int64_t>(nsplit, 1024);  // a workgroup takes every nsplit-th pass
+  DeviceGuard g(ctx->device);
+  DeviceTenancy tenancy(ctx, false);  // shared
+  if (int e = batch_prev_ok(ctx, batch)) return e;
+  // inputs, staged in pinned memory and uploaded in one copy: hyp | diag_add | diag_vec | t |
+  // the problem table; then the outputs: mean | var | V | cov | status
+  const size_t n_in = (size_t)nh + np + (diag_vec ? sn : 0) + 3 * sm;
+  const size_t b_in = n_in * 8 + (size_t)np * sizeof(PostProb);
+  const size_t n_out = 2 * (size_t)sm + sv + sc;
+  const size_t b_all = b_in + n_out * 8 + (size_t)np * sizeof(int);
+  int r = ensure_pinned(ctx, std::max<size_t>(b_in, 64 * sizeof(double)));
+  if (r) return r;
+  r = ensure(ctx, (void**)&ctx->xin, &ctx->xin_bytes, b_all);
+  if (r) return r;
+  double* hp = ctx->hpin;
+  std::memcpy(hp, hyp, nh * 8);
+  std::memcpy(hp + nh, diag_add, np * 8);
+  if (diag_vec) std::memcpy(hp + nh + np, diag_vec, sn * 8);
+  std::memcpy(hp + nh + np + (diag_vec ? sn : 0), t, 3 * sm * 8);
+  std::memcpy(hp + n_in, pp.data(), (size_t)np * sizeof(PostProb));
+  double* d_in = ctx->xin;
+  hipError_t e = hipMemcpyAsync(d_in, hp, b_in, hipMemcpyHostToDevice, ctx->stream);
+  if (e != hipSuccess) return hip_fail(ctx, e, "lfm_batch_posterior_f64: upload");
+  SmallPostLaunch f{};
+  f.probs = batch->dprobs;
+  f.offs = batch->doffs;
+  f.pp = reinterpret_cast<const PostProb*>(d_in + n_in);
+  f.nprob = (int)np;
+  f.nsplit = (int)nsplit;
+  f.unit = unit;
+  f.ntiles = (int)ntiles;
+  f.hyp = d_in;
+  f.dadd = d_in + nh;
+  f.dv = diag_vec ? d_in + nh + np : nullptr;
+  f.t = d_in + nh + np + (diag_vec ? sn : 0);
+  double* d_out = reinterpret_cast<double*>(reinterpret_cast<char*>(d_in) + b_in);
+  f.mean = d_out;
+  f.var = d_out + sm;  // always computed (the copy back is the caller's choice)
+  f.V = cov ? d_out + 2 * sm : nullptr;
+  f.cov = cov ? d_out + 2 * sm + sv : nullptr;
+  f.status = reinterpret_cast<int*>(d_out + n_out);
+  r = launch_small_post(ctx, f, small_post_lds(batch->table.data(), (int)np));
+  if (r) return r;
+  hipEventRecord(batch->done, ctx->stream);
+  std::vector<int> st((size_t)np);
+  e = hipMemcpyAsync(mean, f.mean, sm * 8, hipMemcpyDeviceToHost, ctx->stream);
+  if (e == hipSuccess && var)
+    e = hipMemcpyAsync(var, f.var, sm * 8, hipMemcpyDeviceToHost, ctx->stream);
+  if (e == hipSuccess && cov)
+    e = hipMemcpyAsync(cov, f.cov, sc * 8, hipMemcpyDeviceToHost, ctx->stream);
+  if (e == hipSuccess)
+    e = hipMemcpyAsync(st.data(), f.status, np * sizeof(int), hipMemcpyDeviceToHost, ctx->stream);
+  if (e != hipSuccess) return hip_fail(ctx, e, "lfm_batch_posterior_f64: download");
+  r = finish(ctx);
+  if (r) return r;
+  int worst = LFM_OK;
+  for (int64_t p = 0; p < np; ++p) {
+    const int s = st[p] ? LFM_E_NOT_PD : LFM_OK;
+    if (status) status[p] = s;
+    if (s) worst = s;
+  }
+  if (worst) set_err(ctx, LFM_E_NOT_PD, "Cholesky failed: non-positive pivot in a batch problem");
   return worst;
 }
 

@@ -30,6 +30,7 @@ enum KClass {
   K_PANEL,        // fused pending update + diagonal factor + panel solve (one block column)
   K_SIDE_SYRK,    // schedule 3: the tail of a step's trailing update on the side CUs (helper)
   K_SMALL_GRAD,   // one-workgroup-per-problem value + gradient (and the in-kernel fit)
+  K_SMALL_POST,   // batched posterior predictors of the small problems (and their covariance)
   K_NCLASS
 };
 
@@ -311,6 +312,35 @@ struct SmallFitLaunch {
 };
 int launch_small_fit(lfm_ctx* ctx, const SmallFitLaunch& f, size_t lds);
 int launch_small_args(lfm_ctx* ctx, SmallArgs& a, int nprob, int maxn, int maxg, int gridtab);
+// The batched posterior (lfm_batch_posterior_f64; lfm_small.hip small_post_kernel). One entry
+// per problem: where its test inputs, outputs and workspace start in the call's packed arrays.
+struct PostProb {
+  int64_t t_off;    // rows of t / entries of mean and var before this problem's (sum of m)
+  int64_t v_off;    // doubles of V = L^{-1} K(x, t) before this problem's n x m block
+  int64_t cov_off;  // doubles of cov before this problem's m x m block (sum of m^2)
+  int m;            // test rows
+  int dv_off;       // entries of diag_vec before this problem's (sum of n)
+  int tile0;        // covariance launch: 16 x 16 lower-triangle tiles before this problem's
+  int pad;
+};
+struct SmallPostLaunch {
+  const SmallProb* probs;  // the batch's table (x, y, the grid layout; dsb / sc unused)
+  const int* offs;         // [2 nprob]: each problem's vectors / scalars in the packed hyp
+  const PostProb* pp;      // [nprob]
+  int nprob, nsplit, unit; // grid (nprob, nsplit); a workgroup's pass is `unit` test columns
+  int ntiles;              // covariance launch: tiles of the whole batch
+  const double* hyp;       // device copies of the call's inputs
+  const double* dv;        // NULL: no diag_vec
+  const double* dadd;
+  const double* t;
+  double *mean, *var, *V, *cov;  // var or cov may be NULL (V: only with cov)
+  int* status;             // [nprob]: 1 + the first failing pivot, or 0
+};
+// columns of the K(x, t) panel a problem's workgroup keeps in LDS beside its map (a power of two,
+// 16 ... 256; 0: the problem does not fit), and the launch's LDS bytes over these problems
+int small_post_cols(int n, int G, int T);
+size_t small_post_lds(const SmallProb* probs, int nprob);
+int launch_small_post(lfm_ctx* ctx, const SmallPostLaunch& f, size_t lds);
 void small_batch_attrs();  // the MLL kernels' 160 KB LDS attribute (before launches / capture)
 // gridtab: the largest small_grid_extra of the problems (doubles; 0: none on the grid path)
 // LDS doubles a grid-layout problem adds to its map: the gram tables, the times, the block genes

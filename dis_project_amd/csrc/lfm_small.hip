@@ -7,7 +7,10 @@
 //   small_grad_kernel(_args)  its value and gradient with respect to the constrained
 //                             parameters (jax.value_and_grad at src/trainer.py:126);
 //   small_fit_kernel          JaxTrainer.fit (src/trainer.py:162-228): every problem's Adam steps
-//                             run inside the kernel, one workgroup per problem.
+//                             run inside the kernel, one workgroup per problem;
+//   small_post_kernel, small_post_cov_kernel
+//                             latent_predict / multi_gene_predict (src/model.py:420-514) of every
+//                             problem at its own test inputs (lfm_batch_posterior_f64).
 #include "lfm_dual.h"
 #include <mutex>
 
@@ -1619,6 +1622,204 @@ int launch_small_fit(lfm_ctx* ctx, const SmallFitLaunch& f, size_t lds) {
   hipLaunchKernelGGL(small_fit_kernel, dim3(f.nprob), dim3(256), lds, ctx->stream, a);
   prof_end(ctx, K_SMALL_GRAD, ev, 0, 0, ctx->stream);
   return hip_fail(ctx, hipGetLastError(), "small_fit_kernel");
+}
+
+// ------------------------------------------- batched posterior predictors (small problems)
+// latent_predict / multi_gene_predict (src/model.py:420-514) of every problem of a resident
+// batch at its own test inputs t (what src/utils.py:144-172 and notebook.py:91-110 call per
+// fitted model):
+//     S = K(x,x) + diag(diag_vec) + diag_add I = L L^T,  V = L^{-1} K(x,t),  z = L^{-1} (y - m(x)),
+//     mean = m(t) + V^T z,   var = diag K(t,t) - sum_k V_k^2,   cov = K(t,t) - V^T V.
+// small_post_kernel, grid (problem, split): every workgroup of a problem builds Sigma with
+// small_sigma's arithmetic (noise and jitter zero: the caller's diagonal is added after it) and
+// factors it column by column in LDS, which leaves L below A's diagonal, 1 / L_ii in invd and
+// z in A's row n. It then takes every gridDim.y-th pass of `unit` test columns: the panel
+// K(x, t_pass) is filled into LDS by the whole workgroup, then thread c forward-substitutes
+// column c against L (L's entries are broadcast reads, the column is the thread's own: no barrier
+// inside the substitution) and sums mean and var over k = 0 .. n - 1 in that order. A test
+// point's mean / var / V column depend on that point's row of t alone (mean_function's block
+// position j // (m / G) apart), not on unit, the split count or m.
+// small_post_cov_kernel, one workgroup per 16 x 16 tile of the lower triangles of all the
+// problems' covariances: cov_ij = k(t_i, t_j) - sum_k V_ki V_kj from V in HBM (the same sums in
+// the same order: diag(cov) is var bit for bit), written to (i, j) and (j, i).
+// Not positive definite: status[p] = 1 + the failing column, the problem's outputs NaN.
+__host__ __device__ inline size_t small_post_base(int n, int G, int T) {
+  // the problem's map, then invd [n]; the panel follows
+  return small_map(nullptr, n, G, T, n + 1 <= 64, 0, 0, nullptr) + (size_t)n;
+}
+__host__ __device__ inline int small_post_cols_hd(int n, int G, int T) {
+  const size_t base = small_post_base(n, G, T), cap = 160 * 1024 / sizeof(double);
+  for (int c = 256; c >= 16; c >>= 1)
+    if (base + (size_t)n * c <= cap) return c;
+  return 0;
+}
+int small_post_cols(int n, int G, int T) { return small_post_cols_hd(n, G, T); }
+size_t small_post_lds(const SmallProb* probs, int nprob) {
+  size_t mx = 0;
+  for (int p = 0; p < nprob; ++p) {
+    const SmallProb& q = probs[p];
+    mx = std::max(mx, small_post_base(q.n, q.G, q.T) +
+                          (size_t)q.n * small_post_cols_hd(q.n, q.G, q.T));
+  }
+  return mx * sizeof(double);
+}
+
+__global__ __launch_bounds__(256) void small_post_kernel(SmallPostLaunch a) {
+  extern __shared__ __attribute__((aligned(16))) double sm[];
+  const int p = blockIdx.x, split = blockIdx.y, tid = threadIdx.x;
+  const SmallProb P = a.probs[p];
+  const PostProb pq = a.pp[p];
+  const int n = P.n, M = n + 1, G = P.G;
+  const int unit = min(a.unit, small_post_cols_hd(n, G, P.T));  // a power of two
+  if ((int64_t)split * unit >= pq.m) return;  // no pass of this problem left for this split
+  const int tabs = M <= 64;
+  SmallMap m;
+  double* invd = sm + small_map(sm, n, G, P.T, tabs, 0, 0, &m);
+  double* panel = invd + n;
+  const int ld = m.ld;
+  double* A = m.A;
+  const double* dsb = a.hyp + a.offs[p];
+  for (int i = tid; i < 3 * G; i += 256) m.hyp[i] = dsb[i];
+  if (tid == 0) {
+    m.hyp[3 * G] = a.hyp[a.offs[a.nprob + p]];  // l
+    m.hyp[3 * G + 1] = 0.0;                     // small_sigma's noise and jitter: none
+    m.hyp[3 * G + 2] = 0.0;
+    m.red[8] = 0.0;
+  }
+  small_stage(P, m);
+  __syncthreads();
+  const HypDev h{m.hyp, m.hyp + G, m.hyp + 2 * G, G, m.hyp[3 * G]};
+  small_sigma(P, m, h, tabs);
+  __syncthreads();
+  const double dadd = a.dadd[p];
+  for (int c = tid; c < n; c += 256) {
+    const double dv = a.dv ? a.dv[pq.dv_off + c] : 0.0;
+    A[c * ld + c] = (A[c * ld + c] + dv) + dadd;
+  }
+  __syncthreads();
+  // right-looking Cholesky of the n + 1 augmented rows, row r on threads r and r + 128 (the
+  // columns of its update alternate between them); the diagonal keeps d_c, invd 1 / sqrt(d_c)
+  {
+    const int r = tid & 127, half = tid >> 7;
+    for (int c = 0; c < n; ++c) {
+      const double d = A[c * ld + c];
+      const double y = 1.0 / sqrt(d);
+      if (half == 0 && r > c && r < M) A[r * ld + c] *= y;
+      if (tid == 0) {
+        invd[c] = y;
+        if (!(d > 0.0) && m.red[8] == 0.0) m.red[8] = (double)(c + 1);
+      }
+      __syncthreads();
+      if (r > c && r < M) {
+        const double lrc = A[r * ld + c];
+        const int qe = min(r, n - 1);
+        for (int q = c + 1 + half; q <= qe; q += 2)
+          A[r * ld + q] = fma(-lrc, A[q * ld + c], A[r * ld + q]);
+      }
+      __syncthreads();
+    }
+  }
+  const int bad = (int)m.red[8];
+  if (split == 0 && tid == 0) a.status[p] = bad;
+  const double* z = A + n * ld;
+  const double* tp = a.t + 3 * pq.t_off;
+  const int64_t bs = pq.m / G;  // mean_function's block of the test inputs
+  const double nan = __builtin_nan("");
+  const int lu = __ffs(unit) - 1;
+  for (int64_t j0 = (int64_t)split * unit; j0 < pq.m; j0 += (int64_t)gridDim.y * unit) {
+    if (!bad) {
+      for (int e = tid; e < n * unit; e += 256) {
+        const int i = e >> lu, c = e & (unit - 1);
+        const int64_t j = j0 + c;
+        if (j < pq.m) {
+          const double* xi = m.xs + 3 * i;
+          const double* tj = tp + 3 * j;
+          panel[e] = kernel_ref(h, xi[0], xi[1], xi[2], tj[0], tj[1], tj[2]);
+        }
+      }
+    }
+    __syncthreads();
+    const int64_t j = j0 + tid;
+    if (tid < unit && j < pq.m) {
+      double mean = nan, var = nan;
+      if (!bad) {
+        double macc = 0.0, vacc = 0.0;
+        for (int i = 0; i < n; ++i) {
+          const double* Li = A + i * ld;
+          double s = panel[i * unit + tid];
+          for (int k = 0; k < i; ++k) s = fma(-Li[k], panel[k * unit + tid], s);
+          const double v = s * invd[i];
+          panel[i * unit + tid] = v;
+          macc = fma(v, z[i], macc);
+          vacc = fma(v, v, vacc);
+          if (a.V) a.V[pq.v_off + (int64_t)i * pq.m + j] = v;
+        }
+        const double* tj = tp + 3 * j;
+        mean = mean_at(h, tp, j, bs) + macc;
+        var = kernel_ref(h, tj[0], tj[1], tj[2], tj[0], tj[1], tj[2]) - vacc;
+      }
+      a.mean[pq.t_off + j] = mean;
+      if (a.var) a.var[pq.t_off + j] = var;
+    }
+    __syncthreads();  // the pass's columns are done before the next pass fills the panel
+  }
+}
+
+__global__ __launch_bounds__(256) void small_post_cov_kernel(SmallPostLaunch a) {
+  __shared__ double Vi[SMALL_GRAD_MAX * 16], Vj[SMALL_GRAD_MAX * 16];
+  const int tid = threadIdx.x;
+  // the problem of this tile: the last one whose first tile is not past it
+  int lo = 0, hi = a.nprob - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (a.pp[mid].tile0 <= (int)blockIdx.x) lo = mid;
+    else hi = mid - 1;
+  }
+  const int p = lo;
+  const PostProb pq = a.pp[p];
+  const int n = a.probs[p].n, G = a.probs[p].G, mt = pq.m;
+  int ti, tj;
+  tri_index((int)blockIdx.x - pq.tile0, &ti, &tj);
+  const int bad = a.status[p];
+  const double* V = a.V + pq.v_off;
+  if (!bad) {
+    for (int e = tid; e < n * 16; e += 256) {
+      const int k = e >> 4, c = e & 15;
+      const int ci = ti * 16 + c, cj = tj * 16 + c;
+      Vi[e] = ci < mt ? V[(int64_t)k * mt + ci] : 0.0;
+      Vj[e] = cj < mt ? V[(int64_t)k * mt + cj] : 0.0;
+    }
+  }
+  __syncthreads();
+  const int ty = tid >> 4, tx = tid & 15;
+  const int i = ti * 16 + ty, j = tj * 16 + tx;
+  if (i >= mt || j > i) return;
+  double v = __builtin_nan("");
+  if (!bad) {
+    const double* dsb = a.hyp + a.offs[p];
+    const HypDev h{dsb, dsb + G, dsb + 2 * G, G, a.hyp[a.offs[a.nprob + p]]};
+    double acc = 0.0;
+    for (int k = 0; k < n; ++k) acc = fma(Vi[k * 16 + ty], Vj[k * 16 + tx], acc);
+    const double* xi = a.t + 3 * (pq.t_off + i);
+    const double* xj = a.t + 3 * (pq.t_off + j);
+    v = kernel_ref(h, xi[0], xi[1], xi[2], xj[0], xj[1], xj[2]) - acc;
+  }
+  double* cov = a.cov + pq.cov_off;
+  cov[(int64_t)i * mt + j] = v;
+  cov[(int64_t)j * mt + i] = v;
+}
+
+int launch_small_post(lfm_ctx* ctx, const SmallPostLaunch& f, size_t lds) {
+  if (lds > 160 * 1024) return set_err(ctx, LFM_E_ARG, "small posterior batch: LDS past 160 KB");
+  static std::once_flag once;
+  std::call_once(once, [] { small_attr(reinterpret_cast<const void*>(&small_post_kernel)); });
+  hipEvent_t ev;
+  prof_begin(ctx, K_SMALL_POST, &ev, ctx->stream);
+  hipLaunchKernelGGL(small_post_kernel, dim3(f.nprob, f.nsplit), dim3(256), lds, ctx->stream, f);
+  if (f.cov)
+    hipLaunchKernelGGL(small_post_cov_kernel, dim3(f.ntiles), dim3(256), 0, ctx->stream, f);
+  prof_end(ctx, K_SMALL_POST, ev, 0, 0, ctx->stream);
+  return hip_fail(ctx, hipGetLastError(), "small_post_kernel");
 }
 
 size_t small_grid_extra(int n, int G, int T) {

@@ -1,0 +1,155 @@
+"""``BatchPredictor`` — the predict half of the reference's small-problem workflow, batched.
+
+The reference fits every replicate x leave-one-gene-out model (src/notebook.py:33-75) and then
+calls ``latent_predict`` and ``multi_gene_predict`` (src/model.py:420-514) on each fitted model
+(src/notebook.py:91-110, src/utils.py:144-172). ``trainer.BatchTrainer`` runs the fits of the
+whole farm in one launch; this class does the same for the predictors: the training data of
+every problem is registered in HBM once (``lfm_batch_create``) and one
+``lfm_batch_posterior_f64`` call evaluates every problem at its own test inputs. The assembly of
+the returned ``GaussianDistribution`` is ``ExactLFM.latent_predict`` / ``multi_gene_predict``'s.
+"""
+
+from __future__ import annotations
+
+from typing import Sequence
+
+import numpy as np
+
+from . import _lib
+from ._lib import as_f64, dptr
+
+
+# ------------------------------------------------------------------ pure helpers
+def pack_test_inputs(test_inputs, genes: Sequence[int]):
+    """Test inputs of P problems as lfm_batch_posterior_f64 takes them: (t [sum m_p, 3] packed in
+    problem order, m [P] int64). ``test_inputs`` is one [m, 3] array shared by every problem or a
+    sequence of P such arrays. Every m_p must be >= 1 and a multiple of that problem's num_genes
+    (mean_function's broadcast, model.py:145-149), else ValueError."""
+    genes = [int(g) for g in genes]
+    if isinstance(test_inputs, np.ndarray) and test_inputs.ndim == 2:
+        per = [test_inputs] * len(genes)
+    else:
+        per = list(test_inputs)
+        if len(per) != len(genes):
+            raise ValueError("one test-input array per problem (or one shared [m, 3] array)")
+    ts = []
+    for p, (t, G) in enumerate(zip(per, genes)):
+        t = as_f64(t)
+        if t.ndim != 2 or t.shape[1] != 3:
+            raise ValueError(f"problem {p}: test inputs must be [m, 3]")
+        if t.shape[0] < 1 or t.shape[0] % G != 0:
+            raise ValueError(f"problem {p}: m = {t.shape[0]} test rows is not a positive multiple "
+                             f"of num_genes = {G} (mean_function, model.py:145-149)")
+        ts.append(t)
+    m = np.asarray([t.shape[0] for t in ts], np.int64)
+    return np.ascontiguousarray(np.concatenate(ts, axis=0)), m
+
+
+def unpack_outputs(m, mean, var=None, cov=None):
+    """lfm_batch_posterior_f64's packed outputs as per-problem arrays: a list of (mean [m_p],
+    var [m_p] or None, cov [m_p, m_p] or None)."""
+    m = np.asarray(m, np.int64)
+    if np.any(m < 1):
+        raise ValueError("every m must be >= 1")
+    mean = np.asarray(mean)
+    if mean.shape != (int(m.sum()),) or (var is not None and np.shape(var) != mean.shape) or \
+            (cov is not None and np.shape(cov) != (int((m * m).sum()),)):
+        raise ValueError("packed outputs do not match m")
+    out, o1, o2 = [], 0, 0
+    for k in (int(v) for v in m):
+        out.append((mean[o1:o1 + k].copy(),
+                    None if var is None else np.asarray(var)[o1:o1 + k].copy(),
+                    None if cov is None else np.asarray(cov)[o2:o2 + k * k].reshape(k, k).copy()))
+        o1 += k
+        o2 += k * k
+    return out
+
+
+# ------------------------------------------------------------------ the predictor
+class BatchPredictor:
+    """``latent_predict`` / ``multi_gene_predict`` of P (model, training data) problems in one
+    call each. ``train_datas``: the P53-style data objects ``ExactLFM.latent_predict`` takes
+    (``dataset_3d`` is applied to each; n <= 127 per problem). ``models`` (one ExactLFM per
+    problem, e.g. ``BatchTrainer.fit``'s) are read at every call. ``status`` holds the last
+    call's per-problem codes (LFM_E_NOT_PD: that problem's outputs are NaN, as under JAX)."""
+
+    def __init__(self, train_datas, ctx=None):
+        from .dataset import Dataset, dataset_3d
+        from .farm import BatchEvaluator
+
+        self.ctx = ctx or _lib.get_context()
+        datasets, var = [], []
+        for d in train_datas:
+            x, y, v = dataset_3d(d)
+            datasets.append(Dataset(as_f64(x).reshape(-1, 3), as_f64(y).reshape(-1, 1)))
+            var.append(as_f64(v).reshape(-1))
+        if not datasets:
+            raise ValueError("no training data")
+        self.variances = np.ascontiguousarray(np.concatenate(var))
+        self._ev = BatchEvaluator(self.ctx, datasets)
+        self.status = np.zeros(len(datasets), np.int32)
+
+    def __len__(self):
+        return len(self._ev.datasets)
+
+    def _posterior(self, models, test_inputs, diag_add, want_cov):
+        models = list(models)
+        if len(models) != len(self):
+            raise ValueError("one model per registered problem")
+        genes = [int(mm.num_genes) for mm in models]
+        t, m = pack_test_inputs(test_inputs, genes)
+        hyp = self._ev.pack(models)  # lfm_batch_mll_f64's layout; registers this gene layout
+        batch = self._ev.batch
+        dadd = as_f64(diag_add).reshape(-1)
+        mean = np.empty(int(m.sum()))
+        var = np.empty_like(mean)
+        cov = np.empty(int((m * m).sum())) if want_cov else None
+        self.status = np.zeros(len(models), np.int32)
+        rc = self.ctx.lib.lfm_batch_posterior_f64(
+            self.ctx.handle, batch, dptr(hyp), dptr(self.variances), dptr(dadd), dptr(m), dptr(t),
+            dptr(mean), dptr(var), dptr(cov) if want_cov else None, dptr(self.status))
+        self.ctx.check(rc, allow_not_pd=True)
+        return unpack_outputs(m, mean, var, cov)
+
+    def latent_predict(self, models, test_inputs):
+        """model.py:420-465 per problem: S = K(x,x) + diag(variances) + jitter I;
+        scale = diag(var + jitter) + jitter I. No covariance is computed."""
+        from .distributions import GaussianDistribution
+
+        models = list(models)
+        res = self._posterior(models, test_inputs, [mm.jitter for mm in models], False)
+        out = []
+        for (mean, var, _), mm in zip(res, models):
+            scale = np.diag(var + mm.jitter) + np.eye(mean.shape[0]) * mm.jitter
+            out.append(GaussianDistribution(mean, scale, device=self.ctx.device))
+        return out
+
+    def multi_gene_predict(self, models, test_inputs):
+        """model.py:467-514 per problem: S = K(x,x) + diag(variances) + obs_stddev^2 I;
+        scale = K(t,t) - K(t,x) S^{-1} K(x,t) + jitter I."""
+        from .distributions import GaussianDistribution
+
+        models = list(models)
+        res = self._posterior(models, test_inputs, [mm.obs_stddev ** 2 for mm in models], True)
+        out = []
+        for (mean, _, cov), mm in zip(res, models):
+            scale = cov + np.eye(mean.shape[0]) * mm.jitter
+            out.append(GaussianDistribution(mean, scale, device=self.ctx.device))
+        return out
+
+    def marginals(self, models, test_inputs, kind: str = "latent"):
+        """(mean, var) per problem — the diagonal of ``latent_predict``'s (kind "latent") or
+        ``multi_gene_predict``'s (kind "gene") scale — without forming any covariance: what the
+        plots of utils.py:144-172 read."""
+        models = list(models)
+        if kind == "latent":
+            res = self._posterior(models, test_inputs, [mm.jitter for mm in models], False)
+            return [(mean, (var + mm.jitter) + mm.jitter) for (mean, var, _), mm in zip(res, models)]
+        if kind == "gene":
+            res = self._posterior(models, test_inputs, [mm.obs_stddev ** 2 for mm in models],
+                                  False)
+            return [(mean, var + mm.jitter) for (mean, var, _), mm in zip(res, models)]
+        raise ValueError('kind must be "latent" or "gene"')
+
+    def close(self):
+        self._ev.close()

@@ -240,6 +240,38 @@ int lfm_posterior_f64(lfm_ctx* ctx, const double* x, const double* y, int64_t n,
                       const double* diag_vec, double diag_add, const double* t, int64_t m,
                       const lfm_hyp* hyp, double* mean, double* cov);
 
+/* latent_predict / multi_gene_predict (model.py:420-514) of every problem of a resident batch
+ * (lfm_batch_create) at its own test inputs, in a fixed number of launches whatever the problem
+ * count — the predict half of the fit-then-predict workflow (notebook.py:91-110 and
+ * utils.py:144-172 call the two predictors once per fitted model). Per problem p:
+ *   S_p = K(x_p,x_p) + diag(diag_vec_p) + diag_add[p] I,
+ *   mean = m(t_p) + K(t_p,x_p) S_p^{-1} (y_p - m(x_p)),  cov = K(t_p,t_p) - K(t_p,x_p) S_p^{-1} K(x_p,t_p).
+ *   hyp       the packed layout of lfm_batch_mll_f64; only D, S, B and l are read (the diagonal's
+ *             noise comes from diag_vec / diag_add, as in lfm_posterior_f64: the callers' jitter
+ *             and sigma^2 are applied by the shim, dis_project_amd.predict.BatchPredictor)
+ *   diag_vec  packed [sum n_p] in problem order, or NULL;  diag_add [nprob]
+ *   m         [nprob] test rows per problem, each >= 1 and a multiple of that problem's
+ *             num_genes (mean_function, model.py:145-149)
+ *   t         packed [sum m_p x 3]; gene indices truncate, wrap and clamp as those of x, and any
+ *             mix of flags is allowed (kxx, kxf, kfx, kff)
+ *   mean      packed [sum m_p]
+ *   var       packed [sum m_p], the diagonal of cov (bit for bit); may be NULL
+ *   cov       packed [sum m_p^2], each problem's dense row-major m_p x m_p, exactly symmetric;
+ *             may be NULL, and then no off-diagonal K(t,t) entry is evaluated (latent_predict
+ *             and the plots read the marginals only). One of var / cov must be given.
+ *   status    [nprob] optional: LFM_OK or LFM_E_NOT_PD per problem
+ * Every problem needs n <= 127 (as lfm_batch_mll_grad_f64) and its LDS map within 160 KB, else
+ * LFM_E_ARG (lfm_posterior_f64 takes any n); a NULL required pointer or a bad m is LFM_E_ARG.
+ * A problem that is not positive definite gets NaN outputs and its status, and the call returns
+ * LFM_E_NOT_PD; every other problem's outputs are valid and the same bits as without it. A test
+ * point's mean and variance depend on its own row of t (and, through mean_function's block
+ * position, on its index and m_p), not on how the batch is split over workgroups. Synchronous;
+ * holds the device's lock shared; no device-side waits or atomics: the same inputs give the
+ * same bits. */
+int lfm_batch_posterior_f64(lfm_ctx* ctx, lfm_batch* batch, const double* hyp,
+                            const double* diag_vec, const double* diag_add, const int64_t* m,
+                            const double* t, double* mean, double* var, double* cov, int* status);
+
 /* ------------------- GaussianDistribution(loc, scale).log_prob(y) (gpjax 0.8.2) */
 /* scale is a dense SPD n x n (row-major, leading dim lds; lower triangle read). */
 int lfm_log_prob_f64(lfm_ctx* ctx, const double* loc, const double* scale, int64_t n,
