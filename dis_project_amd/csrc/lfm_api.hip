@@ -26,10 +26,6 @@
 
 using namespace lfm;
 
-#ifndef LFM_GRAM_FUSE_DEFAULT
-#define LFM_GRAM_FUSE_DEFAULT 1
-#endif
-
 namespace lfm {
 
 const char* const kClassName[K_NCLASS] = {"tables",   "gram_grid", "gram_direct",
@@ -686,7 +682,7 @@ hipError_t create_streams(lfm_ctx* ctx) {
   ctx->sched = env_int_api("LFM_SCHED", 3) == 1 ? 1 : 3;
   ctx->s3_events = (int)env_int_api("LFM_S3_EVENTS", 0);
   ctx->grad_direct = env_int_api("LFM_GRAD_DIRECT", 0) != 0;
-  ctx->gram_fuse = env_int_api("LFM_GRAM_FUSE", LFM_GRAM_FUSE_DEFAULT) != 0;
+  ctx->gram_fuse = env_int_api("LFM_GRAM_FUSE", 1) != 0;
   ctx->w4min = env_int_api("LFM_W4_MIN", 6144);
   ctx->w2min = env_int_api("LFM_W2_MIN", -1);
   ctx->w0 = std::max(1, env_int_api("LFM_W0", 1));

@@ -42,14 +42,24 @@ static constexpr int NB = 128;       // panel width (block column)
 static constexpr int IB = 16;        // inner block of the diagonal factor / panel solve
 static constexpr int ST = 128;       // SYRK output tile edge
 static constexpr int KB = 16;        // SYRK K-step staged through LDS
-#ifndef LFM_LDS_PAD
-#define LFM_LDS_PAD 2
-#endif
 // LDS row stride of a staged K stage: KS + LDP doubles. ds_read_b64 banks by (a / 4) mod 64
 // per 32-lane half: the MFMA fragment reads (16 rows x 4 k, and 4 rows x 4 k) are conflict-free
 // at a stride of 18 (and 66 for the chain's 64-deep stages); at 17 the 16-row reads were 2-way
 // conflicted. Measured: -0.57 ms per C2 evaluation (scripts/ab_lib.py, 5 rounds), same bits.
-static constexpr int LDP = LFM_LDS_PAD;
+static constexpr int LDP = 2;
+// schedule 1's 64-row SYRK (syrk_kernel<., 64>): workgroups per CU in its launch bounds
+static constexpr int SLAB_WGS = 3;
+// schedule-3 MLL bulk super-panel width in block columns (DESIGN.md §4)
+static constexpr int WBULK = 5;
+// the same for the gradient's bordered factorisation (its window keeps every step full width)
+static constexpr int WBORD = 4;
+// rest-triangle enumeration: tile rows in groups of Q, Q x Q supertiles within a group
+static constexpr int SUPERTILE = 6;
+// Bulk trailing update (step_kernel's update units): K depth of one LDS stage (32: 130 VGPRs +
+// 64 AGPRs, 2 waves / SIMD; DESIGN.md §4)
+static constexpr int STEP_KS = 16;
+// tall units (X_{s+1} = A21 Bd) in 64 x (128 / TALL_SPLIT) pieces
+static constexpr int TALL_SPLIT = 2;
 static constexpr int STATUS_NONE = INT_MAX;
 constexpr int PANEL_TIMEOUT = STATUS_TIMEOUT;  // status: a bounded device-side wait ran out
 // Which wait ran out first (status[1], reported in LFM_E_TIMEOUT's message): 1 tall unit on the
@@ -145,31 +155,16 @@ __device__ __forceinline__ void pin16(double (&p)[16]) {
 
 // ---------------------------------------------------------------- potrf
 // Two doubles; COH: device-coherent loads that bypass the CU's vector L1, which may hold stale
-// lines of data another CU wrote (write-through) in the same launch. LFM_COH_NT (default):
-// one 16-B nontemporal load (global_load_dwordx4 nt, L2-served like sc1); else two 8-B
-// agent-scope relaxed atomic loads (sc1).
-#ifndef LFM_COH_NT
-#define LFM_COH_NT 1
-#endif
-#ifndef LFM_LEAF_SHARE
-#define LFM_LEAF_SHARE 1
-#endif
-#ifndef LFM_KK_UNROLL
-#define LFM_KK_UNROLL 1
-#endif
+// lines of data another CU wrote (write-through) in the same launch: one 16-B nontemporal load
+// (global_load_dwordx4 nt, L2-served like sc1).
 typedef double double2v __attribute__((ext_vector_type(2)));
 template <bool COH>
 __device__ __forceinline__ double2 ld2(const double* p) {
   if (COH) {
     double2 v;
-#if LFM_COH_NT
     const double2v t = __builtin_nontemporal_load(reinterpret_cast<const double2v*>(p));
     v.x = t.x;
     v.y = t.y;
-#else
-    v.x = __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    v.y = __hip_atomic_load(p + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#endif
     return v;
   }
   return *reinterpret_cast<const double2*>(p);
@@ -232,15 +227,7 @@ __device__ __forceinline__ void potrf_block(double* __restrict__ Mb, double* __r
   // pst (diagnostics, NULL: off): s_memrealtime after the load (0), panel iterations 0, 3, 6
   // (1-3), the loop (4), inverse block row 6 (5) and 7 (6), the block store (7)
   auto pstamp = [&](int p) {
-#ifndef LFM_PSTAMP_LEAF
     if (pst && threadIdx.x == 0) pst[p] = __builtin_amdgcn_s_memrealtime();
-#endif
-  };
-  // diagnostics build (-DLFM_PSTAMP_LEAF): panel iteration 3 by phase and wave instead
-  auto lstamp = [&](int ib, int p, int wv) {
-#ifdef LFM_PSTAMP_LEAF
-    if (pst && ib == 3 && threadIdx.x == 64 * wv) pst[p] = __builtin_amdgcn_s_memrealtime();
-#endif
   };
   __shared__ double pvs[NB];  // unscaled pivots
   __shared__ double ipv[NB];  // 1 / L_cc
@@ -472,7 +459,6 @@ __device__ __forceinline__ void potrf_block(double* __restrict__ Mb, double* __r
 #pragma unroll 1
   for (int ib = 0; ib < NB / IB; ++ib) {
     const int c0 = ib * IB;
-    lstamp(ib, 0, 0);
     // (2) rows below: x_c = (p_c - sum_{q<c} x_q L[c][q]) / L_cc, swept right-looking: once
     // x_c is known it is subtracted from every later p_q at once. Each p_q still accumulates
     // its terms in increasing c (bit-identical to the left-looking sum), but the dependent
@@ -501,24 +487,20 @@ __device__ __forceinline__ void potrf_block(double* __restrict__ Mb, double* __r
         for (int q = 0; q < IB; ++q) MS(row, c0 + q) = p[q];
       }
     }
-    lstamp(ib, 1, 0);
     __syncthreads();
-    lstamp(ib, 2, 0);
     if (nr == 0) break;
     // (3) wave 0: next diagonal block, then its leaf; waves 1-3: the other trailing tiles
     const int nrb = nr / IB;
     // the early panels' wide trailing triangles: wave 0 takes its last k0 tiles after the leaf
     // (28 tiles -> 4, 21 -> 2, 15 -> 1), so the four waves reach the barrier together
     const int ntiles = nrb * (nrb + 1) / 2;
-    const int k0 = LFM_LEAF_SHARE ? max(0, (ntiles - 11) / 4) : 0;
+    const int k0 = max(0, (ntiles - 11) / 4);
     if (w == 0) {
       if (PH & 4) {
         tile_update(c0 + IB, c0 + IB, c0);
         wave_lds_fence();
       }
-      lstamp(ib, 3, 0);
       if (PH & 1) leaf(ib + 1);
-      lstamp(ib, 4, 0);
       if (PH & 4) {
         for (int tc = ntiles - k0; tc < ntiles; ++tc) {
           int ti, tj;
@@ -545,10 +527,7 @@ __device__ __forceinline__ void potrf_block(double* __restrict__ Mb, double* __r
       else
         for (int J = w - 2; J < ib - 1; J += 2) linv_block(ib - 1, J);
     }
-    lstamp(ib, 5, 1);
-    lstamp(ib, 6, 3);
     __syncthreads();
-    lstamp(ib, 7, 0);
     if (ib == 0 || ib == 3 || ib == 6) pstamp(ib == 0 ? 1 : ib == 3 ? 2 : 3);
   }
   pstamp(4);
@@ -829,7 +808,7 @@ __device__ __forceinline__ void gemm_accumulate(const double* __restrict__ pi, i
     __syncthreads();
     if (k0 + KS < kd) gload(k0 + KS);
     {
-#pragma unroll LFM_KK_UNROLL
+#pragma unroll 1
       for (int kk = 0; kk < KS; kk += 4) {
         double bb[4];
 #pragma unroll
@@ -909,7 +888,7 @@ __device__ __forceinline__ void gemm_accumulate16(const double* __restrict__ pi,
     }
     __syncthreads();
     if (k0 + KS < kd) gload(k0 + KS);
-#pragma unroll LFM_KK_UNROLL
+#pragma unroll 1
     for (int kk = 0; kk < KS; kk += 4) {
       double bb[JB], a[RB];
 #pragma unroll
@@ -932,71 +911,16 @@ struct Panel {
   int64_t ld, r0;
 };
 
-// schedule 1's 64-row SYRK (syrk_kernel<., 64>): workgroups per CU in its launch bounds
-#ifndef LFM_SLAB_WGS
-#define LFM_SLAB_WGS 3
-#endif
-// schedule-3 MLL bulk super-panel width in block columns (DESIGN.md §4)
-#ifndef LFM_WBULK
-#define LFM_WBULK 5
-#endif
-// the same for the gradient's bordered factorisation (its window keeps every step full width)
-#ifndef LFM_WBORD
-#define LFM_WBORD 4
-#endif
-// rest-triangle enumeration: tile rows in groups of Q, Q x Q supertiles within a group (1: row
-// by row)
-#ifndef LFM_SUPERTILE
-#define LFM_SUPERTILE 6
-#endif
-// rectangular bands (the step kernel's next-super-panel columns) enumerated row by row (0:
-// column by column)
-#ifndef LFM_BAND_ROWS
-#define LFM_BAND_ROWS 1
-#endif
-// Bulk trailing update (step_kernel's update units): K depth of one LDS stage (32: 130 VGPRs +
-// 64 AGPRs, 2 waves / SIMD; DESIGN.md §4)
-#ifndef LFM_STEP_KS
-#define LFM_STEP_KS 16
-#endif
-// trailing-update tile body on v_mfma_f64_16x16x4_f64 (1) or the 4x4x4_4b blocks (0)
-#ifndef LFM_MFMA16
-#define LFM_MFMA16 1
-#endif
-// tall units (X_{s+1} = A21 Bd) in 64 x (128 / LFM_TALL_SPLIT) pieces
-#ifndef LFM_TALL_SPLIT
-#define LFM_TALL_SPLIT 2
-#endif
-// the chain's 32 x 32 products (gemm32) on v_mfma_f64_16x16x4_f64 (1) or 4x4x4_4b (0)
-#ifndef LFM_G32_M16
-#define LFM_G32_M16 1
-#endif
-// tall units dealt round-robin to the XCDs (1) or in contiguous ranges like the other roles (0)
-#ifndef LFM_TALL_RR
-#define LFM_TALL_RR 1
-#endif
-// round-robin deal in groups of the LFM_TALL_SPLIT pieces of one row block (1): the pieces that
-// read the same A21 rows go to the same XCD back to back, so the second reads them from that
-// XCD's L2; else (0) piece by piece, consecutive pieces on different XCDs (round 3)
-#ifndef LFM_TALL_GROUP
-#define LFM_TALL_GROUP 1
-#endif
-// workgroups of the tall segment: a multiple of 8 (XCDs), of 8 LFM_TALL_SPLIT when grouped
+// workgroups of the tall segment: a multiple of 8 TALL_SPLIT (8 XCDs, the pieces of one row block
+// back to back: tall_or_xcd_range)
 __host__ __device__ constexpr int64_t tall_grid(int64_t nt) {
-  return (LFM_TALL_RR && LFM_TALL_GROUP) ? (nt + 8 * LFM_TALL_SPLIT - 1) / (8 * LFM_TALL_SPLIT) *
-                                               (8 * LFM_TALL_SPLIT)
-                                         : (nt + 7) / 8 * 8;
+  return (nt + 8 * TALL_SPLIT - 1) / (8 * TALL_SPLIT) * (8 * TALL_SPLIT);
 }
-// C tile loads of the trailing update: device-coherent, or plain / nontemporal (LFM_C_NT bit 0;
-// bit 1: nontemporal C stores)
-#ifndef LFM_C_NT
-#define LFM_C_NT 3
-#endif
+// C tile loads of the trailing update: device-coherent or nontemporal (the C stores likewise)
 template <bool COH>
 __device__ __forceinline__ double ldc(const double* p) {
   if (COH) return ld1<true>(p);
-  if (LFM_C_NT & 1) return __builtin_nontemporal_load(p);
-  return *p;
+  return __builtin_nontemporal_load(p);
 }
 
 // The tile body of syrk_unit: C (TR x 128 at row i0, column j0) -= panel rows i0.. x rows j0..
@@ -1016,13 +940,8 @@ __device__ __forceinline__ void syrk_tile(double* __restrict__ A, int64_t lda, P
   double* Cb = A + (i0 + wr + lk) * lda + j0 + wc + li;  // C[wr + lk][wc + li]
   const int ld4 = (int)(4 * lda);  // row-group stride (elements); 60 * ld4 < 2^31 for lda < 2^23
 
-#if LFM_MFMA16
   double4v acc4[IRN / 4][4];
 #define ACC(ir, jr) acc4[(ir) >> 2][jr][(ir) & 3]
-#else
-  double acc[IRN][4];
-#define ACC(ir, jr) acc[ir][jr]
-#endif
   if constexpr (GEN) {
     constexpr int WIN = ST + TR - 1;
     static_assert(4 * WIN + 3 * TR + 3 * ST <= (TR + ST) * (KS + LDP), "gram windows in sP");
@@ -1088,13 +1007,8 @@ __device__ __forceinline__ void syrk_tile(double* __restrict__ A, int64_t lda, P
       for (int jr = 0; jr < 4; ++jr)
         ACC(ir, jr) = (CIO && CLOAD) ? -ldc<LDCOH>(&Cb[ir * ld4 + jr * 16]) : 0.0;
   }
-#if LFM_MFMA16
   gemm_accumulate16<TR, false, LDCOH, KS>(P.p + (i0 - P.r0) * P.ld, P.ld,
                                           P.p + (j0 - P.r0) * P.ld, P.ld, kd, acc4, sP);
-#else
-  gemm_accumulate<TR, false, LDCOH, KS>(P.p + (i0 - P.r0) * P.ld, P.ld, P.p + (j0 - P.r0) * P.ld,
-                                        P.ld, kd, acc, sP);
-#endif
 
   int ld4s = ld4;
   asm volatile("" : "+v"(ld4s));  // recompute store addresses instead of keeping 64 pointers live
@@ -1108,10 +1022,8 @@ __device__ __forceinline__ void syrk_tile(double* __restrict__ A, int64_t lda, P
         if (coh)
           __hip_atomic_store(&Cb[ir * ld4s + jr * 16], -ACC(ir, jr), __ATOMIC_RELAXED,
                              __HIP_MEMORY_SCOPE_AGENT);
-        else if (LFM_C_NT & 2)
-          __builtin_nontemporal_store(-ACC(ir, jr), &Cb[ir * ld4s + jr * 16]);
         else
-          Cb[ir * ld4s + jr * 16] = -ACC(ir, jr);
+          __builtin_nontemporal_store(-ACC(ir, jr), &Cb[ir * ld4s + jr * 16]);
       }
       if (!CIO && ACC(ir, jr) == 1.2345e300) Cb[0] = 0.0;  // keep the MFMAs live
     }
@@ -1127,7 +1039,7 @@ __device__ __forceinline__ void unit_tile(int T, int tj_lo, int tj_hi, int64_t b
                                           int* ti_out, int* tj_out) {
   constexpr int SUB = ST / TR;  // row tiles per 128 rows
   int ti, tj;  // ti in TR-row units
-  if (LFM_BAND_ROWS && tj_hi - tj_lo <= kBandMaxCols && ti0 >= tj_hi) {
+  if (tj_hi - tj_lo <= kBandMaxCols && ti0 >= tj_hi) {
     // rectangular band (every row below the band's columns): row by row, so consecutive units
     // share a row panel and the band's few column panels stay in L2
     const int nb = tj_hi - tj_lo;
@@ -1145,7 +1057,7 @@ __device__ __forceinline__ void unit_tile(int T, int tj_lo, int tj_hi, int64_t b
     ti = SUB * max(tj, ti0) + (int)b;
   } else {
     // triangle of 128-tiles over tile columns [tj_lo, T), SUB row slabs of TR rows per tile;
-    // groups of LFM_SUPERTILE tile rows are enumerated in order (so a launch can skip the first
+    // groups of SUPERTILE tile rows are enumerated in order (so a launch can skip the first
     // ones: b offset), within a group Q x Q supertiles in turn, tiles row by row within those:
     // consecutive units (one XCD's co-resident workgroups) then share row and column panels
     const int sub = (int)(b % SUB);
@@ -1153,7 +1065,7 @@ __device__ __forceinline__ void unit_tile(int T, int tj_lo, int tj_hi, int64_t b
     int a = (int)((sqrt(8.0 * (double)b + 1.0) - 1.0) * 0.5);
     while ((int64_t)(a + 1) * (a + 2) / 2 <= b) ++a;
     while ((int64_t)a * (a + 1) / 2 > b) --a;
-    constexpr int Q = LFM_SUPERTILE;
+    constexpr int Q = SUPERTILE;
     if constexpr (Q > 1) {
       const int R = a / Q, r0 = R * Q, qr = min(Q, T - tj_lo - r0);
       const int64_t off = b - (int64_t)r0 * (r0 + 1) / 2;
@@ -1230,7 +1142,7 @@ __device__ __forceinline__ void xcd_range(int64_t nunits, int x, int64_t* lo, in
 // Trailing update (mode by tile-column range, see syrk_unit); skip: units of the triangle
 // enumeration left out at its start (tile rows already updated elsewhere).
 template <bool CIO, int TR>
-__global__ __launch_bounds__(256, TR == 64 ? LFM_SLAB_WGS : 2) void syrk_kernel(
+__global__ __launch_bounds__(256, TR == 64 ? SLAB_WGS : 2) void syrk_kernel(
     double* __restrict__ A, int64_t lda, int64_t s, Panel P, int kd, int T, int tj_lo, int tj_hi,
     int prio, int xcd_remap, int ti0, int64_t skip) {
   __shared__ double sP[TR + ST][KB + LDP];
@@ -1341,16 +1253,12 @@ __device__ __forceinline__ void stamp_max(unsigned long long* p, bool negate = f
 // it the launch's last by a whole unit: profiles/r03_unit_trace_*).
 __device__ __forceinline__ void tall_or_xcd_range(int seg, int64_t cnt, int64_t b, int64_t* u,
                                                   int64_t* end) {
-  if (seg == 2 && LFM_TALL_RR) {
-    if (LFM_TALL_GROUP) {
-      // workgroup b runs on XCD x = b % 8 at position p = b / 8 of its queue: group j = (p / S)
-      // 8 + x, piece p % S (the segment is padded to 8 S workgroups: tall_grid)
-      constexpr int S = LFM_TALL_SPLIT;
-      const int64_t p = b / 8;
-      *u = S * ((p / S) * 8 + b % 8) + p % S;
-    } else {
-      *u = b;
-    }
+  if (seg == 2) {
+    // workgroup b runs on XCD x = b % 8 at position p = b / 8 of its queue: group j = (p / S)
+    // 8 + x, piece p % S (the segment is padded to 8 S workgroups: tall_grid)
+    constexpr int S = TALL_SPLIT;
+    const int64_t p = b / 8;
+    *u = S * ((p / S) * 8 + b % 8) + p % S;
     *end = cnt;
     return;
   }
@@ -1371,7 +1279,7 @@ __device__ __forceinline__ void bump_after_stores(unsigned* ctr) {
 }
 
 
-// tall unit u (row slab rb, column block cb, its part hf of LFM_TALL_SPLIT) of step s + 1:
+// tall unit u (row slab rb, column block cb, its part hf of TALL_SPLIT) of step s + 1:
 // deepest column blocks first (longest units), so the launch ends on short ones; the split
 // halves a unit's width so the launch's last round drains in shorter pieces
 // Returns false when its device-side wait ran out (the workgroup then stops claiming units).
@@ -1383,12 +1291,12 @@ __device__ __forceinline__ bool tall_unit(const StepArgs& g, int64_t u, double (
       __hip_atomic_fetch_add(st + slot, __builtin_amdgcn_s_memrealtime() - t_unit,
                              __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   };
-  constexpr int TCW = NB / LFM_TALL_SPLIT;  // output columns per tall unit
-  const int64_t nrb = g.nt / (g.tw * LFM_TALL_SPLIT);
-  const int cb = g.tw - 1 - (int)(u / (nrb * LFM_TALL_SPLIT));
-  const int64_t rq = u % (nrb * LFM_TALL_SPLIT);
-  const int64_t rb = rq / LFM_TALL_SPLIT;
-  const int c0 = cb * NB + (int)(rq % LFM_TALL_SPLIT) * TCW;  // first output column in X_{s+1}
+  constexpr int TCW = NB / TALL_SPLIT;  // output columns per tall unit
+  const int64_t nrb = g.nt / (g.tw * TALL_SPLIT);
+  const int cb = g.tw - 1 - (int)(u / (nrb * TALL_SPLIT));
+  const int64_t rq = u % (nrb * TALL_SPLIT);
+  const int64_t rb = rq / TALL_SPLIT;
+  const int c0 = cb * NB + (int)(rq % TALL_SPLIT) * TCW;  // first output column in X_{s+1}
   const int64_t i0 = g.tr0 + rb * 64;
   if (i0 > g.n && i0 < g.pad_end) return true;  // identity padding rows: their X is never read
   {
@@ -1434,7 +1342,6 @@ __device__ __forceinline__ bool tall_unit(const StepArgs& g, int64_t u, double (
   const int wr = (wv >> 1) * 32, wc = (wv & 1) * (TCW / 2);
   const int li = lane & 15, lk = lane >> 4;
   constexpr int JR = TCW / 32;  // 16-column blocks per wave
-#if LFM_MFMA16
   double4v acc4[2][JR];
 #pragma unroll
   for (int rb = 0; rb < 2; ++rb)
@@ -1443,17 +1350,6 @@ __device__ __forceinline__ bool tall_unit(const StepArgs& g, int64_t u, double (
   gemm_accumulate16<64, true, true, KB, TCW>(g.A + i0 * g.lda + g.tk0, g.lda, g.Bd + c0, W,
                                              NB * (cb + 1), acc4, sP);
 #define ACC(ir, jr) acc4[(ir) >> 2][jr][(ir) & 3]
-#else
-  static_assert(TCW == NB, "the 4x4x4 tile body has no split tall units");
-  double acc[8][4];
-#pragma unroll
-  for (int ir = 0; ir < 8; ++ir)
-#pragma unroll
-    for (int jr = 0; jr < 4; ++jr) acc[ir][jr] = 0.0;
-  gemm_accumulate<64, true, true>(g.A + i0 * g.lda + g.tk0, g.lda, g.Bd + cb * NB, W,
-                                  NB * (cb + 1), acc, sP);
-#define ACC(ir, jr) acc[ir][jr]
-#endif
   double* Xb = g.X + (i0 - g.tr0 + wr + lk) * W + c0 + wc + li;
 #pragma unroll
   for (int ir = 0; ir < 8; ++ir)
@@ -1475,9 +1371,9 @@ __device__ __forceinline__ bool tall_unit(const StepArgs& g, int64_t u, double (
 template <int TR>
 __device__ __forceinline__ void step_body(const StepArgs& g, unsigned long long* ran = nullptr) {
   constexpr int SUB = ST / TR;  // units per 128-row tile
-  __shared__ double sPbuf[(64 + ST) * (LFM_STEP_KS + LDP)];
+  __shared__ double sPbuf[(64 + ST) * (STEP_KS + LDP)];
   double (*sP)[KB + LDP] = reinterpret_cast<double (*)[KB + LDP]>(sPbuf);
-  double (*sPu)[LFM_STEP_KS + LDP] = reinterpret_cast<double (*)[LFM_STEP_KS + LDP]>(sPbuf);
+  double (*sPu)[STEP_KS + LDP] = reinterpret_cast<double (*)[STEP_KS + LDP]>(sPbuf);
   const int64_t b = blockIdx.x;
   // roles in blockIdx order: ahead (1), rest (2), tall (3), each padded to a multiple of 8
   const int cnt[3] = {g.na, g.nr, g.nt};
@@ -1506,14 +1402,13 @@ __device__ __forceinline__ void step_body(const StepArgs& g, unsigned long long*
   if (role == 1) {
     // device-coherent stores + a counter bump once they have completed: the tall units read
     // these rows with device-coherent loads (no L2 writeback / invalidate on either side)
-    syrk_unit<true, TR, true, LFM_STEP_KS>(g.A, g.lda, g.s0, g.px, g.kd, g.T, 0, g.wn, u, g.wn, sPu,
-                                           0, g.n, g.pad_end, g.zero_from,
-                                           g.gen.tab ? &g.gen : nullptr);
+    syrk_unit<true, TR, true, STEP_KS>(g.A, g.lda, g.s0, g.px, g.kd, g.T, 0, g.wn, u, g.wn, sPu,
+                                       0, g.n, g.pad_end, g.zero_from,
+                                       g.gen.tab ? &g.gen : nullptr);
     __builtin_amdgcn_s_waitcnt(0);
     __syncthreads();
     // 128-tile row of the unit (the band's enumeration order, syrk_unit)
-    const int trow = LFM_BAND_ROWS ? g.wn + (int)(u / (SUB * g.wn))
-                                   : g.wn + (int)(u % (SUB * (g.T - g.wn))) / SUB;
+    const int trow = g.wn + (int)(u / (SUB * g.wn));
     if (threadIdx.x == 0 && g.a_done)
       __hip_atomic_fetch_add(&g.a_done[trow], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if (threadIdx.x == 0 && g.xready && trow < g.wn + g.lead)
@@ -1531,11 +1426,11 @@ __device__ __forceinline__ void step_body(const StepArgs& g, unsigned long long*
       c0 = __builtin_amdgcn_s_memtime();
       r0 = __builtin_amdgcn_s_memrealtime();
     }
-    const bool lead = syrk_unit<true, TR, false, LFM_STEP_KS>(g.A, g.lda, g.s0, g.px, g.kd, g.T,
-                                                              g.wn, g.T, u + g.rest_off, 0, sPu,
-                                                              g.xready ? g.wn + g.lead : 0, g.n,
-                                                              g.pad_end, g.zero_from,
-                                                              g.gen.tab ? &g.gen : nullptr);
+    const bool lead = syrk_unit<true, TR, false, STEP_KS>(g.A, g.lda, g.s0, g.px, g.kd, g.T,
+                                                          g.wn, g.T, u + g.rest_off, 0, sPu,
+                                                          g.xready ? g.wn + g.lead : 0, g.n,
+                                                          g.pad_end, g.zero_from,
+                                                          g.gen.tab ? &g.gen : nullptr);
     if (lead) bump_after_stores(g.xready);
     if (st) {
       __syncthreads();
@@ -1778,17 +1673,10 @@ __device__ __forceinline__ void gemm32(const double* __restrict__ pi, int64_t ld
   const int li = lane & 15, lk = lane >> 4;
   double* sA = smem;             // [32][G32K]: P rows
   double* sB = smem + 32 * G32K;  // [32][G32K]: Q columns (j-major)
-#if LFM_G32_M16
   double4v acc4[2][2];  // 16 x 16 blocks: acc4[rb][jr][r] = element (16 rb + 4 r + lk, 16 jr + li)
 #pragma unroll
   for (int rb = 0; rb < 2; ++rb) acc4[rb][0] = acc4[rb][1] = (double4v){0.0, 0.0, 0.0, 0.0};
 #define ACC(ir, jr) acc4[(ir) >> 2][jr][(ir) & 3]
-#else
-  double acc[8][2];
-#pragma unroll
-  for (int ir = 0; ir < 8; ++ir) acc[ir][0] = acc[ir][1] = 0.0;
-#define ACC(ir, jr) acc[ir][jr]
-#endif
   double2 pre[16];
   auto gload = [&](int k0) {
 #pragma unroll
@@ -1823,22 +1711,11 @@ __device__ __forceinline__ void gemm32(const double* __restrict__ pi, int64_t ld
 #pragma unroll
     for (int kk = 32 * w; kk < 32 * w + 32; kk += 4) {
       const double b0 = sB[li * G32K + kk + lk], b1 = sB[(16 + li) * G32K + kk + lk];
-#if LFM_G32_M16
       const double a0 = sA[li * G32K + kk + lk], a1 = sA[(16 + li) * G32K + kk + lk];
       acc4[0][0] = mfma16(a0, b0, acc4[0][0]);
       acc4[0][1] = mfma16(a0, b1, acc4[0][1]);
       acc4[1][0] = mfma16(a1, b0, acc4[1][0]);
       acc4[1][1] = mfma16(a1, b1, acc4[1][1]);
-#else
-      double a[8];
-#pragma unroll
-      for (int ir = 0; ir < 8; ++ir) a[ir] = sA[(ir * 4 + (lane & 3)) * G32K + kk + lk];
-#pragma unroll
-      for (int ir = 0; ir < 8; ++ir) {
-        acc[ir][0] = mfma4(a[ir], b0, acc[ir][0]);
-        acc[ir][1] = mfma4(a[ir], b1, acc[ir][1]);
-      }
-#endif
     }
   }
   __syncthreads();  // operand reads done: the partials alias them
@@ -2266,7 +2143,7 @@ int probe_update_launch(lfm_ctx* ctx, hipStream_t st, int T, int kd, int cio, in
       g.tw = 1;
       g.tr0 = 512 + ST;
       g.tk0 = 0;
-      g.nt = 2 * (T - 1) * LFM_TALL_SPLIT;
+      g.nt = 2 * (T - 1) * TALL_SPLIT;
       g.Bd = ctx->A;
       g.X = xs + xb / 8;
       g.zvec = xs;
@@ -2355,7 +2232,7 @@ int chol_factor_solve(lfm_ctx* ctx, double* A, int64_t lda, int64_t n, int64_t M
   // bulk width: 5 block columns (W = 640) for the MLL — its C traffic per flop is 4/5 of W = 512
   // and its chain still hides behind the update (A/B: -0.23..-0.26 ms per evaluation; W = 768
   // and 896 were slower, 1024 much slower); the bordered gradient keeps 4 (5 measured equal)
-  const int wbulk = s3 ? (bordered ? LFM_WBORD : LFM_WBULK) : 4;
+  const int wbulk = s3 ? (bordered ? WBORD : WBULK) : 4;
   const int64_t w2min = ctx->w2min >= 0 ? ctx->w2min : (s3 ? 5120 : 4096);
   const std::vector<std::pair<int64_t, int>> steps =
       plan_steps(nblk, Mp, NB, bordered, s3, wbulk, w4min, w2min, ctx->w0);
@@ -2483,7 +2360,7 @@ int chol_factor_solve(lfm_ctx* ctx, double* A, int64_t lda, int64_t n, int64_t M
     // tall units of step s: rows [K1_s, Mp) x w_s column blocks
     auto tall_units = [&](int s) {
       const int64_t K1 = (steps[s].first + steps[s].second) * NB;
-      return (int)((rows_end(K1) - K1) / 64 * steps[s].second * LFM_TALL_SPLIT);
+      return (int)((rows_end(K1) - K1) / 64 * steps[s].second * TALL_SPLIT);
     };
     // alg_adjust: algorithmic flops of the step's update done elsewhere (the side-CU helper's
     // tail, its own kernel class)
@@ -2501,7 +2378,7 @@ int chol_factor_solve(lfm_ctx* ctx, double* A, int64_t lda, int64_t n, int64_t M
       // the next diagonal block (the chain's), and the triangular solve of the rows below
       // the next super-panel (rows .. n) against its W' x W' factor
       const double issued = ((double)g.na + g.nr) * 64 * ST * 2.0 * g.kd +
-                            (double)g.nt * 64 * (ST / LFM_TALL_SPLIT) * NB * (g.tw + 1);
+                            (double)g.nt * 64 * (ST / TALL_SPLIT) * NB * (g.tw + 1);
       double alg = 0.0;
       if (g.na + g.nr > 0) {
         // bordered: the whole Mp-row window is algorithmic (Cholesky + inverse = Mp^3)
@@ -2566,7 +2443,7 @@ int chol_factor_solve(lfm_ctx* ctx, double* A, int64_t lda, int64_t n, int64_t M
     const double helper_min = ctx->helper_min;  // smallest D0 helped, us
     auto helper_share = [&](const StepArgs& g, int wnext) -> int64_t {
       if (!helper_on) return 0;
-      return helper_units(g.kd, g.na, g.nr, g.nt / LFM_TALL_SPLIT, wnext, NB, ctx->cus,
+      return helper_units(g.kd, g.na, g.nr, g.nt / TALL_SPLIT, wnext, NB, ctx->cus,
                           ctx->side_cus, helper_tc, helper_min);
     };
     // side: chain(0) after the gram; every later chain(s) follows chain(s - 1) in stream order
@@ -2637,7 +2514,7 @@ int chol_factor_solve(lfm_ctx* ctx, double* A, int64_t lda, int64_t n, int64_t M
         double a = 0.0;
         for (int64_t b = b0; b < b1; ++b) {
           int ti, tj;
-          rest_unit_tile(b, T, wn, LFM_SUPERTILE, &ti, &tj);
+          rest_unit_tile(b, T, wn, SUPERTILE, &ti, &tj);
           const int64_t i0 = s0u + (int64_t)ti * 64, j0 = s0u + (int64_t)tj * ST;
           for (int64_t r = i0; r < i0 + 64 && (bordered || r <= n); ++r)
             a += (double)std::max<int64_t>(0, std::min<int64_t>(ST, r - j0 + 1));
@@ -2669,7 +2546,7 @@ int chol_factor_solve(lfm_ctx* ctx, double* A, int64_t lda, int64_t n, int64_t M
         const int64_t total = g.nr;  // the step's rest enumeration
         const int64_t hu = s >= 1 && s + 2 < S
                                ? helper_clamp(helper_share(g, steps[s + 1].second), (int)total,
-                                              g.T, g.wn, g.xready ? g.lead : 0, LFM_SUPERTILE)
+                                              g.T, g.wn, g.xready ? g.lead : 0, SUPERTILE)
                                : 0;
         g.nr = (int)(total - hu);
         const double alg_h =

@@ -197,10 +197,6 @@ __global__ __launch_bounds__(256) void gram_grid_aligned_kernel(
   }
 }
 
-#ifdef LFM_GRAM_AB
-#include "lfm_gram_ab.inc"  // A/B-only store-shape variants (make EXTRA=-DLFM_GRAM_AB)
-#endif
-
 __global__ void f64_to_f32_kernel(const double* __restrict__ a, float* __restrict__ b, int64_t n) {
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
        i += (int64_t)gridDim.x * blockDim.x)
@@ -231,9 +227,6 @@ int launch_gram_grid(lfm_ctx* ctx, const HypDev& h, const GridLayout& lay, const
     // lower: only the lower tiles are launched (2 Q (Q + 1) of them, Q = n / 256)
     const int64_t Q = n / 256;
     dim3 grid = lower ? dim3((unsigned)(2 * Q * (Q + 1))) : dim3((unsigned)(n / 256), (unsigned)(n / 64));
-#ifdef LFM_GRAM_AB
-    if (!gram_ab_launch<OutT>(ctx, grid, tabT, h, lay.T, bg, n, da1, da2, lower, out, ldo))
-#endif
     hipLaunchKernelGGL((gram_grid_aligned_kernel<OutT>), grid, dim3(256), 0, ctx->stream, tabT,
                        h.G, lay.T, bg, n, (OutT)da1, (OutT)da2, lower, out, ldo);
   } else {

@@ -66,17 +66,10 @@ __device__ __forceinline__ double swap_halves(double v) {
 // fences are empty (a wave's LDS operations are performed in issue order) and the wave barrier
 // only fences code motion, so the ISA is unchanged; what it adds over a bare compiler fence is the
 // language-level ordering the reads rely on.
-#ifndef LFM_WAVE_HANDOFF
-#define LFM_WAVE_HANDOFF 1  // A/B only (make EXTRA=-DLFM_WAVE_HANDOFF=0): round 5's compiler fence
-#endif
 __device__ __forceinline__ void wave_lds_handoff() {
-#if LFM_WAVE_HANDOFF
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
   __builtin_amdgcn_wave_barrier();
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-#else
-  asm volatile("" ::: "memory");
-#endif
 }
 // window widths of the phases: 64 48 32 24 16 12 8
 template <int W>
@@ -124,9 +117,6 @@ __device__ __forceinline__ void small_factor_phase(double (&d)[W], int c, SmallF
   if constexpr (W > 8)
     if (c < f.n) small_factor_next<WN>(*reinterpret_cast<double(*)[WN]>(&d[0]), c, f);
 }
-#ifndef LFM_SMALL_PIPE
-#define LFM_SMALL_PIPE 1
-#endif
 // Windows of 32 and narrower: LDL^T (Sigma = L D L^T, unit L), software-pipelined by one
 // column. The trailing matrix is the same Schur complement as Cholesky's, so the two meet at a
 // phase boundary; what changes is what goes through LDS: a column's UNSCALED entries u_r (lane r's
@@ -196,7 +186,7 @@ __device__ __forceinline__ void small_factor_pipe(double (&d)[W], double (&col)[
 // stored and read back here), Cholesky (small_factor_phase) above
 template <int W>
 __device__ __forceinline__ void small_factor_next(double (&d)[W], int c, SmallFactor& f) {
-  if constexpr (W <= 32 && LFM_SMALL_PIPE) {
+  if constexpr (W <= 32) {
     f.inv = rcp_2nr(f.dc);
     wave_lds_handoff();  // the previous phase's reads of colbuf before these stores
     f.colbuf[f.r] = (f.act && f.r > c) ? d[0] : 0.0;
@@ -209,9 +199,6 @@ __device__ __forceinline__ void small_factor_next(double (&d)[W], int c, SmallFa
     small_factor_phase<W>(d, c, f);
   }
 }
-#ifndef LFM_SMALL_TWO
-#define LFM_SMALL_TWO 1
-#endif
 // n + 1 <= 32, the columns while more than 16 remain: LDL^T with each row on TWO lanes (lane i
 // slots 0..15 of row i's window, lane i + 32 slots 16..31), so a column's read-back is 16 values
 // a lane instead of up to 31 — the column step is bound by the wave's LDS read rate
@@ -263,7 +250,7 @@ __device__ __forceinline__ void small_factor_regs(const double* __restrict__ sm,
   f.colbuf = colbuf;
   f.mp = f.mz = f.q = 0.0;
   f.bad = 0;
-  if constexpr (MR == 32 && LFM_SMALL_TWO) {
+  if constexpr (MR == 32) {
     // two lanes a row while more than 16 columns remain, then the one-lane phases from W = 16
     // (the high lanes are rows past n there: inactive)
     const int hi = f.r >> 5, i = f.r & 31;
@@ -380,12 +367,11 @@ __device__ __forceinline__ void small_factor_regs2(const double* __restrict__ sm
 //   wb     [(n + 1) x ldw]  one wave: W's rows as the sweep leaves them (small_sweep_w)
 //   gout   [3G + 3]         the gradient in the packed layout (dD dS dB, dl, d obs_stddev, 0)
 // and the fit (FIT): raw, mu, nu [3G + 3 each] (the unconstrained parameters, Adam's moments).
-#ifndef LFM_FIT_STAMPS
-#define LFM_FIT_STAMPS 0
-#endif
+// (`spare` is never set or read: without the member the compiler allocates the gradient kernels'
+// registers differently, 22 AGPRs instead of 14, so it stays until that is measured)
 struct SmallMap {
   double *A, *red, *hyp, *ktab, *colbuf, *xs, *ys, *gt;
-  double *gg, *al, *wd, *accw, *gout, *raw, *mu, *nu, *tms, *stp, *wb;
+  double *gg, *al, *wd, *accw, *gout, *raw, *mu, *nu, *tms, *spare, *wb;
   int* bgs;
   int n, ld, G;
 };
@@ -437,47 +423,10 @@ __host__ __device__ inline size_t small_map(double* sm, int n, int G, int T, int
     q.raw = take(3 * (size_t)G + 3);
     q.mu = take(3 * (size_t)G + 3);
     q.nu = take(3 * (size_t)G + 3);
-    if (LFM_FIT_STAMPS) q.stp = take(17);
   }
   if (m) *m = q;
   return o;
 }
-
-// timing experiment (make EXTRA=-DLFM_SMALL_SKIP=k; results invalid, never in the product
-// build): 1 no factor, 2 no gram pairs, 3 neither, 4 no pinned reads (constant hyperparameters)
-#ifndef LFM_SMALL_SKIP
-#define LFM_SMALL_SKIP 0
-#endif
-// timing experiment (make EXTRA=-DLFM_SMALL_STAMPS=1, or 2 for a warm second pass in the args
-// kernel; results of problems 1-5 invalid): block 0
-// writes its phase times (µs from its start) into out[1..4] and the factor's clock (MHz) into out[5]
-#ifndef LFM_SMALL_STAMPS
-#define LFM_SMALL_STAMPS 0
-#endif
-// timing experiment (make EXTRA=-DLFM_FIT_STAMPS=1; problem 0's first history entries invalid):
-// the fit kernel's block 0 sums, over its steps, the time of each phase of a step (s_memrealtime
-// ticks) and writes the sums over its own first twelve history entries (scripts/fit_stamps.py)
-// (the sums live in the fit map's stamp slots, m.stp: [0, 16) the phase sums, [16] the last stamp)
-#if LFM_FIT_STAMPS
-__device__ __forceinline__ void fit_stamp(const SmallMap& m, int k) {
-  if (m.stp && blockIdx.x == 0 && threadIdx.x == 0) {
-    unsigned long long* st = reinterpret_cast<unsigned long long*>(m.stp);
-    const unsigned long long t = __builtin_amdgcn_s_memrealtime();
-    st[k] += t - st[16];
-    st[16] = t;
-  }
-}
-// a thread's own time since the last stamp into slot k (the last stamp unchanged)
-__device__ __forceinline__ void fit_peek(const SmallMap& m, int k, int thread) {
-  if (m.stp && blockIdx.x == 0 && threadIdx.x == thread) {
-    unsigned long long* st = reinterpret_cast<unsigned long long*>(m.stp);
-    st[k] += __builtin_amdgcn_s_memrealtime() - st[16];
-  }
-}
-#else
-__device__ __forceinline__ void fit_stamp(const SmallMap&, int) {}
-__device__ __forceinline__ void fit_peek(const SmallMap&, int, int) {}
-#endif
 
 // The MLL from a two-wave factor (every thread: pr / zr its row's pivot and z entry, rows < n):
 // per-wave sums, then wave 0's + wave 1's in that order; returned to every thread.
@@ -538,7 +487,6 @@ __device__ __forceinline__ void small_sigma(const SmallProb& P, const SmallMap& 
     const int nt = (int)(2 * (int64_t)G * W + 3 * (int64_t)G * T + (int64_t)G * G);
     for (int q = tid; q < nt; q += 256) gt[q] = grid_table_entry(h, T, P.dt, m.tms, q);
     __syncthreads();
-    fit_peek(m, 10, 0);
     const double* Wt = gt;
     const double* Xt = Wt + G * W;
     const double* Pt = Xt + G * W;
@@ -562,7 +510,6 @@ __device__ __forceinline__ void small_sigma(const SmallProb& P, const SmallMap& 
       if (i == c) v = (v + jitter) + noise;
       sm[i * ld + c] = v;
     }
-    fit_peek(m, 11, 0);
   } else if (tabs) {
     // n <= 63 (the launch's LDS holds the tables): gene-gene pairs from KxxTab, the same bits
     // as kernel_ref with a third of its transcendentals; pairs with a latent row direct
@@ -582,9 +529,7 @@ __device__ __forceinline__ void small_sigma(const SmallProb& P, const SmallMap& 
       const double* xa = xs + 3 * i;
       const double* xb = xs + 3 * c;
       double v;
-      if (LFM_SMALL_SKIP == 2 || LFM_SMALL_SKIP == 3)
-        v = i == c ? 4.0 : 0.01;
-      else if (flag_int(xa[2]) == 1 && flag_int(xb[2]) == 1)
+      if (flag_int(xa[2]) == 1 && flag_int(xb[2]) == 1)
         v = kxx_tab(h, t, xa[0], gene_index(xa[1], G), i, xb[0], gene_index(xb[1], G), c);
       else
         v = kernel_ref(h, xa[0], xa[1], xa[2], xb[0], xb[1], xb[2]);
@@ -609,7 +554,7 @@ __device__ __forceinline__ void small_sigma(const SmallProb& P, const SmallMap& 
 
 __device__ __forceinline__ void small_body(const SmallProb P, int negative,
                                            double* __restrict__ out, int* __restrict__ status,
-                                           int tabs, unsigned long long st0) {
+                                           int tabs) {
   extern __shared__ __attribute__((aligned(16))) double sm[];
   const int n = P.n, M = n + 1, G = P.G;
   const int tid = threadIdx.x;
@@ -621,18 +566,14 @@ __device__ __forceinline__ void small_body(const SmallProb P, int negative,
   // y, so that no later phase waits on HBM
   double* hyp = m.hyp;
   double* colbuf = m.colbuf;
-  for (int i = tid; i < 3 * G; i += 256) hyp[i] = LFM_SMALL_SKIP == 4 ? 0.5 : P.dsb[i];
-  if (tid < 3) hyp[3 * G + tid] = LFM_SMALL_SKIP == 4 ? (tid == 0 ? 2.5 : 1.0) : P.sc[tid];
+  for (int i = tid; i < 3 * G; i += 256) hyp[i] = P.dsb[i];
+  if (tid < 3) hyp[3 * G + tid] = P.sc[tid];
   small_stage(P, m);
   __syncthreads();
-  const unsigned long long st1 = LFM_SMALL_STAMPS ? __builtin_amdgcn_s_memrealtime() : 0;
   const HypDev h{hyp, hyp + G, hyp + 2 * G, G, hyp[3 * G]};
   small_sigma(P, m, h, tabs);
   if (tid == 0) red[8] = 0.0;
   __syncthreads();
-  const unsigned long long st2 = LFM_SMALL_STAMPS ? __builtin_amdgcn_s_memrealtime() : 0;
-  // the shader clock's count beside the 100 MHz one: the factor's effective clock
-  const unsigned long long ct2 = LFM_SMALL_STAMPS ? __builtin_amdgcn_s_memtime() : 0;
   if (M <= 64) {
     // one wave, the augmented matrix in registers (small_factor_regs); no workgroup barrier
     // (256-thread barriers were ~60 % of the kernel at n = 28, two per column)
@@ -641,16 +582,10 @@ __device__ __forceinline__ void small_body(const SmallProb P, int negative,
     double pr, qp;
     int bad;
     colbuf[64 + r] = 0.0;
-    if (LFM_SMALL_SKIP == 1 || LFM_SMALL_SKIP == 3) {
-      pr = sm[r * ld + r];
-      qp = sm[n * ld + r];
-      bad = 0;
-    } else if (M <= 32)
+    if (M <= 32)
       small_factor_regs<32>(sm, ld, n, M, colbuf, &pr, &qp, &bad);
     else
       small_factor_regs<64>(sm, ld, n, M, colbuf, &pr, &qp, &bad);
-    const unsigned long long st3 = LFM_SMALL_STAMPS ? __builtin_amdgcn_s_memrealtime() : 0;
-    const unsigned long long ct3 = LFM_SMALL_STAMPS ? __builtin_amdgcn_s_memtime() : 0;
     double ldp = r < n ? log(pr) : 0.0;
     for (int o = 32; o > 0; o >>= 1) ldp += __shfl_xor(ldp, o);
     if (r == 0) {
@@ -658,15 +593,7 @@ __device__ __forceinline__ void small_body(const SmallProb P, int negative,
       double mll = -0.5 * ((double)n * log(two_pi) + ldp + qp);
       mll *= negative ? -1.0 : 1.0;
       if (bad) mll = __builtin_nan("");
-      if (LFM_SMALL_STAMPS && blockIdx.x == 0) {
-        const unsigned long long st4 = __builtin_amdgcn_s_memrealtime();
-        out[1] = (double)(st1 - st0) * 0.01;
-        out[2] = (double)(st2 - st0) * 0.01;
-        out[3] = (double)(st3 - st0) * 0.01;
-        out[4] = (double)(st4 - st0) * 0.01;
-        out[5] = st3 > st2 ? (double)(ct3 - ct2) / ((double)(st3 - st2) * 0.01) : 0.0;  // MHz
-      }
-      if (!LFM_SMALL_STAMPS || blockIdx.x == 0 || blockIdx.x > 5) out[blockIdx.x] = mll;
+      out[blockIdx.x] = mll;
       // the status word lands after the result: the host may take it as the problem's
       // completion (lfm_batch_mll_f64)
       __threadfence_system();
@@ -741,24 +668,17 @@ __device__ __forceinline__ void small_body(const SmallProb P, int negative,
 __global__ __launch_bounds__(256) void small_mll_kernel(const SmallProb* __restrict__ probs,
                                                         int negative, double* __restrict__ out,
                                                         int* __restrict__ status, int tabs) {
-  const unsigned long long st0 = LFM_SMALL_STAMPS ? __builtin_amdgcn_s_memrealtime() : 0;
-  small_body(probs[blockIdx.x], negative, out, status, tabs, st0);
+  small_body(probs[blockIdx.x], negative, out, status, tabs);
 }
 
 // The same with the problem table and the hyperparameters in the kernel arguments (a resident
 // batch of at most SMALL_ARG_PROBS problems and SMALL_ARG_HYP hyperparameters): no dependent
 // load of the table from HBM and no read of pinned host memory before the gram.
 __global__ __launch_bounds__(256) void small_mll_kernel_args(SmallArgs a) {
-  const unsigned long long st0 = LFM_SMALL_STAMPS ? __builtin_amdgcn_s_memrealtime() : 0;
   SmallProb P = a.probs[blockIdx.x];
   P.dsb = a.hyp + a.dsb_off[blockIdx.x];
   P.sc = a.hyp + a.sc_off[blockIdx.x];
-  small_body(P, a.negative, a.out, a.status, a.tabs, st0);
-#if LFM_SMALL_STAMPS == 2
-  // a second pass over the same problem, its stamps overwriting the first's: the phases with the
-  // instruction and data caches warm (the same barrier count on every wave: see small_body)
-  small_body(P, a.negative, a.out, a.status, a.tabs, __builtin_amdgcn_s_memrealtime());
-#endif
+  small_body(P, a.negative, a.out, a.status, a.tabs);
 }
 
 // ------------------------------------------------ value and gradient (one workgroup)
@@ -1132,7 +1052,6 @@ __device__ __forceinline__ double small_value_grad(const SmallProb P, const Smal
   small_sigma(P, m, h, 1);
   for (int t = tid; t < 4 * nacc; t += 256) m.accw[t] = 0.0;
   __syncthreads();
-  fit_stamp(m, 1);
   if (M > 64) {
     // every wave takes part in the sweep below (small_sweep4, one barrier a step): the
     // derivative tables first, by every thread
@@ -1165,7 +1084,6 @@ __device__ __forceinline__ double small_value_grad(const SmallProb P, const Smal
       int bad;
       small_sweep_regs(A, ld, n, m.colbuf, a, &logdet, &bad);
       const double quad = -__shfl(a[0], n);  // lane n: -r^T Sigma^{-1} r
-      fit_peek(m, 7, 0);
       small_sweep_w(a, n, m.wb, m.colbuf, m.al, m.wd);
       if (lane == 0) {
         const double two_pi = 6.283185307179586476925;
@@ -1175,7 +1093,6 @@ __device__ __forceinline__ double small_value_grad(const SmallProb P, const Smal
         m.red[0] = mll;
         m.red[1] = (double)bad;
       }
-      fit_peek(m, 8, 0);
     };
     if (M <= 32) {
       // each row on two lanes (small_sweep_half)
@@ -1184,7 +1101,6 @@ __device__ __forceinline__ double small_value_grad(const SmallProb P, const Smal
       int bad;
       small_sweep_half(A, ld, n, m.colbuf, a, &logdet, &bad);
       const double quad = -__shfl(a[0], n);  // lane n: -r^T Sigma^{-1} r
-      fit_peek(m, 7, 0);
       small_sweep_w_half(a, n, m.wb, m.colbuf, m.al, m.wd);
       if (lane == 0) {
         const double two_pi = 6.283185307179586476925;
@@ -1194,7 +1110,6 @@ __device__ __forceinline__ double small_value_grad(const SmallProb P, const Smal
         m.red[0] = mll;
         m.red[1] = (double)bad;
       }
-      fit_peek(m, 8, 0);
     } else {
       double a[64];
       sweep(a);
@@ -1202,14 +1117,11 @@ __device__ __forceinline__ double small_value_grad(const SmallProb P, const Smal
   } else if (P.T > 0) {
     const int ngg = (int)grad_tables_doubles(G, P.T);
     for (int q = tid - 64; q < ngg; q += 192) m.gg[q] = grad_table_entry(h, P.T, P.dt, m.tms, q);
-    fit_peek(m, 9, 64);
   }
   __syncthreads();
-  fit_stamp(m, 2);
   // (W was written by the sweep: small_sweep_w / _half on one wave, small_sweep4_w on four)
   const int np = n * (n + 1) / 2;
   __syncthreads();
-  fit_stamp(m, 3);
   double* aw = m.accw + wv * nacc;  // this wave's partial sums: [0,G) D  [G,2G) S  [2G] l
   // W's strictly lower part: W[i][c] = Wrow[i ldw + c] (one wave: the sweep's row buffer; two
   // waves: A's lower triangle)
@@ -1347,7 +1259,6 @@ __device__ __forceinline__ double small_value_grad(const SmallProb P, const Smal
     }
   }
   __syncthreads();
-  fit_stamp(m, 4);
   const bool failed = m.red[1] != 0.0;
   const double nan = __builtin_nan("");
   if (tid < G) {
@@ -1380,7 +1291,6 @@ __device__ __forceinline__ double small_value_grad(const SmallProb P, const Smal
   *bad_out = (int)m.red[1];
   const double v = m.red[0];
   __syncthreads();
-  fit_stamp(m, 5);
   return v;
 }
 
@@ -1495,10 +1405,6 @@ __global__ __launch_bounds__(256) void small_fit_kernel(FitArgs a) {
     m.nu[i] = a.nu[gi];
   }
   small_stage(P, m);
-#if LFM_FIT_STAMPS
-  if (tid < 16) reinterpret_cast<unsigned long long*>(m.stp)[tid] = 0;
-  if (tid == 16) reinterpret_cast<unsigned long long*>(m.stp)[16] = __builtin_amdgcn_s_memrealtime();
-#endif
   __syncthreads();
   // model.constrain() (trainer.py:103): D, S, B, obs_stddev = softplus, l = 0.5 + 3 sigmoid; the
   // jitter slot holds the static jitter itself
@@ -1509,7 +1415,6 @@ __global__ __launch_bounds__(256) void small_fit_kernel(FitArgs a) {
   __syncthreads();
   int first_bad = 0;
   for (int64_t s = 0; s < a.nsteps; ++s) {
-    fit_stamp(m, 0);
     int bad;
     const double v = small_value_grad_step(n, G, P.T, P.dt, a.negative, &bad);
     if (bad && !first_bad) first_bad = (int)s + 1;
@@ -1541,13 +1446,7 @@ __global__ __launch_bounds__(256) void small_fit_kernel(FitArgs a) {
     if (tid < nh - 1) update(tid);
     if (nh - 1 > 256 && tid + 256 < nh - 1) update(tid + 256);
     __syncthreads();
-    fit_stamp(m, 6);
   }
-#if LFM_FIT_STAMPS
-  __syncthreads();  // block 0's own history entries of steps 0-6 are done: overwrite them
-  if (b == 0 && tid < 12 && tid < a.nsteps)
-    a.history[tid * a.nprob] = (double)reinterpret_cast<unsigned long long*>(m.stp)[tid];
-#endif
   for (int i = tid; i < nh; i += 256) {
     const int gi = i < 3 * G ? od + i : os + (i - 3 * G);
     a.raw[gi] = m.raw[i];

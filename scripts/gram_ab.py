@@ -5,7 +5,6 @@ PAD=<elements> is the script's own: the fill's leading dimension becomes N + PAD
 (also the script's own): each timed fill follows a device sync and a host sleep of that many
 microseconds, as bench.py's steps do (fill, 4-byte read-back, Python) instead of back to back.
 MEMSET=1 times lfm_memset_dev over the fill's byte count instead (contiguous; wall time).
-LFM_GRAM_AB=<mode> selects a store-shape variant in a library built with -DLFM_GRAM_AB.
 Round 3 A/B-ed its rows-per-tile / nontemporal / 16-B store variants this way (profiles/
 r03_ab_gram_*); those knobs were removed with the variants, so the gram has no per-call knob now."""
 import os

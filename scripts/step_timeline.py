@@ -22,7 +22,7 @@ from dis_project_amd import _lib, configs  # noqa: E402
 
 NB = 128
 SLOTS = 4 * 224  # resident step-kernel workgroups: 4 per main-stream CU (32 side CUs)
-TALL_SPLIT = 2  # tall units per 64-row x 128-column block of X (lfm_chol.hip LFM_TALL_SPLIT)
+TALL_SPLIT = 2  # tall units per 64-row x 128-column block of X (lfm_chol.hip TALL_SPLIT)
 
 
 def plan(n, bordered=False):
