@@ -1,0 +1,139 @@
+// lfm_api_internal.h — what the units of the extern "C" boundary share (lfm_ctx.hip, lfm_api.hip,
+// lfm_batch.hip, lfm_farm.hip). The kernel units see lfm_internal.h only.
+#pragma once
+
+#include <algorithm>
+#include <functional>
+
+#include "lfm_internal.h"
+
+namespace lfm {
+// what a launch over small problems is sized by: the largest n and num_genes, and the largest
+// small_grid_extra of the problems on the grid path (doubles; 0: none)
+struct SmallDims {
+  int maxn = 1, maxg = 1, gridtab = 0;
+};
+}  // namespace lfm
+
+// A batch of small problems registered once (the C5 ablation farm, notebook.py:33-75): x / y
+// and the problem table live in HBM; the packed hyperparameters, the results and the status
+// words live in one pinned host buffer the kernel reads and writes directly, so an evaluation is
+// one memcpy into that buffer, ONE kernel launch and one stream synchronise — no copy commands.
+struct lfm_batch {
+  uint64_t id = 0;  // unique per process (never reused): keys the farm's captured graph
+  int device = 0;
+  int64_t nprob = 0, nhyp = 0;
+  lfm::SmallDims dims;
+  char* dmem = nullptr;     // device: x / y (+ grid times / block genes) of every problem, then
+                            // the SmallProb table
+  lfm::SmallProb* dprobs = nullptr;
+  double* hbuf = nullptr;   // pinned host, coherent: hyp [nhyp] | out [nprob] | status [nprob]
+                            // (int); the kernel reads / writes it directly and the host spins on
+                            // the status words, so it must not be cached on the device side
+  hipEvent_t done = nullptr;  // recorded after every launch on the batch: destroy waits on it
+  // small enough for the kernel arguments (LFM_SMALL_KERNARG, default on; read at creation)
+  bool use_args = false;
+  std::vector<lfm::SmallProb> table;  // host copy of the problem table
+  std::vector<int> dsb_off, sc_off;  // each problem's offsets in the packed hyperparameters
+  int* doffs = nullptr;              // device: dsb_off then sc_off (the gradient / fit kernels)
+  double* hgrad = nullptr;           // pinned (in hbuf): the gradient, packed as hyp [nhyp]
+  size_t lds_grad = 0, lds_fit = 0;  // the gradient / fit launches' LDS (0: not possible)
+  // the fit's device buffers (grown on demand): raw mu nu [3 nhyp] | bias [2 nsteps] |
+  // history [nsteps nprob] | status [nprob]
+  char* fitbuf = nullptr;
+  size_t fit_bytes = 0;
+};
+
+namespace lfm {
+
+// ------------------------------------------------------------ lfm_ctx.hip
+struct DeviceGuard {
+  DeviceGuard(int dev) { hipSetDevice(dev); }
+};
+
+// The device's tenancy lock, held for the object's lifetime (the rationale: lfm_ctx.hip)
+class DeviceTenancy {
+ public:
+  // s3: the call would run schedule 3 (exclusive); else shared
+  DeviceTenancy(lfm_ctx* ctx, bool s3);
+  ~DeviceTenancy();
+  DeviceTenancy(const DeviceTenancy&) = delete;
+  DeviceTenancy& operator=(const DeviceTenancy&) = delete;
+
+ private:
+  lfm_ctx* ctx_;
+  int dev_ = -1;
+  bool excl_ = false, nested_ = false;
+};
+
+// the end of a call: ctx->stream synchronised
+int finish(lfm_ctx* ctx);
+// attempt(), re-run once on schedule 1 if it was a schedule-3 call that stalled
+int with_s3_fallback(lfm_ctx* ctx, const std::function<int()>& attempt);
+// linvT, status, result and psync (zeroed) of a new context or restart-pipeline workspace
+hipError_t alloc_fixed(lfm_ctx* ctx);
+
+inline int64_t round_up(int64_t a, int64_t b) { return (a + b - 1) / b * b; }
+
+inline int validate_x(lfm_ctx* ctx, const void* x, int64_t n) {
+  if (!ctx) return LFM_E_ARG;
+  if (!x) return set_err(ctx, LFM_E_ARG, "x is NULL");
+  if (n < 1) return set_err(ctx, LFM_E_ARG, "n must be >= 1");
+  if (n > (int64_t)1 << 30) return set_err(ctx, LFM_E_ARG, "n too large");
+  return LFM_OK;
+}
+
+inline int check_mean_shape(lfm_ctx* ctx, int64_t n, const lfm_hyp* hyp) {
+  // mean_function (model.py:145-149) repeats B/D in blocks of n // num_genes; the
+  // reference's broadcast only succeeds when those blocks tile n exactly.
+  if (n % hyp->num_genes != 0)
+    return set_err(ctx, LFM_E_ARG,
+                   "mean_function needs n divisible by num_genes (model.py:145-149)");
+  return LFM_OK;
+}
+
+// ------------------------------------------------------------ lfm_api.hip
+// Drain and free the restart pipeline's workspaces and its overlap stream
+void twins_drop(lfm_ctx* ctx);
+
+// ---------------------------------------------------------- lfm_batch.hip
+// small-N batch through one launch; probs already validated
+int small_batch(lfm_ctx* ctx, int64_t np, const lfm_problem* probs, const int64_t* idx,
+                int negative, double* out, int* status);
+
+// One launch of the batch's MLL kernel: results to `out` (the pinned buffer, or a device buffer
+// such as the farm's send slots), the status words (reset to -1 here, each written last by its
+// workgroup after a system-scope fence) to the pinned buffer.
+int batch_launch(lfm_ctx* ctx, lfm_batch* batch, const double* hyp, int negative, double* out);
+
+// per-problem status words -> status[] (optional; raw: the words themselves, else LFM_OK /
+// LFM_E_NOT_PD); LFM_E_NOT_PD, with msg as the context's error, if any problem failed
+int batch_status(lfm_ctx* ctx, const int* words, int64_t np, int* status,
+                 const char* msg = "Cholesky failed: non-positive pivot in a batch problem",
+                 bool raw = false);
+
+// the status words of the batch's pinned buffer
+inline int* batch_words(const lfm_batch* batch) {
+  return reinterpret_cast<int*>(batch->hbuf + batch->nhyp + batch->nprob);
+}
+// before a launch: a problem's status word is written last
+inline void batch_reset(const lfm_batch* batch) {
+  int* hst = batch_words(batch);
+  for (int64_t q = 0; q < batch->nprob; ++q) hst[q] = -1;
+}
+
+// Result words the host is still waiting for: a signalling-NaN payload that no kernel writes
+// (its arithmetic yields values or the canonical quiet NaN; the padding slots are all-ones).
+constexpr uint64_t RESULT_PENDING = 0x7FF41F0DCAFE0001ull;
+inline void mark_pending(double* p, int64_t count) {
+  uint64_t* w = reinterpret_cast<uint64_t*>(p);
+  for (int64_t q = 0; q < count; ++q) w[q] = RESULT_PENDING;
+}
+inline bool all_landed(const double* p, int64_t count) {
+  const uint64_t* w = reinterpret_cast<const uint64_t*>(p);
+  for (int64_t q = 0; q < count; ++q)
+    if (__atomic_load_n(&w[q], __ATOMIC_ACQUIRE) == RESULT_PENDING) return false;
+  return true;
+}
+
+}  // namespace lfm

@@ -1157,9 +1157,9 @@ __global__ __launch_bounds__(256, TR == 64 ? SLAB_WGS : 2) void syrk_kernel(
 }
 
 // Device-side waits are bounded in TIME, on the 100 MHz constant clock (s_memrealtime), not
-// in polls: `limit` ticks (ctx->wait_ticks, LFM_DEVICE_WAIT_MS; 2 s by default), so a wait
+// in polls: `limit` ticks (ctx->knobs.wait_ticks, LFM_DEVICE_WAIT_MS; 2 s by default), so a wait
 // starved by another tenant of the GPU ends after a known time whatever the poll rate, and the
-// call re-runs on schedule 1 (lfm_api.hip). limit = 0 fails at once (the LFM_DEBUG_SPIN_LIMIT
+// call re-runs on schedule 1 (lfm_ctx.hip). limit = 0 fails at once (the LFM_DEBUG_SPIN_LIMIT
 // test knob). A wait also ends as soon as another wait of the call has recorded a timeout
 // (`status`), so one stall drains the whole factorisation within one bound.
 __device__ __forceinline__ unsigned long long wall_ticks() { return __builtin_amdgcn_s_memrealtime(); }
@@ -2073,7 +2073,7 @@ struct Launcher {
     prof_begin(ctx, K_PANEL, &ev, st);
     hipLaunchKernelGGL(panel_kernel, dim3((unsigned)(2 + rows / 64)), dim3(256), PANEL_LDS, st, A,
                        lda, kb, pkb, pkd, n, ctx->linvT, ctx->parts, (int)k, ctx->status,
-                       ctx->psync, epoch, ctx->wait_ticks);
+                       ctx->psync, epoch, ctx->knobs.wait_ticks);
     prof_end(ctx, K_PANEL, ev,
              (double)NB * NB * NB / 3.0 + (double)rows * NB * NB + 2.0 * (rows + NB) * NB * pkd,
              0, st);
@@ -2125,7 +2125,7 @@ int probe_update_launch(lfm_ctx* ctx, hipStream_t st, int T, int kd, int cio, in
     g.nr = (int)units;
     g.n = n;
     g.pad_end = INT64_MAX;
-    g.spin = ctx->wait_ticks;
+    g.spin = ctx->knobs.wait_ticks;
     g.zero_from = (cio & 32) ? 0 : INT64_MAX;
     g.copy_from = INT64_MAX;
     double* xs = ctx->A + (size_t)n * n;  // [X_s | X_{s+1} | counters]
@@ -2168,7 +2168,7 @@ int probe_update_launch(lfm_ctx* ctx, hipStream_t st, int T, int kd, int cio, in
 }
 
 bool chol_fuses_gram(const lfm_ctx* ctx, int mode, const GridLayout& lay, int64_t n) {
-  return ctx->gram_fuse && lay.ok && lay.T % 256 == 0 && n % 256 == 0 && n >= 1024 &&
+  return ctx->knobs.gram_fuse && lay.ok && lay.T % 256 == 0 && n % 256 == 0 && n >= 1024 &&
          s3_on(ctx) && mode != CHOL_SCHUR;
 }
 
@@ -2209,7 +2209,7 @@ int chol_factor_solve(lfm_ctx* ctx, double* A, int64_t lda, int64_t n, int64_t M
   const bool bordered = mode == CHOL_INVERSE;
   const int64_t npb = (n + NB - 1) / NB;  // block columns that hold pivots
   const int64_t nblk = bordered ? Mp / NB : npb;
-  int r = ensure(ctx, (void**)&ctx->parts, &ctx->parts_cap, (size_t)nblk * sizeof(double));
+  int r = ctx->parts.reserve(ctx, (size_t)nblk * sizeof(double));
   if (r) return r;
   // schedule 3 for the MLL and for the bordered inverse (gradient); the Schur-complement
   // posterior keeps schedule 1
@@ -2228,14 +2228,14 @@ int chol_factor_solve(lfm_ctx* ctx, double* A, int64_t lda, int64_t n, int64_t M
   // would otherwise hold up the first w = 1 chains (measured 0.13-0.24 ms faster than going
   // straight to w = 1); its first super-panel is one block wide (its factor precedes any bulk
   // work).
-  const int64_t w4min = ctx->w4min;
+  const int64_t w4min = ctx->knobs.w4min;
   // bulk width: 5 block columns (W = 640) for the MLL — its C traffic per flop is 4/5 of W = 512
   // and its chain still hides behind the update (A/B: -0.23..-0.26 ms per evaluation; W = 768
   // and 896 were slower, 1024 much slower); the bordered gradient keeps 4 (5 measured equal)
   const int wbulk = s3 ? (bordered ? WBORD : WBULK) : 4;
-  const int64_t w2min = ctx->w2min >= 0 ? ctx->w2min : (s3 ? 5120 : 4096);
+  const int64_t w2min = ctx->knobs.w2min >= 0 ? ctx->knobs.w2min : (s3 ? 5120 : 4096);
   const std::vector<std::pair<int64_t, int>> steps =
-      plan_steps(nblk, Mp, NB, bordered, s3, wbulk, w4min, w2min, ctx->w0);
+      plan_steps(nblk, Mp, NB, bordered, s3, wbulk, w4min, w2min, ctx->knobs.w0);
   const int S = (int)steps.size();
   r = ensure_events(ctx, 3 * (size_t)S + 3);  // [2 S + 3, 3 S + 3): LFM_S3_EVENTS=2
   if (r) return r;
@@ -2275,7 +2275,7 @@ int chol_factor_solve(lfm_ctx* ctx, double* A, int64_t lda, int64_t n, int64_t M
     // overlapped (a twin workspace of lfm_mll_multi_f64, ctx->ovl): chain(0), X_0, chain(1) and
     // launch 0 run on ctx->stream (the primary's overlap stream, behind this evaluation's gram),
     // the rest on the shared pair, after them and after the previous evaluation's launches
-    const bool ovl = ctx->ovl && ctx->s3_events == 0 && S >= 2;
+    const bool ovl = ctx->ovl && ctx->knobs.s3_events == 0 && S >= 2;
     hipEventRecord(ev[0], ctx->stream);
     main = ctx->m3;
     side = ctx->s3;
@@ -2292,15 +2292,13 @@ int chol_factor_solve(lfm_ctx* ctx, double* A, int64_t lda, int64_t n, int64_t M
     for (const auto& st : steps) wmax = std::max(wmax, st.second);
     const int64_t Wmax = (int64_t)wmax * NB, Tmax = Mp / ST + 1;
     // two workspaces: chain(s + 1) starts while the tall units of step s still read Bd_s
-    r = ensure(ctx, (void**)&ctx->wk, &ctx->wk_bytes, (size_t)4 * Wmax * Wmax * sizeof(double));
-    if (!r)
-      r = ensure(ctx, (void**)&ctx->xbuf, &ctx->xbuf_bytes, (size_t)2 * Mp * Wmax * sizeof(double));
-    if (!r) r = ensure(ctx, (void**)&ctx->zvec, &ctx->zvec_bytes, (size_t)Mp * sizeof(double));
-    if (!r)
-      r = ensure(ctx, (void**)&ctx->linv_full, &ctx->linv_full_bytes, (size_t)NB * NB * sizeof(double));
-    if (!r) r = ensure(ctx, (void**)&ctx->xd, &ctx->xd_bytes, (size_t)Wmax * Wmax * sizeof(double));
+    r = ctx->wk.reserve(ctx, (size_t)4 * Wmax * Wmax * sizeof(double));
+    if (!r) r = ctx->xbuf.reserve(ctx, (size_t)2 * Mp * Wmax * sizeof(double));
+    if (!r) r = ctx->zvec.reserve(ctx, (size_t)Mp * sizeof(double));
+    if (!r) r = ctx->linv_full.reserve(ctx, (size_t)NB * NB * sizeof(double));
+    if (!r) r = ctx->xd.reserve(ctx, (size_t)Wmax * Wmax * sizeof(double));
     const size_t nflags = (size_t)S * (3 + Tmax);
-    if (!r) r = ensure(ctx, (void**)&ctx->flags, &ctx->flags_bytes, nflags * sizeof(unsigned));
+    if (!r) r = ctx->flags.reserve(ctx, nflags * sizeof(unsigned));
     if (r) return r;
     unsigned* chain_done = ctx->flags;     // [S]
     unsigned* a_done = ctx->flags + S;     // [S][Tmax]
@@ -2344,7 +2342,7 @@ int chol_factor_solve(lfm_ctx* ctx, double* A, int64_t lda, int64_t n, int64_t M
       c.zvec = ctx->zvec;
       c.bar = bars + s;
       c.done = chain_done + s;
-      c.spin = ctx->wait_ticks;
+      c.spin = ctx->knobs.wait_ticks;
       c.stamps = ctx->dbg_stamps ? ctx->dbg_stamps + 16 * (size_t)std::min(s, 255) : nullptr;
       hipEvent_t pe;
       prof_begin(ctx, K_POTRF, &pe, side);
@@ -2369,7 +2367,7 @@ int chol_factor_solve(lfm_ctx* ctx, double* A, int64_t lda, int64_t n, int64_t M
       g.pad_end = pad_end;
       if (!g.zero_from) g.zero_from = INT64_MAX;
       if (!g.copy_from) g.copy_from = INT64_MAX;
-      g.spin = ctx->wait_ticks;
+      g.spin = ctx->knobs.wait_ticks;
       const int64_t grid = (int64_t)(g.na + 7) / 8 * 8 + rest_wgs(g) + tall_grid(g.nt);
       if (grid == 0) return;
       // issued: every 64 x 128 unit in full (padding rows included), tall units as GEMMs with
@@ -2438,9 +2436,9 @@ int chol_factor_solve(lfm_ctx* ctx, double* A, int64_t lda, int64_t n, int64_t M
     // units of step s's rest triangle for the side-CU helper: the main launch of U unit-
     // equivalents takes D0 = U t / (S_m o) alone; giving x units to the helper's S_h slots,
     // which start after chain(s + 1) (Tc), balances at x t (1 / S_h + 1 / S_m) = o (D0 - Tc)
-    const int helper_on = mode == CHOL_MLL || bordered ? ctx->helper : 0;
-    const double helper_tc = ctx->helper_tc;    // chain(s + 1) + margin, us
-    const double helper_min = ctx->helper_min;  // smallest D0 helped, us
+    const int helper_on = mode == CHOL_MLL || bordered ? ctx->knobs.helper : 0;
+    const double helper_tc = ctx->knobs.helper_tc;    // chain(s + 1) + margin, us
+    const double helper_min = ctx->knobs.helper_min;  // smallest D0 helped, us
     auto helper_share = [&](const StepArgs& g, int wnext) -> int64_t {
       if (!helper_on) return 0;
       return helper_units(g.kd, g.na, g.nr, g.nt / TALL_SPLIT, wnext, NB, ctx->cus,
@@ -2455,7 +2453,7 @@ int chol_factor_solve(lfm_ctx* ctx, double* A, int64_t lda, int64_t n, int64_t M
       hipStreamWaitEvent(side, ev[0], 0);
     }
     bool tail_marked = false;
-    if (ctx->s3_events == 1) {
+    if (ctx->knobs.s3_events == 1) {
       // The same work ordered by stream events only (tall units in launches of their own after
       // the factor's event, chains after the tall launch's event) — for tools that serialise
       // dispatches (rocprofv3 --pmc), under which device-side waits between the two streams
@@ -2492,7 +2490,7 @@ int chol_factor_solve(lfm_ctx* ctx, double* A, int64_t lda, int64_t n, int64_t M
       // its device-side waits name (chain(s + 1) after launch s - 1, launch s after chain(s + 1)),
       // so a tool that serialises dispatches (rocprofv3 --pmc) counts the timed schedule's own
       // launches, one for one
-      const bool serial = ctx->s3_events == 2;
+      const bool serial = ctx->knobs.s3_events == 2;
       hipEvent_t* evC = ev + 2 * S + 3;  // [S] chain(s) done (serialised only)
       chain(0);
       if (serial) {
@@ -2554,7 +2552,7 @@ int chol_factor_solve(lfm_ctx* ctx, double* A, int64_t lda, int64_t n, int64_t M
         if (helped) hipStreamWaitEvent(main, evH[2 * (s - 1)], 0);
         // overlapped: the next evaluation may start once the launches before this evaluation's
         // tail have run (its first step below LFM_OVL_AT trailing rows)
-        if (ctx->ovl && !tail_marked && s >= 1 && rows_end(g.s0) - g.s0 < ctx->ovl_at) {
+        if (ctx->ovl && !tail_marked && s >= 1 && rows_end(g.s0) - g.s0 < ctx->knobs.ovl_at) {
           hipEventRecord(ctx->ovl_tail, main);
           tail_marked = true;
         }

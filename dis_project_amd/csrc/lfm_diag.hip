@@ -328,7 +328,7 @@ int probe_syrk(lfm_ctx* ctx, int T, int kd, int cio, int reps, double* us) {
   constexpr int64_t TILE = 128;
   const int64_t n = (int64_t)T * TILE + 512;
   const size_t xb = (cio & (512 | 256)) ? (size_t)n * 128 * 8 : 0;  // X_s / X_{s+1} slabs
-  int r = ensure(ctx, (void**)&ctx->A, &ctx->A_bytes, (size_t)n * n * 8 + 2 * xb + 4096);
+  int r = ctx->A.reserve(ctx, (size_t)n * n * 8 + 2 * xb + 4096);
   if (r) return r;
   if (cio & 8)
     hipLaunchKernelGGL(fill_hash_kernel, dim3(4096), dim3(256), 0, ctx->stream, ctx->A,
@@ -396,7 +396,7 @@ int lfm_debug_stamps(lfm_ctx* ctx, int enable, unsigned long long* out, int max)
   const size_t cnt = 256 * 24;  // 256 chain rows of 16, then 256 step-launch rows of 8
   if (enable) {
     if (!ctx->dbg_stamps) {
-      hipError_t e = hipMalloc((void**)&ctx->dbg_stamps, cnt * 8);
+      hipError_t e = hipMalloc((void**)&ctx->dbg_stamps.p, cnt * 8);
       if (e != hipSuccess) return hip_fail(ctx, e, "debug stamps");
     }
     hipError_t e = hipMemsetAsync(ctx->dbg_stamps, 0, cnt * 8, ctx->stream);
@@ -409,8 +409,7 @@ int lfm_debug_stamps(lfm_ctx* ctx, int enable, unsigned long long* out, int max)
     e = hipMemcpyAsync(out, ctx->dbg_stamps, std::min<size_t>(cnt, (size_t)std::max(max, 0)) * 8,
                        hipMemcpyDeviceToHost, ctx->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-  hipFree(ctx->dbg_stamps);
-  ctx->dbg_stamps = nullptr;
+  ctx->dbg_stamps.release();
   return hip_fail(ctx, e, "debug stamps");
 }
 
@@ -422,14 +421,12 @@ int lfm_debug_trace(lfm_ctx* ctx, int64_t cap, unsigned long long* out, int64_t 
   if (!ctx || cap < 0) return LFM_E_ARG;
   DeviceGuard g(ctx->device);
   if (cap > 0) {
-    if (ctx->dbg_trace) hipFree(ctx->dbg_trace);
-    ctx->dbg_trace = nullptr;
-    hipError_t e = hipMalloc((void**)&ctx->dbg_trace, (size_t)cap * 32);
+    ctx->dbg_trace.release();
+    hipError_t e = hipMalloc((void**)&ctx->dbg_trace.p, (size_t)cap * 32);
     if (e == hipSuccess) e = hipMemsetAsync(ctx->dbg_trace, 0, (size_t)cap * 32, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
     if (e != hipSuccess) {
-      hipFree(ctx->dbg_trace);
-      ctx->dbg_trace = nullptr;
+      ctx->dbg_trace.release();
       return hip_fail(ctx, e, "debug trace");
     }
     ctx->dbg_trace_cap = cap;
@@ -443,8 +440,7 @@ int lfm_debug_trace(lfm_ctx* ctx, int64_t cap, unsigned long long* out, int64_t 
   const int64_t nrec = std::min<int64_t>(ctx->dbg_trace_cur, std::max<int64_t>(max, 0));
   if (e == hipSuccess && out && nrec > 0)
     e = hipMemcpy(out, ctx->dbg_trace, (size_t)nrec * 32, hipMemcpyDeviceToHost);
-  hipFree(ctx->dbg_trace);
-  ctx->dbg_trace = nullptr;
+  ctx->dbg_trace.release();
   ctx->dbg_trace_cap = ctx->dbg_trace_cur = 0;
   return hip_fail(ctx, e, "debug trace");
 }

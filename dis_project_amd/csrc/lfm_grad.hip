@@ -274,12 +274,11 @@ int launch_grad(lfm_ctx* ctx, const HypDev& h, const double* d_x, int64_t n, con
   hipMemsetAsync(acc, 0, (size_t)(2 * h.G + 1) * sizeof(double), ctx->stream);
   // the table path on the aligned grid layout (T % 256 == 0, the C2-C4 shape), else the
   // general per-pair dual-number path (LFM_GRAD_DIRECT=1 forces it: a test's cross-check)
-  const bool grid = lay && lay->ok && lay->T % 256 == 0 && n % 256 == 0 && !ctx->grad_direct;
+  const bool grid = lay && lay->ok && lay->T % 256 == 0 && n % 256 == 0 && !ctx->knobs.grad_direct;
   hipEvent_t ev;
   prof_begin(ctx, K_GRAD, &ev);
   if (grid) {
-    int r = ensure(ctx, (void**)&ctx->gtab, &ctx->gtab_bytes,
-                   grad_tables_doubles(h.G, lay->T) * sizeof(double));
+    int r = ctx->gtab.reserve(ctx, grad_tables_doubles(h.G, lay->T) * sizeof(double));
     if (r) return r;
     const size_t nt = grad_tables_doubles(h.G, lay->T);
     hipLaunchKernelGGL(grad_tables_kernel, dim3((unsigned)std::min<size_t>((nt + 255) / 256, 4096)),

@@ -213,7 +213,7 @@ int launch_gram_grid(lfm_ctx* ctx, const HypDev& h, const GridLayout& lay, const
     tabT = tab;
   } else {
     const size_t nt = tables_doubles(h.G, lay.T);
-    int r = ensure(ctx, (void**)&ctx->tab32, &ctx->tab32_bytes, nt * sizeof(float));
+    int r = ctx->tab32.reserve(ctx, nt * sizeof(float));
     if (r) return r;
     hipLaunchKernelGGL(f64_to_f32_kernel, dim3(256), dim3(256), 0, ctx->stream, tab, ctx->tab32,
                        (int64_t)nt);

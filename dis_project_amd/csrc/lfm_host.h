@@ -87,7 +87,7 @@ int64_t helper_units(int kd, int na, int nr, int nt, int wnext, int nb, int cus,
 // (T - wn <= kBandMaxCols).
 int64_t helper_clamp(int64_t hu, int nr, int T, int wn, int lead, int Q);
 
-// Readers-writer lock over one GPU's library work (lfm_api.hip DeviceTenancy: a schedule-3
+// Readers-writer lock over one GPU's library work (lfm_ctx.hip DeviceTenancy: a schedule-3
 // factorisation exclusive, all other GPU work shared). In-process a std::shared_mutex; across
 // processes flock on `path` (LOCK_EX / LOCK_SH; the process's shared hold is counted over its
 // threads, taken by the first reader and dropped by the last) behind a turnstile file (`path`

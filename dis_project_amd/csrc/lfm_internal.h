@@ -42,50 +42,50 @@ struct ProfEvent {
   double flops, bytes, issued;
 };
 
-}  // namespace lfm
+// Growth of a context's workspace (lfm_ctx.hip): at least 16 bytes, ctx->stream synchronised
+// before the old allocation is freed, LFM_E_OOM with the size in the message; the host form
+// allocates pinned memory with `flags` and reports failure as `what`.
+int ensure(lfm_ctx* ctx, void** p, size_t* cap, size_t bytes);
+int ensure_host(lfm_ctx* ctx, void** p, size_t* cap, size_t bytes, unsigned flags,
+                const char* what);
 
-struct lfm_ctx {
-  int device = 0;
-  hipStream_t stream = nullptr;  // main stream: gram fill, bulk trailing updates, finalize
-  hipStream_t side = nullptr;    // high-priority look-ahead stream: panel factor + solve
-  hipStream_t m3 = nullptr;      // schedule 3: bulk stream (CUs outside the chain's)
-  hipStream_t s3 = nullptr;      // schedule 3: factor-chain stream (LFM_SIDE_CUS CUs)
+// A buffer its context owns: device memory (Pinned: host memory), grown on demand and freed with
+// the context. Reads as the pointer it holds (ctx->A + off).
+template <typename T, bool Pinned = false>
+struct Buf {
+  T* p = nullptr;
+  size_t bytes = 0;  // capacity
+  Buf() = default;
+  Buf(const Buf&) = delete;
+  Buf& operator=(const Buf&) = delete;
+  ~Buf() { release(); }
+  operator T*() const { return p; }
+  int reserve(lfm_ctx* ctx, size_t n, unsigned flags = hipHostMallocDefault,
+              const char* what = "hipHostMalloc") {
+    return Pinned ? ensure_host(ctx, (void**)&p, &bytes, n, flags, what)
+                  : ensure(ctx, (void**)&p, &bytes, n);
+  }
+  // Forget the allocation without freeing it (the farm: work still queued may write into it)
+  void abandon() {
+    p = nullptr;
+    bytes = 0;
+  }
+  void release() {
+    if (p) Pinned ? hipHostFree(p) : hipFree(p);
+    abandon();
+  }
+};
+
+// The run-time knobs, read once when the context is created (create_streams,
+// lfm_ctx.hip); a restart-pipeline workspace copies its primary's.
+struct Knobs {
   int side_req = 32;             // LFM_SIDE_CUS at creation: the reservation to (re)create
-  int cus = 256;                 // compute units of the device
-  std::vector<hipEvent_t> evs;   // cross-stream dependency events (timing disabled)
-  std::string err;
-  int nb = 128;  // Cholesky block size
-
-  // device workspace, grown on demand
-  double* A = nullptr;   size_t A_bytes = 0;     // augmented factor (Mp x Mp) / generic matrix
-  double* tab = nullptr; size_t tab_bytes = 0;   // gene tables (fp64)
-  float* tab32 = nullptr; size_t tab32_bytes = 0;// gene tables (fp32 copy)
-  double* par = nullptr; size_t par_bytes = 0;   // packed hyperparameters + layout
-  double* xin = nullptr; size_t xin_bytes = 0;   // staged x / y / loc inputs
-  double* linvT = nullptr;                       // 8 x 16x16 inverses of the diagonal sub-blocks
-  double* parts = nullptr; size_t parts_cap = 0; // per-block logdet partials
-  int* status = nullptr;                         // [0] first failing pivot (INT_MAX = none)
-  double* wk = nullptr; size_t wk_bytes = 0;     // schedule 3: diagonal block + identity border
-  double* xbuf = nullptr; size_t xbuf_bytes = 0; // schedule 3: solved panel X = A21 L11^{-T}
-  double* zvec = nullptr; size_t zvec_bytes = 0; // schedule 3: z = L^{-1} r
-  double* linv_full = nullptr; size_t linv_full_bytes = 0; // schedule 3: 128x128 block inverse
-  double* xd = nullptr; size_t xd_bytes = 0;     // schedule 3: the chain's rows of X_{s-1}
-  unsigned* flags = nullptr; size_t flags_bytes = 0; // schedule 3: per-step device flags
-  unsigned* psync = nullptr;                     // fused panel: [0] factor epoch, [1] slab count
-  unsigned panel_epoch = 0;                      // fused panel launches so far
-  int side_cus = 0;                              // CUs reserved for the side stream (LFM_SIDE_CUS)
   int sched = 3;                                 // look-ahead schedule 1 or 3 (LFM_SCHED)
-  bool s3_yield = false;                         // this call runs schedule 1: nested in a
-                                                 // shared hold of the device's tenancy lock
-  int last_sched = 0;                            // schedule the last factorisation ran (diag)
   int s3_events = 0;  // LFM_S3_EVENTS: 1 schedule 3 ordered by events, 2 its timed launches serialised
   unsigned wait_ticks = 200000000u;              // device-side wait bound, 100 MHz ticks (2 s;
                                                  // LFM_DEVICE_WAIT_MS, LFM_DEBUG_SPIN_LIMIT)
-  int64_t fallbacks = 0;                         // schedule-3 calls re-run on schedule 1 after a
-                                                 // device-side wait timed out (lfm_ctx_fallbacks)
   bool grad_direct = false;                      // gradient: per-pair path only (LFM_GRAD_DIRECT)
   bool gram_fuse = true;                         // gram in the first update (LFM_GRAM_FUSE)
-  // the other run-time knobs, also read once when the context is created
   int64_t w4min = 6144;   // LFM_W4_MIN: bulk super-panels while the trailing matrix has this many rows
   int64_t w2min = -1;     // LFM_W2_MIN: w = 2 down to this many rows (-1: 5120 schedule 3, else 4096)
   int w0 = 1;             // LFM_W0: width of schedule 3's first super-panel
@@ -95,41 +95,93 @@ struct lfm_ctx {
   double rccl_timeout_s = 300.0;  // LFM_RCCL_TIMEOUT_S: bound on every farm collective wait
   int farm_stall_ms = 0;  // LFM_DEBUG_FARM_STALL_MS: test stand-in for a late peer rank
   bool small_kernarg = true;  // LFM_SMALL_KERNARG: small batches' table in the kernel arguments
-  double* gtab = nullptr; size_t gtab_bytes = 0; // gradient tables (grid layout)
-  double* result = nullptr;                      // [0..] scalar results
-  double* gacc = nullptr; size_t gacc_bytes = 0; // gradient accumulators + output
+  bool farm_graph_on = true;  // LFM_FARM_GRAPH: the device-side farm round as one captured graph
+  int ovl_on = 1;                    // LFM_OVERLAP: 0 evaluates lfm_mll_multi_f64's sets one by one
+  int64_t ovl_at = 6144;             // LFM_OVL_AT: the tail starts at the first step whose
+                                     // trailing matrix has fewer rows than this
+  int ovl_reserve = 96;              // LFM_OVL_RESERVE: main CUs the overlap stream leaves to the
+                                     // previous evaluation's tail
+};
 
-  unsigned long long* dbg_stamps = nullptr;     // lfm_debug_stamps: chain phases 256 x 16, then
+// A context's streams and events. A base of lfm_ctx, so they are destroyed after its members:
+// deleting a context frees its buffers (Buf) first, then the events, then the streams — the
+// order lfm_ctx_destroy has always had.
+struct CtxStreams {
+  hipStream_t stream = nullptr;  // main stream: gram fill, bulk trailing updates, finalize
+  hipStream_t side = nullptr;    // high-priority look-ahead stream: panel factor + solve
+  hipStream_t m3 = nullptr;      // schedule 3: bulk stream (CUs outside the chain's)
+  hipStream_t s3 = nullptr;      // schedule 3: factor-chain stream (LFM_SIDE_CUS CUs)
+  std::vector<hipEvent_t> evs;   // cross-stream dependency events (timing disabled)
+  // profiling: event pairs not read yet, and spare events
+  std::vector<ProfEvent> pending;
+  std::vector<hipEvent_t> pool;
+  ~CtxStreams();  // lfm_ctx.hip
+};
+
+}  // namespace lfm
+
+struct lfm_ctx : lfm::CtxStreams {
+  int device = 0;
+  lfm::Knobs knobs;
+  int cus = 256;                 // compute units of the device
+  std::string err;
+  int nb = 128;  // Cholesky block size
+
+  // device workspace, grown on demand
+  lfm::Buf<double> A;          // augmented factor (Mp x Mp) / generic matrix
+  lfm::Buf<double> tab;        // gene tables (fp64)
+  lfm::Buf<float> tab32;       // gene tables (fp32 copy)
+  lfm::Buf<double> par;        // packed hyperparameters + layout
+  lfm::Buf<double> xin;        // staged x / y / loc inputs
+  lfm::Buf<double> linvT;      // 8 x 16x16 inverses of the diagonal sub-blocks
+  lfm::Buf<double> parts;      // per-block logdet partials
+  lfm::Buf<int> status;        // [0] first failing pivot (INT_MAX = none)
+  lfm::Buf<double> wk;         // schedule 3: diagonal block + identity border
+  lfm::Buf<double> xbuf;       // schedule 3: solved panel X = A21 L11^{-T}
+  lfm::Buf<double> zvec;       // schedule 3: z = L^{-1} r
+  lfm::Buf<double> linv_full;  // schedule 3: 128x128 block inverse
+  lfm::Buf<double> xd;         // schedule 3: the chain's rows of X_{s-1}
+  lfm::Buf<unsigned> flags;    // schedule 3: per-step device flags
+  lfm::Buf<unsigned> psync;    // fused panel: [0] factor epoch, [1] slab count
+  unsigned panel_epoch = 0;                      // fused panel launches so far
+  int side_cus = 0;                              // CUs reserved for the side stream (LFM_SIDE_CUS)
+  bool s3_yield = false;                         // this call runs schedule 1: nested in a
+                                                 // shared hold of the device's tenancy lock
+  int last_sched = 0;                            // schedule the last factorisation ran (diag)
+  int64_t fallbacks = 0;                         // schedule-3 calls re-run on schedule 1 after a
+                                                 // device-side wait timed out (lfm_ctx_fallbacks)
+  lfm::Buf<double> gtab;       // gradient tables (grid layout)
+  lfm::Buf<double> result;     // [0..] scalar results
+  lfm::Buf<double> gacc;       // gradient accumulators + output
+
+  lfm::Buf<unsigned long long> dbg_stamps;      // lfm_debug_stamps: chain phases 256 x 16, then
                                                 // step launches 256 x 8
-  unsigned long long* dbg_trace = nullptr;      // lfm_debug_trace: 4 words per step-kernel unit
+  lfm::Buf<unsigned long long> dbg_trace;       // lfm_debug_trace: 4 words per step-kernel unit
   int64_t dbg_trace_cap = 0, dbg_trace_cur = 0;  // records allocated / written
   unsigned dbg_trace_launch = 0;                 // launches traced so far
 
   // pinned host staging
-  double* hpin = nullptr; size_t hpin_bytes = 0;
+  lfm::Buf<double, true> hpin;
 
   // profiling
   bool prof = false;
   unsigned prof_mask = ~0u;  // kernel classes timed while prof is on
-  std::vector<lfm::ProfEvent> pending;
-  std::vector<hipEvent_t> pool;
   lfm_kstat stats[lfm::K_NCLASS];
 
   // farm (RCCL)
   void* comm = nullptr;
   bool comm_nb = false;  // communicator created non-blocking (calls polled, bounded)
   int nranks = 0, rank = -1;
-  double* farm_buf = nullptr; size_t farm_bytes = 0;
-  double* farm_h = nullptr; size_t farm_h_bytes = 0;  // pinned host staging of the all-gather
-                                                      // (its own: a copy left queued by a timed-
-                                                      // out call can only ever write here)
-  double* farm_pub = nullptr; size_t farm_pub_bytes = 0;  // coherent pinned: the device-side
-                                                          // round's gathered slots + seq word
+  lfm::Buf<double> farm_buf;
+  lfm::Buf<double, true> farm_h;    // pinned host staging of the all-gather
+                                    // (its own: a copy left queued by a timed-
+                                    // out call can only ever write here)
+  lfm::Buf<double, true> farm_pub;  // coherent pinned: the device-side
+                                    // round's gathered slots + seq word
   unsigned farm_seq = 0;    // device-side rounds published so far
   bool farm_stale = false;  // an aborted farm call may have left work queued (drained first)
   // the device-side round captured as one graph (LFM_FARM_GRAPH, default 1; read at creation),
   // replayed while its key (batch id, slots, sign, communicator generation) holds
-  bool farm_graph_on = true;
   hipGraphExec_t farm_exec = nullptr;
   hipGraphExec_t farm_exec_old = nullptr;  // dropped by an aborted round: destroyed once drained
   uint64_t farm_exec_batch = 0, comm_gen = 0, farm_exec_gen = 0;
@@ -148,11 +200,6 @@ struct lfm_ctx {
   hipEvent_t ovl_tail = nullptr;     // twin: recorded on m3 ahead of its tail's first launch
   hipEvent_t ovl_done = nullptr;     // twin: recorded on m3 after its finalize
   hipEvent_t ovl_res = nullptr;      // twin: its result copied to the host (primary's stream)
-  int ovl_on = 1;                    // LFM_OVERLAP: 0 evaluates lfm_mll_multi_f64's sets one by one
-  int64_t ovl_at = 6144;             // LFM_OVL_AT: the tail starts at the first step whose
-                                     // trailing matrix has fewer rows than this
-  int ovl_reserve = 96;              // LFM_OVL_RESERVE: main CUs the overlap stream leaves to the
-                                     // previous evaluation's tail
 };
 
 // ---------------------------------------------------------------- helpers
@@ -166,15 +213,13 @@ constexpr int STATUS_TIMEOUT = -2;
 int status_code(lfm_ctx* ctx, double st, double why = 0.0);
 
 // The next factorisation on ctx runs schedule 3: the CU-partitioned pair exists and the call
-// is not nested in a shared hold of the device's tenancy lock (lfm_api.hip DeviceTenancy).
+// is not nested in a shared hold of the device's tenancy lock (lfm_ctx.hip DeviceTenancy).
 inline bool s3_on(const lfm_ctx* ctx) {
-  return ctx->sched == 3 && ctx->side_cus > 0 && !ctx->s3_yield;
+  return ctx->knobs.sched == 3 && ctx->side_cus > 0 && !ctx->s3_yield;
 }
 
 int set_err(lfm_ctx* ctx, int code, const std::string& msg);
 int hip_fail(lfm_ctx* ctx, hipError_t e, const char* what);
-int ensure(lfm_ctx* ctx, void** p, size_t* cap, size_t bytes);
-int ensure_pinned(lfm_ctx* ctx, size_t bytes);
 
 // profiling hooks around a launch on ctx->stream
 void prof_begin(lfm_ctx* ctx, int cls, hipEvent_t* a, hipStream_t st = nullptr);
@@ -215,11 +260,7 @@ struct SmallProb {
   const double* times = nullptr;  // [T]
   const int* bg = nullptr;        // [n / T] gene of each block
 };
-// host: detect the grid layout of problem p and, when its tables fit the kernel's budget, put
-// its times and block genes at hd (device address dd) and fill sp's grid fields; returns the
-// doubles used (at most small_grid_doubles(n))
-int64_t small_grid_pack(const double* x, int64_t n, int64_t G, SmallProb& sp, double* hd,
-                        const double* dd);
+// doubles small_grid_pack (lfm_batch.hip) uses at most for a problem's times and block genes
 inline int64_t small_grid_doubles(int64_t n) { return n + (n + 1) / 2; }
 // largest per-problem grid table (doubles) in LDS: with n = 128 beside it the launch stays
 // within a CU's 160 KB (launch_small_batch)
@@ -348,7 +389,7 @@ size_t small_grid_extra(int n, int G, int T);
 int launch_small_batch(lfm_ctx* ctx, const SmallProb* d_probs, int nprob, int maxn, int maxg,
                        int gridtab, int negative, double* d_out, int* d_status);
 
-// Path of the advisory lock file behind schedule 3's cross-process tenancy (lfm_api.hip;
+// Path of the advisory lock file behind schedule 3's cross-process tenancy (lfm_ctx.hip;
 // empty if the device has no PCI bus id)
 std::string tenancy_lock_path(int dev);
 

@@ -66,7 +66,7 @@ int posterior_blocked(lfm_ctx* ctx, const HypDev& h, const double* d_x, const do
                       double* d_mean, double* d_cov) {
   const int64_t Np = (n + 127) / 128 * 128;
   const int64_t Mtot = (Np + m + 1 + 127) / 128 * 128;
-  int r = ensure(ctx, (void**)&ctx->A, &ctx->A_bytes, (size_t)Mtot * Mtot * sizeof(double));
+  int r = ctx->A.reserve(ctx, (size_t)Mtot * Mtot * sizeof(double));
   if (r) return r;
   double* A = ctx->A;
   r = launch_gram_direct<double>(ctx, h, d_x, n, d_x, n, diag_add, 0.0, LFM_UPLO_LOWER, A, Mtot);

@@ -212,7 +212,7 @@ static void check_oracle() {
   std::printf("oracle: mll %.10f\n", v1);
 }
 
-// The device tenancy lock (TenancyLock, lfm_api.hip DeviceTenancy). Two objects on one path
+// The device tenancy lock (TenancyLock, lfm_ctx.hip DeviceTenancy). Two objects on one path
 // stand for two processes (flock is per open file description).
 static void check_tenancy() {
   using clk = std::chrono::steady_clock;

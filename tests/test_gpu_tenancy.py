@@ -1,4 +1,4 @@
-"""Schedule 3 is single tenant per GPU (include/lfm.h lfm_ctx_set_schedule; lfm_api.hip
+"""Schedule 3 is single tenant per GPU (include/lfm.h lfm_ctx_set_schedule; lfm_ctx.hip
 DeviceTenancy): its factor chain needs every workgroup resident on the reserved CUs, so two
 chains, or any other work refilling those CUs, starve it at its grid barriers. The library
 holds a per-device readers-writer lock over its GPU work — exclusive for a schedule-3
