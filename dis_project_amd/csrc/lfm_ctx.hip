@@ -112,7 +112,7 @@ void release_partition(lfm_ctx* ctx) {
 //   LFM_GRAD_DIRECT      1: the gradient's per-pair path even on a grid layout (cross-check)
 //   LFM_GRAM_FUSE        0: the full gram in its own kernel even where the first update could
 //                        generate it (cross-check: the MLL is bit-identical either way)
-//   LFM_W4_MIN / LFM_W2_MIN / LFM_W0   the step plan (lfm_chol.hip chol_factor_solve)
+//   LFM_W4_MIN / LFM_W2_MIN / LFM_W0   the step plan (lfm_chol_sched.hip chol_factor_solve)
 //   LFM_HELPER / LFM_HELPER_TC / LFM_HELPER_MIN   schedule 3's side-CU helper and its sizing
 //   LFM_S3_FALLBACK      0: a stalled schedule-3 call returns LFM_E_TIMEOUT (no schedule-1 re-run)
 //   LFM_RCCL_TIMEOUT_S   bound on every wait of the farm communicator (default 300 s)

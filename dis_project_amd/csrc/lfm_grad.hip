@@ -6,7 +6,7 @@
 //     a = S^{-1} r,  W = a a^T - S^{-1},  r = y - m,
 // for theta in true_d, true_s, true_b [G], l and obs_stddev (jitter is static, model.py:64).
 //
-// S^{-1} comes from the bordered factorisation (lfm_chol.hip, chol_factor_solve with
+// S^{-1} comes from the bordered factorisation (lfm_chol_sched.hip, chol_factor_solve with
 // bordered = 1): the 2Mp x 2Mp matrix [[S_aug, .], [I, 0]] is eliminated through its first
 // Mp columns, which leaves -(L_aug^{-T} L_aug^{-1}) in the bottom block. With the residual
 // row n of the augmented factor (z = L^{-1} r, unit pivot) that block is

@@ -134,6 +134,165 @@ int64_t helper_clamp(int64_t hu, int nr, int T, int wn, int lead, int Q) {
 }
 
 namespace {
+// Algorithmic flops (profiling) of rest units [b0, b1) of a step's update: 2 kd per updated
+// lower element of their tiles, rows past n (identity padding) excluded
+double units_alg(const S3Params& p, int64_t s0, int T, int wn, int kd, int64_t b0, int64_t b1) {
+  double a = 0.0;
+  for (int64_t b = b0; b < b1; ++b) {
+    int ti, tj;
+    rest_unit_tile(b, T, wn, p.supertile, &ti, &tj);
+    const int64_t i0 = s0 + (int64_t)ti * 64, j0 = s0 + (int64_t)tj * p.st;
+    for (int64_t r = i0; r < i0 + 64 && (p.bordered || r <= p.n); ++r)
+      a += (double)std::max<int64_t>(0, std::min<int64_t>(p.st, r - j0 + 1));
+  }
+  return a * 2.0 * kd;
+}
+
+// Flops of one step-kernel launch: the update of step u with nr_main of its rest units (u NULL:
+// none) and the tall units of step t (NULL: none); alg_adjust: algorithmic flops of the update
+// done elsewhere (the helper's tail, a kernel class of its own).
+// issued: every 64 x 128 unit in full (padding rows included), tall units as GEMMs with the
+// triangular inverse; algorithmic: the update of the unpadded augmented trailing matrix (rows
+// s0 .. n, residual row n included: it is the forward substitution) less the next diagonal
+// block (the chain's), and the triangular solve of the rows below the next super-panel (rows
+// .. n) against its W' x W' factor
+void launch_flops(const S3Params& p, const S3Step* u, int64_t nr_main, const S3Step* t,
+                  double alg_adjust, double* alg_out, double* issued_out) {
+  const int NB = p.nb, ST = p.st;
+  const int na = u ? u->na : 0, kd = u ? u->w * NB : 0;
+  const int nr = u ? (int)nr_main : 0, nt = t ? t->nt : 0, tw = t ? t->tw : 0;
+  *issued_out = ((double)na + nr) * 64 * ST * 2.0 * kd +
+                (double)nt * 64 * (ST / p.tall_split) * NB * (tw + 1);
+  double alg = 0.0;
+  if (na + nr > 0) {
+    // bordered: the whole Mp-row window is algorithmic (Cholesky + inverse = Mp^3)
+    const double m = p.bordered ? (double)p.Mp : (double)(p.n - u->K1);
+    const double d = std::min<double>(u->wn * NB, m);
+    alg += 2.0 * kd * (m * (m + 1) / 2 + (p.bordered ? 0.0 : m) - d * (d + 1) / 2);
+  }
+  if (nt > 0) {
+    const double W2 = (double)tw * NB;
+    const int64_t rows = p.bordered ? t->tk0 + p.Mp - t->tr0 : p.n + 1 - t->tr0;
+    alg += (double)std::max<int64_t>(0, rows) * W2 * W2;
+  }
+  *alg_out = alg - alg_adjust;
+}
+}  // namespace
+
+S3Plan plan_s3(const std::vector<std::pair<int64_t, int>>& steps, const S3Params& p) {
+  S3Plan P;
+  P.params = p;
+  P.step_list = steps;
+  const int S = (int)steps.size(), NB = p.nb, ST = p.st;
+  const int64_t n = p.n, Mp = p.Mp;
+  // the trailing matrix of a step whose super-panel ends at column K1: rows / columns [K1, Mp)
+  // (MLL), or the Mp-row window [K1, K1 + Mp) the identity border has reached (bordered: rows
+  // Mp + j are zero in panel columns < j; the window size is constant)
+  auto rows_end = [&](int64_t K1) { return p.bordered ? K1 + Mp : Mp; };
+  P.S = S;
+  int wmax = 1;
+  for (const auto& st : steps) wmax = std::max(wmax, st.second);
+  const int64_t Wmax = P.Wmax = (int64_t)wmax * NB, Tmax = P.Tmax = Mp / ST + 1;
+  // two workspaces: chain(s + 1) starts while the tall units of step s still read Bd_s
+  P.wk_bytes = (size_t)4 * Wmax * Wmax * sizeof(double);
+  P.xbuf_bytes = (size_t)2 * Mp * Wmax * sizeof(double);
+  P.zvec_bytes = (size_t)Mp * sizeof(double);
+  P.linv_bytes = (size_t)NB * NB * sizeof(double);
+  P.xd_bytes = (size_t)Wmax * Wmax * sizeof(double);
+  P.nflags = (size_t)S * (3 + Tmax);
+  P.flags_bytes = P.nflags * sizeof(unsigned);
+  P.chain_done = 0;
+  P.a_done = (size_t)S;
+  P.bars = P.a_done + (size_t)S * Tmax;  // grid barrier counters of chain(s)
+  P.xready = P.bars + S;                 // inputs of chain(s) landed (s >= 1)
+  // MLL: rows past n are identity padding whose updates nothing reads; bordered: none is
+  // skipped (the border rows have real entries in the padding columns, which are eliminated
+  // too, so the padding rows' X must exist)
+  P.pad_end = p.bordered ? n + 1 : INT64_MAX;
+  P.zsplit = n;  // finalize: z columns below zsplit come from zvec
+  P.nevents = chol_events(S);
+  P.steps.resize(S);
+  for (int s = 0; s < S; ++s) {
+    S3Step& q = P.steps[s];
+    q.w = steps[s].second;
+    q.kd = q.w * NB;
+    q.K0 = steps[s].first * NB;
+    q.K1 = (steps[s].first + steps[s].second) * NB;
+    q.wn = s + 1 < S ? steps[s + 1].second : 0;
+    q.T = (int)((rows_end(q.K1) - q.K1) / ST);
+    // update of step s (trailing matrix from K1), excluding the next diagonal block (none after
+    // the last super-panel: the bordered mode's final update of its border block)
+    q.na = 2 * q.wn * (q.T - q.wn);
+    q.nr = (q.T - q.wn) * (q.T - q.wn + 1);  // two 64-row units per tile of the triangle
+    // tall units of step s: rows [K1, rows_end) x w column blocks
+    q.nt = (int)((rows_end(q.K1) - q.K1) / 64 * q.w * p.tall_split);
+    q.tr0 = q.K0 + (int64_t)q.w * NB;
+    q.tk0 = q.K0;
+    q.tw = q.w;
+    if (p.bordered) q.zero_from = q.copy_from = Mp + q.K0;
+    q.gen = p.fused && s == 0;
+    // launch s writes the inputs of chain(s + 2): the block's tiles (leading rest units,
+    // w (w + 1) 64-row slabs) and its rows of the columns of super-panel s + 1 (leading ahead
+    // units, 2 w w_{s+1} slabs); chain(s + 2) forms X_{s+1} of its rows
+    if (s + 2 < S) q.lead = steps[s + 2].second;
+    if (s >= 2) q.xtarget = (unsigned)(q.w * (q.w + 1) + 2 * q.w * steps[s - 1].second);
+    q.nr_main = q.nr;
+    q.f_done = P.chain_done + s;
+    q.f_adone = P.a_done + (size_t)s * Tmax;
+    q.f_bar = P.bars + s;
+    q.f_xready = P.xready + s;
+    q.wk_off = (size_t)(s & 1) * 2 * Wmax * Wmax;
+    q.bd_off = q.wk_off + (size_t)((int64_t)q.w * NB * q.w * NB);
+    q.x_off = (size_t)(s & 1) * Mp * Wmax;
+    q.ugrid = pad8(q.na) + pad8(q.nr);
+    q.tgrid = tall_grid(q.nt, p.tall_split);
+    launch_flops(p, &q, q.nr, nullptr, 0.0, &q.upd_alg, &q.upd_issued);
+    launch_flops(p, nullptr, 0, &q, 0.0, &q.tall_alg, &q.tall_issued);
+    // chain(s), algorithmic: the block's factor W^3 / 3, its pending update from X_{s-1} (the
+    // block's lower elements x 2 kd) and its rows of X_{s-1} (W kd^2); issued adds the block
+    // inverse (W^3) and the padded 32 x 32 tiles
+    const double W = q.w * NB, kd = s > 0 ? steps[s - 1].second * NB : 0;
+    q.chain_alg = W * W * W / 3.0 + W * (W + 1) * kd + W * kd * kd;
+    q.chain_issued = W * W * W / 3.0 + W * W * W + W * W * kd + 2.0 * W * kd * kd;
+  }
+  bool tail_marked = false;
+  for (int s = 0; s < S; ++s) {
+    S3Step& q = P.steps[s];
+    if (s + 1 == S) {  // the last super-panel: only the bordered mode updates past it
+      q.grid = p.bordered ? q.ugrid : 0;
+      q.step_alg = q.upd_alg;
+      q.step_issued = q.upd_issued;
+      break;
+    }
+    const S3Step& nx = P.steps[s + 1];
+    // Side-CU helper: the tail of this step's rest units, sized to end with the main launch
+    // (helper_units), never a lead tile of chain(s + 2) (helper_clamp)
+    if (p.helper && s >= 1 && s + 2 < S)
+      q.hu = helper_clamp(helper_units(q.w * NB, q.na, q.nr, nx.nt / p.tall_split, nx.w, NB,
+                                       p.cus, p.side_cus, p.helper_tc, p.helper_min),
+                          q.nr, q.T, q.wn, q.lead, p.supertile);
+    q.nr_main = (int)(q.nr - q.hu);
+    if (p.prof && q.hu > 0)
+      q.helper_alg = units_alg(p, q.K1, q.T, q.wn, q.w * NB, q.nr_main, q.nr);
+    q.helper_issued = (double)q.hu * 64 * ST * 2.0 * (q.w * NB);
+    q.hgrid = pad8((int)q.hu);
+    q.grid = pad8(q.na) + pad8(q.nr_main) + nx.tgrid;
+    launch_flops(p, &q, q.nr_main, &nx, q.helper_alg, &q.step_alg, &q.step_issued);
+    // overlapped: the next evaluation may start once the launches before this evaluation's
+    // tail have run (its first step below ovl_at trailing rows)
+    if (!tail_marked && s >= 1 && rows_end(q.K1) - q.K1 < p.ovl_at) q.ovl_mark = tail_marked = true;
+  }
+  return P;
+}
+
+bool plan_s3_keep(S3Plan& kept, const std::vector<std::pair<int64_t, int>>& steps,
+                  const S3Params& p) {
+  if (kept.params == p && kept.step_list == steps) return false;
+  kept = plan_s3(steps, p);
+  return true;
+}
+
+namespace {
 // flock, restarted when a signal interrupts the wait; 0 or the errno of the failure
 int flock_retry(int fd, int op) {
   for (;;) {

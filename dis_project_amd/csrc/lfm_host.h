@@ -1,5 +1,7 @@
 // lfm_host.h — host-only logic of liblfm: x-layout detection, the factorisation's step plan,
-// the host mirror of the trailing update's unit enumeration and the side-CU helper's sizing.
+// the host mirror of the trailing update's unit enumeration, the side-CU helper's sizing and
+// schedule 3's whole launch plan (plan_s3: every unit count, grid, buffer and flag offset,
+// device-counter target and profiling figure of a call, which lfm_chol_sched.hip only reads).
 // Plain C++ (no HIP types), so lfm_host.cpp also builds into the host sanitizer check
 // (tests/native, `make -C tests/native asan`) with g++ -fsanitize=address,undefined.
 #pragma once
@@ -10,6 +12,7 @@
 #include <mutex>
 #include <shared_mutex>
 #include <string>
+#include <tuple>
 #include <utility>
 #include <vector>
 
@@ -86,6 +89,101 @@ int64_t helper_units(int kd, int na, int nr, int nt, int wnext, int nb, int cus,
 // enumeration mirror still finds a lead tile in the tail, and for band-enumerated regions
 // (T - wn <= kBandMaxCols).
 int64_t helper_clamp(int64_t hu, int nr, int T, int wn, int lead, int Q);
+
+// Workgroups of a step launch's ahead / rest segment: the units padded to a multiple of 8 (one
+// queue per XCD)
+LFM_HD constexpr int64_t pad8(int units) { return (int64_t)(units + 7) / 8 * 8; }
+// ... and of its tall segment: a multiple of 8 split (8 XCDs, the pieces of one row block back
+// to back: lfm_chol.hip tall_or_xcd_range)
+LFM_HD constexpr int64_t tall_grid(int64_t nt, int split) {
+  return (nt + 8 * split - 1) / (8 * split) * (8 * split);
+}
+
+// Events a factorisation of S steps orders its streams with (lfm_chol_sched.hip): [0] inputs
+// ready, [1, 2 S + 1) per-step pairs, [2 S + 1] side stream done, [2 S + 2] hand-back,
+// [2 S + 3, 3 S + 3) the chains of LFM_S3_EVENTS=2
+constexpr size_t chol_events(int S) { return 3 * (size_t)S + 3; }
+
+// What schedule 3's plan needs besides the step list. st / tall_split / supertile: the kernels'
+// tile constants (lfm_chol.h ST, TALL_SPLIT, SUPERTILE); the knobs as lfm_internal.h Knobs has
+// them. prof: also enumerate the helpers' algorithmic flops (S3Step::helper_alg; a loop over
+// every helper unit's rows, so only while the profiler is on).
+struct S3Params {
+  int64_t n = 0, Mp = 0;
+  bool bordered = false, fused = false, prof = false;
+  int nb = 128, st = 128, tall_split = 2, supertile = 6;
+  int cus = 256, side_cus = 32;
+  int helper = 1;
+  double helper_tc = 700, helper_min = 1200;
+  int64_t ovl_at = 6144;
+};
+inline bool operator==(const S3Params& a, const S3Params& b) {
+  auto t = [](const S3Params& p) {
+    return std::tie(p.n, p.Mp, p.bordered, p.fused, p.prof, p.nb, p.st, p.tall_split, p.supertile,
+                    p.cus, p.side_cus, p.helper, p.helper_tc, p.helper_min, p.ovl_at);
+  };
+  return t(a) == t(b);
+}
+
+// Step s of schedule 3: super-panel s (columns [K0, K1), w block columns), its X_s (the tall
+// units), its trailing update (ahead + rest units) and the launches that carry them. The
+// device-ordered step launch s is update(s) + tall(s + 1); LFM_S3_EVENTS=1 launches the two
+// apart.
+struct S3Step {
+  int64_t K0 = 0, K1 = 0;
+  int w = 0, kd = 0;    // kd = W_s = nb w: the depth of the step's update
+  int T = 0, wn = 0;   // trailing 128-tiles from K1; the next super-panel's width (0: none)
+  int na = 0, nr = 0;   // ahead units; the whole rest enumeration (the main launch: nr - hu)
+  // tall units: X_s = A[tr0 .., tk0 ..) Bd_s, tw column blocks
+  int nt = 0, tw = 0;
+  int64_t tr0 = 0, tk0 = 0;
+  int64_t zero_from = INT64_MAX, copy_from = INT64_MAX;  // StepArgs (bordered only)
+  bool gen = false;     // the update generates Sigma (fused gram: step 0)
+  // chain(s + 2) starts while launch s runs: lead = w_{s+2} (0: none waits); xtarget: the lead
+  // units of launch s - 2 chain(s) waits for (s >= 2), w_s (w_s + 1) rest + 2 w_s w_{s-1} ahead
+  int lead = 0;
+  unsigned xtarget = 0;
+  int64_t hu = 0;       // the side-CU helper's share: rest units [nr_main, nr), nr_main = nr - hu
+  int nr_main = 0;
+  // this step's flags (offsets into the flag array): chain_done[s], a_done[s][0], bars[s],
+  // xready[s]
+  size_t f_done = 0, f_adone = 0, f_bar = 0, f_xready = 0;
+  int64_t grid = 0;     // step launch s: pad8(na) + pad8(nr_main) + tall_grid(nt_{s+1})
+  int64_t hgrid = 0;    // helper launch
+  int64_t ugrid = 0, tgrid = 0;  // update(s) alone (no helper), tall(s) alone
+  bool ovl_mark = false;         // the overlap tail (LFM_OVL_AT) starts ahead of launch s
+  // the (s & 1) buffers, in doubles: the chain's workspace in wk, Bd_s in wk, X_s in xbuf
+  size_t wk_off = 0, bd_off = 0, x_off = 0;
+  // profiling (lfm_profile_read): algorithmic / issued flops of step launch s, of update(s) and
+  // tall(s) alone, of the helper and of chain(s)
+  double step_alg = 0, step_issued = 0, upd_alg = 0, upd_issued = 0, tall_alg = 0,
+         tall_issued = 0, helper_alg = 0, helper_issued = 0, chain_alg = 0, chain_issued = 0;
+};
+
+struct S3Plan {
+  // what the plan was built from: a context keeps its last plan per mode and builds the next
+  // call's only when these differ (the helper's lead-tile scan makes a plan cost 0.2 - 1 ms of
+  // host time at N = 16384, which would otherwise precede the call's first launch)
+  S3Params params;
+  std::vector<std::pair<int64_t, int>> step_list;
+  int S = 0;
+  int64_t Wmax = 0, Tmax = 0;
+  size_t wk_bytes = 0, xbuf_bytes = 0, zvec_bytes = 0, linv_bytes = 0, xd_bytes = 0,
+         flags_bytes = 0;
+  // the flag array (unsigned): chain_done [S], a_done [S][Tmax], bars [S], xready [S]
+  size_t nflags = 0, chain_done = 0, a_done = 0, bars = 0, xready = 0;
+  int64_t pad_end = 0, zsplit = 0;
+  size_t nevents = 0;
+  std::vector<S3Step> steps;
+};
+
+// The whole launch plan of one schedule-3 factorisation over plan_steps' step list, computed
+// once per call (lfm_chol_sched.hip reserves what it says and issues its launches).
+S3Plan plan_s3(const std::vector<std::pair<int64_t, int>>& steps, const S3Params& p);
+// The same through a kept plan (a context's last one in this mode): rebuilt only if it was built
+// from other inputs. Returns whether it was rebuilt.
+bool plan_s3_keep(S3Plan& kept, const std::vector<std::pair<int64_t, int>>& steps,
+                  const S3Params& p);
 
 // Readers-writer lock over one GPU's library work (lfm_ctx.hip DeviceTenancy: a schedule-3
 // factorisation exclusive, all other GPU work shared). In-process a std::shared_mutex; across

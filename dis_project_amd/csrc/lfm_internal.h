@@ -142,6 +142,8 @@ struct lfm_ctx : lfm::CtxStreams {
   lfm::Buf<double> linv_full;  // schedule 3: 128x128 block inverse
   lfm::Buf<double> xd;         // schedule 3: the chain's rows of X_{s-1}
   lfm::Buf<unsigned> flags;    // schedule 3: per-step device flags
+  lfm::S3Plan s3_plan[2];      // schedule 3: the last MLL / bordered call's launch plan, reused
+                               // while its inputs hold (lfm_chol_sched.hip schedule3)
   lfm::Buf<unsigned> psync;    // fused panel: [0] factor epoch, [1] slab count
   unsigned panel_epoch = 0;                      // fused panel launches so far
   int side_cus = 0;                              // CUs reserved for the side stream (LFM_SIDE_CUS)
@@ -301,7 +303,7 @@ struct GramGen {
 int launch_gram_region(lfm_ctx* ctx, const GramGen& g, int64_t r0, int64_t r1, int64_t c0,
                        int64_t c1, double* out, int64_t ldo);
 
-// cholesky kernels (lfm_chol.hip)
+// the factorisation (lfm_chol_sched.hip; its kernels: lfm_chol.hip, lfm_chol.h)
 enum CholMode { CHOL_MLL = 0, CHOL_INVERSE = 1, CHOL_SCHUR = 2 };
 // gen: the gram to fuse (lfm_api decides with chol_fuses_gram; the full gram is then NOT in A)
 int chol_factor_solve(lfm_ctx* ctx, double* A, int64_t lda, int64_t n, int64_t Mp, int negative,
@@ -394,7 +396,7 @@ int launch_small_batch(lfm_ctx* ctx, const SmallProb* d_probs, int nprob, int ma
 std::string tenancy_lock_path(int dev);
 
 // Hook of the diagnostics library (liblfm_diag.so, lfm_diag.hip): one launch of the
-// trailing-update kernel over a full triangle (lfm_chol.hip; launch only, no kernel of its own)
+// trailing-update kernel over a full triangle (lfm_chol_sched.hip; launch only, no kernel of its own)
 int probe_update_launch(lfm_ctx* ctx, hipStream_t st, int T, int kd, int cio, int64_t n,
                         size_t xb);
 

@@ -77,7 +77,7 @@ int lfm_probe_rate(lfm_ctx* ctx, int which, int nblocks, int iters, double* tflo
 /* The trailing-update kernel alone (64-row slabs) on a T x T grid of 128-tiles, depth kd:
  * average us per launch. cio bit 0: C tile I/O (else MFMAs only), bit 3: random operands,
  * bit 4: on schedule 3's CU-masked bulk stream, bit 6: the step kernel's rest role (the other
- * bits: lfm_chol.hip probe_update_launch). */
+ * bits: lfm_chol_sched.hip probe_update_launch). */
 int lfm_probe_syrk(lfm_ctx* ctx, int T, int kd, int cio, int reps, double* us);
 
 #ifdef __cplusplus

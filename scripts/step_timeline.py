@@ -22,11 +22,11 @@ from dis_project_amd import _lib, configs  # noqa: E402
 
 NB = 128
 SLOTS = 4 * 224  # resident step-kernel workgroups: 4 per main-stream CU (32 side CUs)
-TALL_SPLIT = 2  # tall units per 64-row x 128-column block of X (lfm_chol.hip TALL_SPLIT)
+TALL_SPLIT = 2  # tall units per 64-row x 128-column block of X (lfm_chol.h TALL_SPLIT)
 
 
 def plan(n, bordered=False):
-    """Schedule 3's step plan (lfm_chol.hip chol_factor_solve, default LFM_W4_MIN/W2_MIN)."""
+    """Schedule 3's step plan (lfm_chol_sched.hip chol_factor_solve, default LFM_W4_MIN/W2_MIN)."""
     Mp = (n + 1 + NB - 1) // NB * NB
     nblk = Mp // NB if bordered else (n + NB - 1) // NB
     w4 = int(os.environ.get("LFM_W4_MIN", 6144))
@@ -34,7 +34,7 @@ def plan(n, bordered=False):
     steps, k = [], 0
     while k < nblk:
         m = Mp + NB if bordered else Mp - k * NB
-        # the bulk width (lfm_chol.hip chol_factor_solve): 5, its first super-panel 4 (MLL)
+        # the bulk width (lfm_chol_sched.hip chol_factor_solve): 5, its first super-panel 4 (MLL)
         wb = 4 if bordered or len(steps) == 1 else 5
         w = wb if (m >= w4 and k + wb <= nblk) else 4 if (m >= w4 and k + 4 <= nblk) else \
             2 if (m >= w2 and k + 2 <= nblk) else 1
@@ -114,7 +114,7 @@ def main():
         tf = alg / (upd * 1e-6) / 1e12 if upd > 0 else 0.0
         mhz = float(sp[s][4]) / float(sp[s][5]) * 100.0 if sp[s][5] else 0.0
         T = (m + NB - 1) // NB if not grad else Mp // NB
-        nr = (T - wn) * (T - wn + 1)  # rest units (lfm_chol.hip update_args)
+        nr = (T - wn) * (T - wn + 1)  # rest units (lfm_host.cpp plan_s3)
         unit_us = float(sp[s][5]) * 0.01 / nr if nr > 0 else 0.0
         na = 2 * wn * (T - wn)  # ahead units
         # tall units of this launch (X_{s+1}): rows below the next diagonal block, identity

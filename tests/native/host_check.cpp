@@ -12,8 +12,11 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
+#include <climits>
+#include <map>
 #include <random>
 #include <set>
+#include <tuple>
 #include <string>
 #include <thread>
 #include <vector>
@@ -178,6 +181,501 @@ static void check_plan() {
         ++cases;
       }
   std::printf("plan_steps: %d cases\n", cases);
+}
+
+// ---- schedule 3's launch plan (plan_s3) ----
+static constexpr int kST = 128, kSplit = 2, kQ = 6;  // lfm_chol.h ST, TALL_SPLIT, SUPERTILE
+
+static S3Params s3_params(int64_t n, int64_t Mp, bool bordered, int side_cus, int helper,
+                          bool prof) {
+  S3Params p;
+  p.n = n;
+  p.Mp = Mp;
+  p.bordered = bordered;
+  p.prof = prof;
+  p.st = kST;
+  p.tall_split = kSplit;
+  p.supertile = kQ;
+  p.cus = 256;
+  p.side_cus = side_cus;
+  p.helper = helper;
+  return p;
+}
+
+// Lead units among rest units [b0, b1) of a step's enumeration, as the device finds them
+// (syrk_unit in_lead: tile row and column < wn + lead): the triangle through the enumeration
+// mirror, a band region (<= kBandMaxCols columns) column by column as unit_tile's band branch
+static int64_t lead_rest_units(int T, int wn, int lead, int64_t b0, int64_t b1) {
+  static std::map<std::tuple<int, int, int, int64_t, int64_t>, int64_t> memo;
+  const auto key = std::make_tuple(T, wn, lead, b0, b1);
+  const auto it = memo.find(key);
+  if (it != memo.end()) return it->second;
+  int64_t cnt = 0;
+  if (T - wn > kBandMaxCols) {
+    for (int64_t b = b0; b < b1; ++b) {
+      int ti, tj;
+      rest_unit_tile(b, T, wn, kQ, &ti, &tj);
+      cnt += ti / 2 < wn + lead && tj < wn + lead;
+    }
+  } else {
+    int64_t b = 0;
+    for (int tj = wn; tj < T; ++tj)
+      for (int ti = 2 * tj; ti < 2 * T; ++ti, ++b)
+        cnt += b >= b0 && b < b1 && ti / 2 < wn + lead && tj < wn + lead;
+    CHECK(b == (int64_t)(T - wn) * (T - wn + 1), "band enumeration size");
+  }
+  return memo[key] = cnt;
+}
+
+static void check_s3_plan(const std::vector<std::pair<int64_t, int>>& steps, const S3Params& p,
+                          const S3Plan& P, const char* tag) {
+  const int S = P.S;
+  const int64_t rows = p.bordered ? 2 * p.Mp : p.Mp;  // of the matrix
+  CHECK(S == (int)steps.size() && (int)P.steps.size() == S && S >= 1, "%s: steps", tag);
+  // the plan names its inputs (a context reuses its last plan while they hold)
+  S3Params other = p;
+  other.n += 1;
+  CHECK(P.params == p && !(P.params == other) && P.step_list == steps, "%s: plan inputs", tag);
+  // flag layout: four regions, disjoint, in order, ending at nflags
+  CHECK(P.chain_done == 0 && P.a_done == P.chain_done + S &&
+            P.bars == P.a_done + (size_t)S * P.Tmax && P.xready == P.bars + S &&
+            P.nflags == P.xready + S && P.flags_bytes == P.nflags * sizeof(unsigned),
+        "%s: flag regions", tag);
+  CHECK(P.nevents == chol_events(S) && P.nevents >= (size_t)3 * S + 3, "%s: events", tag);
+  CHECK(P.pad_end == (p.bordered ? p.n + 1 : INT64_MAX) && P.zsplit == p.n, "%s: pad_end", tag);
+  CHECK(P.zvec_bytes >= (size_t)p.Mp * 8 && P.linv_bytes >= 128 * 128 * 8, "%s: zvec", tag);
+  int marks = 0;
+  double alg = 0.0;
+  for (int s = 0; s < S; ++s) {
+    const S3Step& q = P.steps[s];
+    const int64_t W = (int64_t)q.w * 128, end = p.bordered ? q.K1 + p.Mp : p.Mp;
+    CHECK(q.K0 == steps[s].first * 128 && q.w == steps[s].second && q.K1 == q.K0 + W &&
+              q.kd == W && W <= P.Wmax, "%s s=%d: columns", tag, s);
+    CHECK(q.wn == (s + 1 < S ? steps[s + 1].second : 0), "%s s=%d: wn", tag, s);
+    // flags of the step: each index inside its region
+    CHECK(q.f_done >= P.chain_done && q.f_done < P.a_done, "%s s=%d: chain_done", tag, s);
+    CHECK(q.f_adone >= P.a_done && q.f_adone + P.Tmax <= P.bars && q.T <= P.Tmax,
+          "%s s=%d: a_done row", tag, s);
+    CHECK(q.f_bar >= P.bars && q.f_bar < P.xready, "%s s=%d: bars", tag, s);
+    CHECK(q.f_xready >= P.xready && q.f_xready < P.nflags, "%s s=%d: xready", tag, s);
+    // buffers: the chain's 2W x W workspace, Bd_s (W x W), X_s (rows [K1, end) x W), the
+    // chain's W x kd_{s-1} rows of X_{s-1}
+    CHECK((q.wk_off + 2 * W * W) * 8 <= P.wk_bytes && q.bd_off == q.wk_off + (size_t)(W * W),
+          "%s s=%d: workspace", tag, s);
+    CHECK((q.x_off + (size_t)((end - q.K1) * W)) * 8 <= P.xbuf_bytes, "%s s=%d: X buffer", tag, s);
+    if (s > 0) {
+      CHECK((size_t)(W * P.steps[s - 1].kd) * 8 <= P.xd_bytes, "%s s=%d: xd", tag, s);
+      CHECK(q.wk_off != P.steps[s - 1].wk_off && q.x_off != P.steps[s - 1].x_off,
+            "%s s=%d: buffers alternate", tag, s);
+    }
+    // the matrix: the trailing tiles, the tall rows and the panel columns
+    CHECK(q.K1 <= p.Mp && q.K1 + (int64_t)128 * q.T <= rows && q.T >= 0, "%s s=%d: tiles", tag, s);
+    CHECK(q.tk0 == q.K0 && q.tr0 == q.K1 && q.tw == q.w && q.tk0 + W <= p.Mp,
+          "%s s=%d: tall columns", tag, s);
+    CHECK(q.nt % (q.w * kSplit) == 0 && q.tr0 + 64 * (int64_t)(q.nt / (q.w * kSplit)) <= rows &&
+              q.nt == (end - q.K1) / 64 * q.w * kSplit, "%s s=%d: tall rows", tag, s);
+    CHECK(q.zero_from == (p.bordered ? p.Mp + q.K0 : INT64_MAX) && q.copy_from == q.zero_from,
+          "%s s=%d: border rows", tag, s);
+    // units: the ahead band has 2 wn units per tile row (a_done's target), the rest triangle
+    // two per tile; main and helper make up the whole enumeration
+    CHECK(q.na == 2 * q.wn * (q.T - q.wn) && q.nr == (q.T - q.wn) * (q.T - q.wn + 1),
+          "%s s=%d: unit counts", tag, s);
+    for (int trow = q.wn; q.wn > 0 && trow < q.T; ++trow) {
+      int cnt = 0;
+      for (int u = 0; u < q.na; ++u) cnt += q.wn + u / (2 * q.wn) == trow;
+      if (cnt != 2 * q.wn) CHECK(false, "%s s=%d: a_done row %d gets %d", tag, s, trow, cnt);
+    }
+    CHECK(q.hu >= 0 && q.hu <= q.nr / 2 && q.nr_main + q.hu == q.nr, "%s s=%d: helper share", tag, s);
+    if (s == 0 || s + 2 >= S || !p.helper) CHECK(q.hu == 0, "%s s=%d: helper where none", tag, s);
+    CHECK(q.lead == (s + 2 < S ? steps[s + 2].second : 0), "%s s=%d: lead", tag, s);
+    if (q.hu > 0)
+      CHECK(lead_rest_units(q.T, q.wn, q.lead, q.nr_main, q.nr) == 0,
+            "%s s=%d: lead tile in the helper's tail", tag, s);
+    if (s + 2 < S) {
+      // chain(s + 2) waits for the lead units of launch s: all of them run in the main launch
+      CHECK(q.T - q.wn >= q.lead, "%s s=%d: lead block outside the trailing matrix", tag, s);
+      int64_t ahead = 0;
+      for (int u = 0; u < q.na; ++u) ahead += q.wn + u / (2 * q.wn) < q.wn + q.lead;
+      const int64_t rest = lead_rest_units(q.T, q.wn, q.lead, 0, q.nr_main);
+      CHECK(rest == (int64_t)q.lead * (q.lead + 1), "%s s=%d: %lld lead rest units", tag, s,
+            (long long)rest);
+      CHECK((unsigned)(ahead + rest) == P.steps[s + 2].xtarget,
+            "%s s=%d: %lld lead units, chain(s + 2) waits for %u", tag, s,
+            (long long)(ahead + rest), P.steps[s + 2].xtarget);
+    }
+    if (s < 2) CHECK(q.xtarget == 0, "%s s=%d: xtarget without a wait", tag, s);
+    // grids: the padded segments
+    const int64_t tnext = s + 1 < S ? tall_grid(P.steps[s + 1].nt, kSplit) : 0;
+    CHECK(q.ugrid == pad8(q.na) + pad8(q.nr) && q.tgrid == tall_grid(q.nt, kSplit) &&
+              q.tgrid >= q.nt && q.tgrid % (8 * kSplit) == 0 && q.hgrid == pad8((int)q.hu),
+          "%s s=%d: segment grids", tag, s);
+    if (s + 1 < S)
+      CHECK(q.grid == pad8(q.na) + pad8(q.nr_main) + tnext, "%s s=%d: grid", tag, s);
+    else
+      CHECK(q.grid == (p.bordered ? q.ugrid : 0), "%s s=%d: last grid", tag, s);
+    marks += q.ovl_mark;
+    alg += q.chain_alg + q.helper_alg + q.step_alg;
+    CHECK(q.step_issued >= 0 && q.chain_issued >= q.chain_alg, "%s s=%d: issued flops", tag, s);
+  }
+  alg += P.steps[0].tall_alg;  // X_0's launch
+  CHECK(marks <= 1, "%s: %d overlap tail marks", tag, marks);
+  // The algorithmic flops of all launches are NOT checked against the closed form of the
+  // factorisation ((n + 1)^3 / 3, bordered Mp^3): the per-launch formulas are approximations
+  // whose sum depends on the step widths (16512 rows, MLL: 1.5051e12 against 1.5006e12, 0.3 %;
+  // bordered 4.64e12 .. 4.75e12 against 4.50e12). They are pinned by the golden plans below.
+  CHECK(std::isfinite(alg) && alg > 0, "%s: algorithmic flops", tag);
+}
+
+// The device-ordered launches of a plan, in issue order, one line each — what the kernels are
+// given, pointers as offsets into their buffers (-1: null), INT64_MAX as "max":
+//   E events / M bytes of flags cleared / T the overlap tail mark / R the buffers reserved
+//   C grid Kc w kd K0p xtarget Wk Bdp bar done xready                      chain_kernel
+//   L|H grid s0 kd T wn na nr nt tr0 tk0 tw lead rest_off zero_from copy_from pad_end
+//       px.p px.ld px.r0 Bd X a_done chain_done xready gen                 step / helper launch
+//   F class algorithmic issued                                 flops per kernel class, hexfloat
+static std::string s3_launch_text(const S3Plan& P, const S3Params& p) {
+  std::string out;
+  char buf[512];
+  auto num = [](int64_t v) { return v == INT64_MAX ? std::string("max") : std::to_string(v); };
+  double fl[3][2] = {{0, 0}, {0, 0}, {0, 0}};  // chains, step launches, helpers
+  // u: the step whose update the launch carries (NULL: none), t: whose tall units
+  auto step = [&](const char* k, int64_t grid, const S3Step* u, const S3Step* t, int nr,
+                  int64_t roff, bool device_ordered, double alg, double issued) {
+    if (grid == 0) return;
+    const bool h = k[0] == 'H';
+    const S3Step* l = u && u->lead && device_ordered ? &P.steps[(u - P.steps.data()) + 2] : nullptr;
+    std::snprintf(buf, sizeof(buf),
+                  "%s %lld %s %d %d %d %d %d %d %s %s %d %d %s %s %s %s %lld %lld %lld %lld %lld "
+                  "%lld %lld %lld %d\n",
+                  k, (long long)grid, num(u ? u->K1 : 0).c_str(), u ? u->kd : 0, u ? u->T : 0,
+                  u ? u->wn : 0, u && !h ? u->na : 0, nr, t && !h ? t->nt : 0,
+                  num(t ? t->tr0 : 0).c_str(), num(t ? t->tk0 : 0).c_str(), t ? t->tw : 0,
+                  l ? u->lead : 0, num(roff).c_str(), num(u ? u->zero_from : INT64_MAX).c_str(),
+                  num(t ? t->copy_from : INT64_MAX).c_str(), num(P.pad_end).c_str(),
+                  u ? (long long)u->x_off : -1LL, u ? (long long)u->kd : 0LL,
+                  u ? (long long)u->K1 : 0LL, t ? (long long)t->bd_off : -1LL,
+                  t ? (long long)t->x_off : -1LL, u && device_ordered ? (long long)u->f_adone : -1LL,
+                  t ? (long long)t->f_done : -1LL, l && !h ? (long long)l->f_xready : -1LL,
+                  (int)(u && u->gen));
+    out += buf;
+    fl[h ? 2 : 1][0] += alg;
+    fl[h ? 2 : 1][1] += issued;
+  };
+  auto chain = [&](int s) {
+    const S3Step& q = P.steps[s];
+    const S3Step* prev = s > 0 ? &P.steps[s - 1] : nullptr;
+    std::snprintf(buf, sizeof(buf), "C %d %lld %d %d %lld %u %lld %lld %lld %lld %lld\n", p.side_cus,
+                  (long long)q.K0, q.w, prev ? prev->kd : 0, prev ? (long long)prev->K0 : 0LL,
+                  q.xtarget, (long long)q.wk_off, prev ? (long long)prev->bd_off : -1LL,
+                  (long long)q.f_bar, (long long)q.f_done, s >= 2 ? (long long)q.f_xready : -1LL);
+    out += buf;
+    fl[0][0] += q.chain_alg;
+    fl[0][1] += q.chain_issued;
+  };
+  out += "E " + std::to_string(P.nevents) + "\nM " + std::to_string(P.flags_bytes) + "\n";
+  const S3Step* st = P.steps.data();
+  bool marked = false;
+  chain(0);
+  step("L", st[0].tgrid, nullptr, &st[0], 0, 0, true, st[0].tall_alg, st[0].tall_issued);
+  for (int s = 0; s + 1 < P.S; ++s) {
+    chain(s + 1);
+    if (st[s].ovl_mark) out += "T\n", marked = true;
+    step("L", st[s].grid, &st[s], &st[s + 1], st[s].nr_main, 0, true, st[s].step_alg,
+         st[s].step_issued);
+    if (st[s].hu > 0)
+      step("H", st[s].hgrid, &st[s], &st[s + 1], (int)st[s].hu, st[s].nr_main, true,
+           st[s].helper_alg, st[s].helper_issued);
+  }
+  if (p.bordered)
+    step("L", st[P.S - 1].ugrid, &st[P.S - 1], nullptr, st[P.S - 1].nr, 0, false,
+         st[P.S - 1].upd_alg, st[P.S - 1].upd_issued);
+  if (!marked) out += "T\n";
+  std::snprintf(buf, sizeof(buf), "R %zu %zu %zu %zu %zu %zu\n", P.wk_bytes, P.xbuf_bytes,
+                P.zvec_bytes, P.linv_bytes, P.xd_bytes, P.flags_bytes);
+  out += buf;
+  const int cls[3] = {4, 6, 12};  // lfm_internal.h K_POTRF, K_SYRK, K_SIDE_SYRK
+  for (int c = 0; c < 3; ++c) {
+    std::snprintf(buf, sizeof(buf), "F %d %a %a\n", cls[c], fl[c][0], fl[c][1]);
+    out += buf;
+  }
+  return out;
+}
+
+// The launches of the parent of the commit that introduced plan_s3 (its chol_factor_solve,
+// built with every HIP call stubbed out), device-ordered, profiler on, overlapped (so the tail
+// mark shows), 256 CUs of which 32 are the side stream's, default knobs:
+// the benchmark's N = 16384 MLL with the fused gram ...
+static const char kGolden16384[] = R"(E 177
+M 30856
+C 32 0 1 0 0 0 0 -1 7598 0 -1
+L 512 0 0 0 0 0 0 512 128 0 1 0 0 max max max -1 0 0 16384 0 -1 0 -1 0
+C 32 128 4 128 0 0 819200 16384 7599 1 -1
+L 18480 128 128 128 4 992 15500 1984 640 128 4 5 0 max max max 0 128 128 1081344 10567680 58 1 7658 1
+C 32 640 5 512 128 70 0 1081344 7600 2 7658
+L 16368 640 512 124 5 1190 12790 2380 1280 640 5 5 0 max max max 10567680 512 640 409600 0 188 2 7659 0
+H 1496 640 512 124 5 0 1490 0 1280 640 5 5 12790 max max max 10567680 512 640 409600 0 188 2 -1 0
+C 32 1280 5 640 640 80 819200 409600 7601 3 7659
+L 15128 1280 640 119 5 1140 11690 2280 1920 1280 5 5 0 max max max 0 640 1280 1228800 10567680 318 3 7660 0
+H 1424 1280 640 119 5 0 1420 0 1920 1280 5 5 11690 max max max 0 640 1280 1228800 10567680 318 3 -1 0
+C 32 1920 5 640 1280 80 0 1228800 7602 4 7660
+L 14008 1920 640 114 5 1090 10720 2180 2560 1920 5 5 0 max max max 10567680 640 1920 409600 0 448 4 7661 0
+H 1272 1920 640 114 5 0 1270 0 2560 1920 5 5 10720 max max max 10567680 640 1920 409600 0 448 4 -1 0
+C 32 2560 5 640 1920 80 819200 409600 7603 5 7661
+L 12920 2560 640 109 5 1040 9794 2080 3200 2560 5 5 0 max max max 0 640 2560 1228800 10567680 578 5 7662 0
+H 1128 2560 640 109 5 0 1126 0 3200 2560 5 5 9794 max max max 0 640 2560 1228800 10567680 578 5 -1 0
+C 32 3200 5 640 2560 80 0 1228800 7604 6 7662
+L 11888 3200 640 104 5 990 8912 1980 3840 3200 5 5 0 max max max 10567680 640 3200 409600 0 708 6 7663 0
+H 992 3200 640 104 5 0 988 0 3840 3200 5 5 8912 max max max 10567680 640 3200 409600 0 708 6 -1 0
+C 32 3840 5 640 3200 80 819200 409600 7605 7 7663
+L 10912 3840 640 99 5 940 8073 1880 4480 3840 5 5 0 max max max 0 640 3840 1228800 10567680 838 7 7664 0
+H 864 3840 640 99 5 0 857 0 4480 3840 5 5 8073 max max max 0 640 3840 1228800 10567680 838 7 -1 0
+C 32 4480 5 640 3840 80 0 1228800 7606 8 7664
+L 9968 4480 640 94 5 890 7278 1780 5120 4480 5 5 0 max max max 10567680 640 4480 409600 0 968 8 7665 0
+H 736 4480 640 94 5 0 732 0 5120 4480 5 5 7278 max max max 10567680 640 4480 409600 0 968 8 -1 0
+C 32 5120 5 640 4480 80 819200 409600 7607 9 7665
+L 9048 5120 640 89 5 840 6527 1680 5760 5120 5 5 0 max max max 0 640 5120 1228800 10567680 1098 9 7666 0
+H 616 5120 640 89 5 0 613 0 5760 5120 5 5 6527 max max max 0 640 5120 1228800 10567680 1098 9 -1 0
+C 32 5760 5 640 5120 80 0 1228800 7608 10 7666
+L 8200 5760 640 84 5 790 5819 1580 6400 5760 5 5 0 max max max 10567680 640 5760 409600 0 1228 10 7667 0
+H 504 5760 640 84 5 0 501 0 6400 5760 5 5 5819 max max max 10567680 640 5760 409600 0 1228 10 -1 0
+C 32 6400 5 640 5760 80 819200 409600 7609 11 7667
+L 7392 6400 640 79 5 740 5155 1480 7040 6400 5 5 0 max max max 0 640 6400 1228800 10567680 1358 11 7668 0
+H 400 6400 640 79 5 0 395 0 7040 6400 5 5 5155 max max max 0 640 6400 1228800 10567680 1358 11 -1 0
+C 32 7040 5 640 6400 80 0 1228800 7610 12 7668
+L 6920 7040 640 74 5 690 4830 1380 7680 7040 5 5 0 max max max 10567680 640 7040 409600 0 1488 12 7669 0
+C 32 7680 5 640 7040 80 819200 409600 7611 13 7669
+L 6080 7680 640 69 5 640 4160 1280 8320 7680 5 5 0 max max max 0 640 7680 1228800 10567680 1618 13 7670 0
+C 32 8320 5 640 7680 80 0 1228800 7612 14 7670
+L 5320 8320 640 64 5 590 3540 1180 8960 8320 5 5 0 max max max 10567680 640 8320 409600 0 1748 14 7671 0
+C 32 8960 5 640 8320 80 819200 409600 7613 15 7671
+L 4608 8960 640 59 5 540 2970 1080 9600 8960 5 5 0 max max max 0 640 8960 1228800 10567680 1878 15 7672 0
+C 32 9600 5 640 8960 80 0 1228800 7614 16 7672
+L 3944 9600 640 54 5 490 2450 980 10240 9600 5 5 0 max max max 10567680 640 9600 409600 0 2008 16 7673 0
+C 32 10240 5 640 9600 80 819200 409600 7615 17 7673
+L 3304 10240 640 49 5 440 1980 880 10880 10240 5 2 0 max max max 0 640 10240 1228800 10567680 2138 17 7674 0
+C 32 10880 2 640 10240 26 0 1228800 7616 18 7674
+T
+L 2312 10880 640 44 2 168 1806 336 11136 10880 2 2 0 max max max 10567680 640 10880 65536 0 2268 18 7675 0
+C 32 11136 2 256 10880 14 819200 65536 7617 19 7675
+L 2120 11136 256 42 2 160 1640 320 11392 11136 2 2 0 max max max 0 256 11136 884736 10567680 2398 19 7676 0
+C 32 11392 2 256 11136 14 0 884736 7618 20 7676
+L 1944 11392 256 40 2 152 1482 304 11648 11392 2 1 0 max max max 10567680 256 11392 65536 0 2528 20 7677 0
+C 32 11648 1 256 11392 6 819200 65536 7619 21 7677
+L 1648 11648 256 38 1 74 1406 148 11776 11648 1 1 0 max max max 0 256 11648 835584 10567680 2658 21 7678 0
+C 32 11776 1 128 11648 4 0 835584 7620 22 7678
+L 1552 11776 128 37 1 72 1332 144 11904 11776 1 1 0 max max max 10567680 128 11776 16384 0 2788 22 7679 0
+C 32 11904 1 128 11776 4 819200 16384 7621 23 7679
+L 1480 11904 128 36 1 70 1260 140 12032 11904 1 1 0 max max max 0 128 11904 835584 10567680 2918 23 7680 0
+C 32 12032 1 128 11904 4 0 835584 7622 24 7680
+L 1408 12032 128 35 1 68 1190 136 12160 12032 1 1 0 max max max 10567680 128 12032 16384 0 3048 24 7681 0
+C 32 12160 1 128 12032 4 819200 16384 7623 25 7681
+L 1344 12160 128 34 1 66 1122 132 12288 12160 1 1 0 max max max 0 128 12160 835584 10567680 3178 25 7682 0
+C 32 12288 1 128 12160 4 0 835584 7624 26 7682
+L 1248 12288 128 33 1 64 1056 128 12416 12288 1 1 0 max max max 10567680 128 12288 16384 0 3308 26 7683 0
+C 32 12416 1 128 12288 4 819200 16384 7625 27 7683
+L 1184 12416 128 32 1 62 992 124 12544 12416 1 1 0 max max max 0 128 12416 835584 10567680 3438 27 7684 0
+C 32 12544 1 128 12416 4 0 835584 7626 28 7684
+L 1128 12544 128 31 1 60 930 120 12672 12544 1 1 0 max max max 10567680 128 12544 16384 0 3568 28 7685 0
+C 32 12672 1 128 12544 4 819200 16384 7627 29 7685
+L 1064 12672 128 30 1 58 870 116 12800 12672 1 1 0 max max max 0 128 12672 835584 10567680 3698 29 7686 0
+C 32 12800 1 128 12672 4 0 835584 7628 30 7686
+L 984 12800 128 29 1 56 812 112 12928 12800 1 1 0 max max max 10567680 128 12800 16384 0 3828 30 7687 0
+C 32 12928 1 128 12800 4 819200 16384 7629 31 7687
+L 928 12928 128 28 1 54 756 108 13056 12928 1 1 0 max max max 0 128 12928 835584 10567680 3958 31 7688 0
+C 32 13056 1 128 12928 4 0 835584 7630 32 7688
+L 872 13056 128 27 1 52 702 104 13184 13056 1 1 0 max max max 10567680 128 13056 16384 0 4088 32 7689 0
+C 32 13184 1 128 13056 4 819200 16384 7631 33 7689
+L 824 13184 128 26 1 50 650 100 13312 13184 1 1 0 max max max 0 128 13184 835584 10567680 4218 33 7690 0
+C 32 13312 1 128 13184 4 0 835584 7632 34 7690
+L 744 13312 128 25 1 48 600 96 13440 13312 1 1 0 max max max 10567680 128 13312 16384 0 4348 34 7691 0
+C 32 13440 1 128 13312 4 819200 16384 7633 35 7691
+L 696 13440 128 24 1 46 552 92 13568 13440 1 1 0 max max max 0 128 13440 835584 10567680 4478 35 7692 0
+C 32 13568 1 128 13440 4 0 835584 7634 36 7692
+L 656 13568 128 23 1 44 506 88 13696 13568 1 1 0 max max max 10567680 128 13568 16384 0 4608 36 7693 0
+C 32 13696 1 128 13568 4 819200 16384 7635 37 7693
+L 608 13696 128 22 1 42 462 84 13824 13696 1 1 0 max max max 0 128 13696 835584 10567680 4738 37 7694 0
+C 32 13824 1 128 13696 4 0 835584 7636 38 7694
+L 544 13824 128 21 1 40 420 80 13952 13824 1 1 0 max max max 10567680 128 13824 16384 0 4868 38 7695 0
+C 32 13952 1 128 13824 4 819200 16384 7637 39 7695
+L 504 13952 128 20 1 38 380 76 14080 13952 1 1 0 max max max 0 128 13952 835584 10567680 4998 39 7696 0
+C 32 14080 1 128 13952 4 0 835584 7638 40 7696
+L 464 14080 128 19 1 36 342 72 14208 14080 1 1 0 max max max 10567680 128 14080 16384 0 5128 40 7697 0
+C 32 14208 1 128 14080 4 819200 16384 7639 41 7697
+L 432 14208 128 18 1 34 306 68 14336 14208 1 1 0 max max max 0 128 14208 835584 10567680 5258 41 7698 0
+C 32 14336 1 128 14208 4 0 835584 7640 42 7698
+L 368 14336 128 17 1 32 272 64 14464 14336 1 1 0 max max max 10567680 128 14336 16384 0 5388 42 7699 0
+C 32 14464 1 128 14336 4 819200 16384 7641 43 7699
+L 336 14464 128 16 1 30 240 60 14592 14464 1 1 0 max max max 0 128 14464 835584 10567680 5518 43 7700 0
+C 32 14592 1 128 14464 4 0 835584 7642 44 7700
+L 312 14592 128 15 1 28 210 56 14720 14592 1 1 0 max max max 10567680 128 14592 16384 0 5648 44 7701 0
+C 32 14720 1 128 14592 4 819200 16384 7643 45 7701
+L 280 14720 128 14 1 26 182 52 14848 14720 1 1 0 max max max 0 128 14720 835584 10567680 5778 45 7702 0
+C 32 14848 1 128 14720 4 0 835584 7644 46 7702
+L 232 14848 128 13 1 24 156 48 14976 14848 1 1 0 max max max 10567680 128 14848 16384 0 5908 46 7703 0
+C 32 14976 1 128 14848 4 819200 16384 7645 47 7703
+L 208 14976 128 12 1 22 132 44 15104 14976 1 1 0 max max max 0 128 14976 835584 10567680 6038 47 7704 0
+C 32 15104 1 128 14976 4 0 835584 7646 48 7704
+L 184 15104 128 11 1 20 110 40 15232 15104 1 1 0 max max max 10567680 128 15104 16384 0 6168 48 7705 0
+C 32 15232 1 128 15104 4 819200 16384 7647 49 7705
+L 168 15232 128 10 1 18 90 36 15360 15232 1 1 0 max max max 0 128 15232 835584 10567680 6298 49 7706 0
+C 32 15360 1 128 15232 4 0 835584 7648 50 7706
+L 120 15360 128 9 1 16 72 32 15488 15360 1 1 0 max max max 10567680 128 15360 16384 0 6428 50 7707 0
+C 32 15488 1 128 15360 4 819200 16384 7649 51 7707
+L 104 15488 128 8 1 14 56 28 15616 15488 1 1 0 max max max 0 128 15488 835584 10567680 6558 51 7708 0
+C 32 15616 1 128 15488 4 0 835584 7650 52 7708
+L 96 15616 128 7 1 12 42 24 15744 15616 1 1 0 max max max 10567680 128 15616 16384 0 6688 52 7709 0
+C 32 15744 1 128 15616 4 819200 16384 7651 53 7709
+L 80 15744 128 6 1 10 30 20 15872 15744 1 1 0 max max max 0 128 15744 835584 10567680 6818 53 7710 0
+C 32 15872 1 128 15744 4 0 835584 7652 54 7710
+L 48 15872 128 5 1 8 20 16 16000 15872 1 1 0 max max max 10567680 128 15872 16384 0 6948 54 7711 0
+C 32 16000 1 128 15872 4 819200 16384 7653 55 7711
+L 40 16000 128 4 1 6 12 12 16128 16000 1 1 0 max max max 0 128 16000 835584 10567680 7078 55 7712 0
+C 32 16128 1 128 16000 4 0 835584 7654 56 7712
+L 32 16128 128 3 1 4 6 8 16256 16128 1 1 0 max max max 10567680 128 16128 16384 0 7208 56 7713 0
+C 32 16256 1 128 16128 4 819200 16384 7655 57 7713
+L 32 16256 128 2 1 2 2 4 16384 16256 1 0 0 max max max 0 128 16256 835584 10567680 7338 57 -1 0
+R 13107200 169082880 132096 131072 3276800 30856
+F 4 0x1.2ea38aaaaaa9ep+33 0x1.1a2d555555561p+34
+F 6 0x1.42658b8fp+40 0x1.4d838p+40
+F 12 0x1.1ac6871p+36 0x1.633cp+36
+)";
+// ... N = 2560 with LFM_W4_MIN=1024, MLL (fused gram) ...
+static const char kGolden2560[] = R"(E 30
+M 900
+C 32 0 1 0 0 0 0 -1 207 0 -1
+L 80 0 0 0 0 0 0 80 128 0 1 0 0 max max max -1 0 0 16384 0 -1 0 -1 0
+C 32 128 4 128 0 0 819200 16384 208 1 -1
+L 656 128 128 20 4 128 272 256 640 128 4 5 0 max max max 0 128 128 1081344 1720320 9 1 218 1
+C 32 640 5 512 128 70 0 1081344 209 2 218
+T
+L 472 640 512 16 5 110 132 220 1280 640 5 5 0 max max max 1720320 512 640 409600 0 31 2 219 0
+C 32 1280 5 640 640 80 819200 409600 210 3 219
+L 240 1280 640 11 5 60 42 120 1920 1280 5 1 0 max max max 0 640 1280 1228800 1720320 53 3 220 0
+C 32 1920 1 640 1280 12 0 1228800 211 4 220
+L 80 1920 640 6 1 10 30 20 2048 1920 1 1 0 max max max 1720320 640 1920 16384 0 75 4 221 0
+C 32 2048 1 128 1920 4 819200 16384 212 5 221
+L 48 2048 128 5 1 8 20 16 2176 2048 1 1 0 max max max 0 128 2048 835584 1720320 97 5 222 0
+C 32 2176 1 128 2048 4 0 835584 213 6 222
+L 40 2176 128 4 1 6 12 12 2304 2176 1 1 0 max max max 1720320 128 2176 16384 0 119 6 223 0
+C 32 2304 1 128 2176 4 819200 16384 214 7 223
+L 32 2304 128 3 1 4 6 8 2432 2304 1 1 0 max max max 0 128 2304 835584 1720320 141 7 224 0
+C 32 2432 1 128 2304 4 0 835584 215 8 224
+L 32 2432 128 2 1 2 2 4 2560 2432 1 0 0 max max max 1720320 128 2432 16384 0 163 8 -1 0
+R 13107200 27525120 21504 131072 3276800 900
+F 4 0x1.298f555555557p+30 0x1.202aaaaaaaaa9p+31
+F 6 0x1.213e8p+32 0x1.7bcp+32
+F 12 0x0p+0 0x0p+0
+)";
+// ... and the same size bordered (the gradient's inverse)
+static const char kGolden2560b[] = R"(E 21
+M 600
+C 32 0 1 0 0 0 0 -1 138 0 -1
+L 96 0 0 0 0 0 0 84 128 0 1 0 0 max 2688 2561 -1 0 0 16384 0 -1 0 -1 0
+C 32 128 4 128 0 0 524288 16384 139 1 -1
+L 784 128 128 21 4 136 306 336 640 128 4 4 0 2688 2816 2561 0 128 128 786432 1376256 6 1 146 0
+C 32 640 4 512 128 52 0 786432 140 2 146
+T
+L 784 640 512 21 4 136 306 336 1152 640 4 4 0 2816 3328 2561 1376256 512 640 262144 0 28 2 147 0
+C 32 1152 4 512 640 52 524288 262144 141 3 147
+L 784 1152 512 21 4 136 306 336 1664 1152 4 4 0 3328 3840 2561 0 512 1152 786432 1376256 50 3 148 0
+C 32 1664 4 512 1152 52 0 786432 142 4 148
+L 784 1664 512 21 4 136 306 336 2176 1664 4 4 0 3840 4352 2561 1376256 512 1664 262144 0 72 4 149 0
+C 32 2176 4 512 1664 52 524288 262144 143 5 149
+L 784 2176 512 21 4 136 306 336 2688 2176 4 0 0 4352 4864 2561 0 512 2176 786432 1376256 94 5 -1 0
+L 464 2688 512 21 0 0 462 0 0 0 0 0 0 4864 max 2561 1376256 512 2688 -1 -1 -1 -1 -1 0
+R 8388608 22020096 21504 131072 2097152 600
+F 4 0x1.3fc3fffffffffp+30 0x1.30fffffffffffp+31
+F 6 0x1.441f5p+34 0x1.678p+34
+F 12 0x0p+0 0x0p+0
+)";
+
+static void check_s3_golden() {
+  struct Case { int64_t n; bool bordered; int64_t w4min; bool fused; const char* want; };
+  const Case cases[] = {{16384, false, 6144, true, kGolden16384},
+                        {2560, false, 1024, true, kGolden2560},
+                        {2560, true, 1024, false, kGolden2560b}};
+  for (const Case& c : cases) {
+    const int64_t Mp = (c.n + 1 + 127) / 128 * 128;
+    const int64_t cols = c.bordered ? Mp / 128 : (c.n + 127) / 128;
+    const auto steps = plan_steps(cols, Mp, 128, c.bordered, true, c.bordered ? 4 : 5, c.w4min,
+                                  5120, 1);
+    S3Params p = s3_params(c.n, Mp, c.bordered, 32, 1, true);
+    p.fused = c.fused;
+    const std::string got = s3_launch_text(plan_s3(steps, p), p);
+    if (got != c.want) {
+      size_t i = 0;
+      while (i < got.size() && got[i] == c.want[i]) ++i;
+      const size_t b = got.rfind('\n', i) + 1;
+      CHECK(false, "golden plan n=%lld%s differs at byte %zu: got '%s'", (long long)c.n,
+            c.bordered ? " bordered" : "", i, got.substr(b, got.find('\n', i) - b).c_str());
+    }
+  }
+  std::printf("plan_s3: 3 golden plans reproduced\n");
+}
+
+// A kept plan is reused while its inputs hold and rebuilt when any of them changes
+static void check_s3_keep() {
+  const int64_t n = 2560, Mp = 2688;
+  const auto steps = plan_steps(20, Mp, 128, false, true, 5, 1024, 5120, 1);
+  const S3Params p = s3_params(n, Mp, false, 32, 1, false);
+  S3Plan kept;
+  CHECK(plan_s3_keep(kept, steps, p) && kept.S == (int)steps.size(), "first call builds");
+  const S3Step* data = kept.steps.data();
+  CHECK(!plan_s3_keep(kept, steps, p) && kept.steps.data() == data, "same inputs: reused");
+  // every field of the parameters, and the step list, invalidates
+  std::vector<S3Params> changed(15, p);
+  changed[0].n -= 1;
+  changed[1].Mp += 128;
+  changed[2].bordered = true;
+  changed[3].fused = true;
+  changed[4].prof = true;
+  changed[5].nb = 64;
+  changed[6].st = 64;
+  changed[7].tall_split = 1;
+  changed[8].supertile = 1;
+  changed[9].cus = 304;
+  changed[10].side_cus = 8;
+  changed[11].helper = 0;
+  changed[12].helper_tc = 701;
+  changed[13].helper_min = 1201;
+  changed[14].ovl_at = 1024;
+  for (size_t i = 0; i < changed.size(); ++i) {
+    CHECK(plan_s3_keep(kept, steps, changed[i]), "changed parameter %zu: not rebuilt", i);
+    CHECK(kept.params == changed[i] && plan_s3_keep(kept, steps, p), "back to the first inputs");
+  }
+  const auto steps2 = plan_steps(20, Mp, 128, false, true, 5, 6144, 5120, 1);
+  CHECK(steps2 != steps && plan_s3_keep(kept, steps2, p) && kept.step_list == steps2,
+        "changed step list: rebuilt");
+  CHECK(s3_launch_text(kept, p) == s3_launch_text(plan_s3(steps2, p), p), "kept plan = fresh plan");
+  std::printf("plan_s3: kept plan reused and invalidated\n");
+}
+
+static void check_s3_plans() {
+  int cases = 0;
+  const int64_t knobs[3][2] = {{6144, 5120}, {1024, 5120}, {(int64_t)1 << 30, 1024}};
+  for (int64_t nblk : {1, 2, 3, 5, 9, 17, 33, 65, 129, 130})
+    for (int64_t dn : {1, 128, 129})
+      for (bool bordered : {false, true})
+        for (int w0 : {1, 2})
+          for (const auto& kn : knobs)
+            for (int side_cus : {8, 32})
+              for (int helper : {0, 1}) {
+                const int64_t Mp = nblk * 128, n = Mp - dn;
+                if (n <= 0) continue;
+                const int64_t cols = bordered ? Mp / 128 : (n + 127) / 128;
+                const auto steps =
+                    plan_steps(cols, Mp, 128, bordered, true, bordered ? 4 : 5, kn[0], kn[1], w0);
+                // the helpers' algorithmic flops (a loop over their units' rows) on a subset
+                const S3Params p =
+                    s3_params(n, Mp, bordered, side_cus, helper, w0 == 1 && side_cus == 32);
+                char tag[128];
+                std::snprintf(tag, sizeof(tag), "n=%lld Mp=%lld %s w0=%d w4min=%lld side=%d helper=%d",
+                              (long long)n, (long long)Mp, bordered ? "bordered" : "mll", w0,
+                              (long long)kn[0], side_cus, helper);
+                check_s3_plan(steps, p, plan_s3(steps, p), tag);
+                ++cases;
+              }
+  std::printf("plan_s3: %d plans\n", cases);
 }
 
 static void check_oracle() {
@@ -370,6 +868,9 @@ int main() {
   check_helper_clamp();
   check_detect_grid();
   check_plan();
+  check_s3_plans();
+  check_s3_golden();
+  check_s3_keep();
   check_oracle();
   if (failures) {
     std::fprintf(stderr, "%d check(s) failed\n", failures);

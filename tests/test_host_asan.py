@@ -1,8 +1,12 @@
 """Host code under AddressSanitizer + UBSan: liblfm's host-only logic
 (dis_project_amd/csrc/lfm_host.cpp: x-layout detection, the factorisation's step plan, the
 host mirror of the trailing update's unit enumeration, the side-CU helper's sizing and lead
-clamp, the device tenancy lock: mutual exclusion, shared admission, cross-process waits and the
-turnstile) and the C++ oracle (oracle/lfm_cpu.cpp), built by tests/native/Makefile and run by
+clamp, schedule 3's launch plan (plan_s3, over 1344 shapes: the flag array's four regions and
+every step's slots in them, workspace / X-buffer / matrix bounds, the lead units of each launch
+counted by enumeration against the target its chain waits for, a_done's target, the helper's
+share and its lead-free tail, the grids, the overlap mark; and three golden plans, the launches
+the library issued before the plan existed, flops included), the device tenancy lock: mutual
+exclusion, shared admission, cross-process waits and the turnstile) and the C++ oracle (oracle/lfm_cpu.cpp), built by tests/native/Makefile and run by
 tests/native/host_check.cpp. CPU only."""
 
 import os
