@@ -7,14 +7,6 @@
 
 #include "lfm_internal.h"
 
-namespace lfm {
-// what a launch over small problems is sized by: the largest n and num_genes, and the largest
-// small_grid_extra of the problems on the grid path (doubles; 0: none)
-struct SmallDims {
-  int maxn = 1, maxg = 1, gridtab = 0;
-};
-}  // namespace lfm
-
 // A batch of small problems registered once (the C5 ablation farm, notebook.py:33-75): x / y
 // and the problem table live in HBM; the packed hyperparameters, the results and the status
 // words live in one pinned host buffer the kernel reads and writes directly, so an evaluation is
@@ -23,23 +15,23 @@ struct lfm_batch {
   uint64_t id = 0;  // unique per process (never reused): keys the farm's captured graph
   int device = 0;
   int64_t nprob = 0, nhyp = 0;
-  lfm::SmallDims dims;
+  std::vector<lfm::SmallShape> shapes;  // what the launch plans are built from
+  lfm::SmallDims dims;                  // small_dims(shapes): sizes the MLL launch
   char* dmem = nullptr;     // device: x / y (+ grid times / block genes) of every problem, then
                             // the SmallProb table
   lfm::SmallProb* dprobs = nullptr;
-  double* hbuf = nullptr;   // pinned host, coherent: hyp [nhyp] | out [nprob] | status [nprob]
-                            // (int); the kernel reads / writes it directly and the host spins on
+  double* hbuf = nullptr;   // pinned host, coherent, laid out by `lay` (hyp | out | status |
+                            // grad); the kernel reads / writes it directly and the host spins on
                             // the status words, so it must not be cached on the device side
+  lfm::BatchLayout lay;
   hipEvent_t done = nullptr;  // recorded after every launch on the batch: destroy waits on it
   // small enough for the kernel arguments (LFM_SMALL_KERNARG, default on; read at creation)
   bool use_args = false;
   std::vector<lfm::SmallProb> table;  // host copy of the problem table
   std::vector<int> dsb_off, sc_off;  // each problem's offsets in the packed hyperparameters
   int* doffs = nullptr;              // device: dsb_off then sc_off (the gradient / fit kernels)
-  double* hgrad = nullptr;           // pinned (in hbuf): the gradient, packed as hyp [nhyp]
   size_t lds_grad = 0, lds_fit = 0;  // the gradient / fit launches' LDS (0: not possible)
-  // the fit's device buffers (grown on demand): raw mu nu [3 nhyp] | bias [2 nsteps] |
-  // history [nsteps nprob] | status [nprob]
+  // the fit's device buffer (grown on demand; a call's FitLayout)
   char* fitbuf = nullptr;
   size_t fit_bytes = 0;
 };
@@ -114,7 +106,7 @@ int batch_status(lfm_ctx* ctx, const int* words, int64_t np, int* status,
 
 // the status words of the batch's pinned buffer
 inline int* batch_words(const lfm_batch* batch) {
-  return reinterpret_cast<int*>(batch->hbuf + batch->nhyp + batch->nprob);
+  return reinterpret_cast<int*>(batch->hbuf + batch->lay.status);
 }
 // before a launch: a problem's status word is written last
 inline void batch_reset(const lfm_batch* batch) {

@@ -15,59 +15,47 @@ namespace lfm {
 
 namespace {
 
-// host: detect the grid layout of problem p and, when its tables fit the kernel's budget, put
-// its times and block genes at hd (device address dd) and fill sp's grid fields; returns the
-// doubles used (at most small_grid_doubles(n))
-int64_t small_grid_pack(const double* x, int64_t n, int64_t G, SmallProb& sp, double* hd,
-                        const double* dd) {
-  sp.T = 0;
-  const GridLayout lay = detect_grid(x, n, G);
-  if (!lay.ok || tables_doubles((int)G, lay.T) > (size_t)SMALL_GRID_TAB_MAX) return 0;
-  const int64_t T = lay.T, nblk = lay.nblk;
-  std::memcpy(hd, lay.times.data(), T * 8);
-  std::memcpy(hd + T, lay.block_gene.data(), nblk * sizeof(int));
-  sp.T = (int)T;
-  sp.dt = lay.dt;
-  sp.times = dd;
-  sp.bg = reinterpret_cast<const int*>(dd + T);
-  return T + (nblk + 1) / 2;
+// The problems' shapes (what plan_small_* take), each with its grid layout detected into lays
+std::vector<SmallShape> small_shapes(int64_t np, const lfm_problem* probs, const int64_t* idx,
+                                     std::vector<GridLayout>& lays) {
+  std::vector<SmallShape> shapes((size_t)np);
+  lays.resize((size_t)np);
+  for (int64_t q = 0; q < np; ++q) {
+    const lfm_problem& p = probs[idx ? idx[q] : q];
+    lays[q] = detect_grid(p.x, p.n, p.hyp.num_genes);
+    shapes[q] = {(int)p.n, (int)p.hyp.num_genes, small_grid_T(lays[q], p.hyp.num_genes)};
+  }
+  return shapes;
 }
 
-// One small problem into the staging area hd (device address dd) from double `off` on, and its
-// table entry sp: x (3n), y (n), its hyperparameters D S B (3G) l obs_stddev jitter (3) when
-// dsb is NULL (else sp points at the caller's dsb / sc), then the grid times / block genes.
-// Returns the offset past it; dims follows the problems packed so far.
-size_t pack_small(const lfm_problem& p, double* hd, const double* dd, size_t off,
-                  const double* dsb, const double* sc, SmallProb& sp, SmallDims& dims) {
-  const int64_t n = p.n, G = p.hyp.num_genes;
-  std::memcpy(hd + off, p.x, 3 * n * 8);
-  sp.x = dd + off;
-  off += 3 * n;
-  std::memcpy(hd + off, p.y, n * 8);
-  sp.y = dd + off;
-  off += n;
+// One small problem into its slots `at` (plan_small_pack) of the staging area hd (device address
+// dd), and its table entry sp: x, y, its hyperparameters D S B, l obs_stddev jitter when dsb is
+// NULL (else sp points at the caller's dsb / sc), then a grid problem's times / block genes.
+void pack_small(const lfm_problem& p, const SmallShape& s, const GridLayout& lay,
+                const SmallPack::Slot& at, double* hd, const double* dd, const double* dsb,
+                const double* sc, SmallProb& sp) {
+  const int64_t n = s.n, G = s.G, T = s.T;
+  std::memcpy(hd + at.x, p.x, 3 * n * 8);
+  std::memcpy(hd + at.y, p.y, n * 8);
   if (!dsb) {
-    dsb = dd + off;
-    std::memcpy(hd + off, p.hyp.true_d, G * 8);
-    std::memcpy(hd + off + G, p.hyp.true_s, G * 8);
-    std::memcpy(hd + off + 2 * G, p.hyp.true_b, G * 8);
-    off += 3 * G;
-    sc = dd + off;
-    hd[off] = p.hyp.l;
-    hd[off + 1] = p.hyp.obs_stddev;
-    hd[off + 2] = p.hyp.jitter;
-    off += 3;
+    dsb = dd + at.dsb;
+    sc = dd + at.sc;
+    std::memcpy(hd + at.dsb, p.hyp.true_d, G * 8);
+    std::memcpy(hd + at.dsb + G, p.hyp.true_s, G * 8);
+    std::memcpy(hd + at.dsb + 2 * G, p.hyp.true_b, G * 8);
+    hd[at.sc] = p.hyp.l;
+    hd[at.sc + 1] = p.hyp.obs_stddev;
+    hd[at.sc + 2] = p.hyp.jitter;
   }
-  sp.dsb = dsb;
-  sp.sc = sc;
-  sp.n = (int)n;
-  sp.G = (int)G;
-  off += small_grid_pack(p.x, n, G, sp, hd + off, dd + off);
-  dims.maxn = std::max<int>(dims.maxn, (int)n);
-  dims.maxg = std::max<int>(dims.maxg, (int)G);
-  if (sp.T)
-    dims.gridtab = std::max<int>(dims.gridtab, (int)small_grid_extra((int)n, (int)G, sp.T));
-  return off;
+  sp = SmallProb{dd + at.x, dd + at.y, dsb, sc, s.n, s.G};
+  if (T) {
+    std::memcpy(hd + at.grid, lay.times.data(), T * 8);
+    std::memcpy(hd + at.grid + T, lay.block_gene.data(), lay.nblk * sizeof(int));
+    sp.T = s.T;
+    sp.dt = lay.dt;
+    sp.times = dd + at.grid;
+    sp.bg = reinterpret_cast<const int*>(dd + at.grid + T);
+  }
 }
 
 // the kernel-argument form of a resident batch: the problem table and the hyperparameters
@@ -119,14 +107,12 @@ int batch_wait(lfm_ctx* ctx, int64_t np, const int* hst, const double* vals, int
 
 int small_batch(lfm_ctx* ctx, int64_t np, const lfm_problem* probs, const int64_t* idx,
                 int negative, double* out, int* status) {
-  // packed device buffer: per problem x(3n) y(n) D S B (3G) l obs_stddev jitter (3) doubles;
-  // then the SmallProb array
-  size_t nd = 0;
-  for (int64_t q = 0; q < np; ++q) {
-    const lfm_problem& p = probs[idx[q]];
-    nd += 4 * (size_t)p.n + 3 * (size_t)p.hyp.num_genes + 3 + small_grid_doubles(p.n);
-  }
-  const size_t bytes_d = nd * 8;
+  // packed device buffer: the staging area (plan_small_pack, hyperparameters inline), then the
+  // SmallProb array
+  std::vector<GridLayout> lays;
+  const std::vector<SmallShape> shapes = small_shapes(np, probs, idx, lays);
+  const SmallPack pack = plan_small_pack(shapes, true);
+  const size_t bytes_d = pack.bound * 8;
   const size_t bytes_p = (size_t)np * sizeof(SmallProb);
   const size_t bytes_o = (size_t)np * (8 + 4);
   const size_t total = round_up(bytes_d, 16) + round_up(bytes_p, 16) + bytes_o + 64;
@@ -139,20 +125,15 @@ int small_batch(lfm_ctx* ctx, int64_t np, const lfm_problem* probs, const int64_
   double* hd = reinterpret_cast<double*>(hb);
   SmallProb* hp = reinterpret_cast<SmallProb*>(hb + round_up(bytes_d, 16));
   const double* dd = reinterpret_cast<const double*>(db);
-  SmallDims dims;
-  size_t off = 0;
-  for (int64_t q = 0; q < np; ++q) {
-    SmallProb sp;
-    off = pack_small(probs[idx[q]], hd, dd, off, nullptr, nullptr, sp, dims);
-    hp[q] = sp;
-  }
+  for (int64_t q = 0; q < np; ++q)
+    pack_small(probs[idx[q]], shapes[q], lays[q], pack.at[q], hd, dd, nullptr, nullptr, hp[q]);
   const size_t up = round_up(bytes_d, 16) + bytes_p;
   hipError_t e = hipMemcpyAsync(db, hb, up, hipMemcpyHostToDevice, ctx->stream);
   if (e != hipSuccess) return hip_fail(ctx, e, "upload small batch");
   double* d_out = reinterpret_cast<double*>(db + round_up(bytes_d, 16) + round_up(bytes_p, 16));
   int* d_st = reinterpret_cast<int*>(d_out + np);
   r = launch_small_batch(ctx, reinterpret_cast<const SmallProb*>(db + round_up(bytes_d, 16)),
-                         (int)np, dims.maxn, dims.maxg, dims.gridtab, negative, d_out, d_st);
+                         (int)np, plan_small_mll(small_dims(shapes)), negative, d_out, d_st);
   if (r) return r;
   double* h_out = reinterpret_cast<double*>(hb + round_up(bytes_d, 16) + round_up(bytes_p, 16));
   e = hipMemcpyAsync(h_out, d_out, np * 12, hipMemcpyDeviceToHost, ctx->stream);
@@ -170,7 +151,7 @@ int small_batch(lfm_ctx* ctx, int64_t np, const lfm_problem* probs, const int64_
 int batch_launch(lfm_ctx* ctx, lfm_batch* batch, const double* hyp, int negative, double* out) {
   if (int r = batch_prev_ok(ctx, batch)) return r;
   const int np = (int)batch->nprob;
-  const SmallDims& d = batch->dims;
+  const SmallMllPlan plan = plan_small_mll(batch->dims);
   int* hst = batch_words(batch);
   batch_reset(batch);
   int r;
@@ -181,10 +162,10 @@ int batch_launch(lfm_ctx* ctx, lfm_batch* batch, const double* hyp, int negative
     a.out = out;
     a.status = hst;
     a.negative = negative;
-    r = launch_small_args(ctx, a, np, d.maxn, d.maxg, d.gridtab);
+    r = launch_small_args(ctx, a, np, plan);
   } else {
     std::memcpy(batch->hbuf, hyp, (size_t)batch->nhyp * 8);
-    r = launch_small_batch(ctx, batch->dprobs, np, d.maxn, d.maxg, d.gridtab, negative, out, hst);
+    r = launch_small_batch(ctx, batch->dprobs, np, plan, negative, out, hst);
   }
   if (r) return r;
   hipEventRecord(batch->done, ctx->stream);
@@ -211,7 +192,7 @@ int lfm_batch_create(lfm_ctx* ctx, int64_t nprob, const lfm_problem* probs, lfm_
   if (!ctx) return LFM_E_ARG;
   if (!out || nprob < 1 || !probs) return set_err(ctx, LFM_E_ARG, "bad batch arguments");
   *out = nullptr;
-  int64_t nd = 0, nhyp = 0;
+  int64_t nhyp = 0;
   for (int64_t q = 0; q < nprob; ++q) {
     const lfm_problem& p = probs[q];
     int r = validate_x(ctx, p.x, p.n);
@@ -223,9 +204,13 @@ int lfm_batch_create(lfm_ctx* ctx, int64_t nprob, const lfm_problem* probs, lfm_
       return set_err(ctx, LFM_E_ARG, "lfm_batch: num_genes must be in [1, n]");
     r = check_mean_shape(ctx, p.n, &p.hyp);
     if (r) return r;
-    nd += 4 * p.n + small_grid_doubles(p.n);
     nhyp += 3 * p.hyp.num_genes + 3;
   }
+  // the hyperparameters stay in the pinned buffer (a call writes them there): not in the staging
+  std::vector<GridLayout> lays;
+  const std::vector<SmallShape> shapes = small_shapes(nprob, probs, nullptr, lays);
+  const SmallPack pack = plan_small_pack(shapes, false);
+  const size_t nd = pack.bound;
   DeviceGuard g(ctx->device);
   std::unique_ptr<lfm_batch> b(new lfm_batch);
   static std::atomic<uint64_t> next_id{0};
@@ -233,6 +218,7 @@ int lfm_batch_create(lfm_ctx* ctx, int64_t nprob, const lfm_problem* probs, lfm_
   b->device = ctx->device;
   b->nprob = nprob;
   b->nhyp = nhyp;
+  b->lay = batch_layout(nhyp, nprob);
   const size_t bytes_d = round_up(nd * 8, 16), bytes_p = round_up((size_t)nprob * sizeof(SmallProb), 16);
   const size_t bytes_o = 2 * (size_t)nprob * sizeof(int);
   hipError_t e = hipMalloc((void**)&b->dmem, bytes_d + bytes_p + bytes_o);
@@ -240,7 +226,7 @@ int lfm_batch_create(lfm_ctx* ctx, int64_t nprob, const lfm_problem* probs, lfm_
   // coherent (fine-grained): the kernel reads the hyperparameters a call has just written and
   // its result / status stores must reach the host's spin without a stream synchronise,
   // whatever HIP_HOST_COHERENT says
-  e = hipHostMalloc((void**)&b->hbuf, (size_t)(2 * nhyp + 2 * nprob) * 8, hipHostMallocCoherent);
+  e = hipHostMalloc((void**)&b->hbuf, b->lay.bytes, hipHostMallocCoherent);
   if (e == hipSuccess) e = hipEventCreateWithFlags(&b->done, hipEventDisableTiming);
   if (e != hipSuccess) {
     hipFree(b->dmem);
@@ -249,17 +235,15 @@ int lfm_batch_create(lfm_ctx* ctx, int64_t nprob, const lfm_problem* probs, lfm_
   }
   b->dprobs = reinterpret_cast<SmallProb*>(b->dmem + bytes_d);
   b->doffs = reinterpret_cast<int*>(b->dmem + bytes_d + bytes_p);
-  b->hgrad = b->hbuf + nhyp + 2 * nprob;
-  std::vector<double> hd((size_t)nd);
+  std::vector<double> hd(nd);
   std::vector<SmallProb> table((size_t)nprob);
   const double* dd = reinterpret_cast<const double*>(b->dmem);
-  size_t off = 0;
   int64_t hv = 0, hs = 0;
   const int64_t nvec = nhyp - 3 * nprob;  // the vectors first, then the scalars
+  const double* hhyp = b->hbuf;
   for (int64_t q = 0; q < nprob; ++q) {
-    // the hyperparameters stay in the pinned buffer: a call writes them there
-    off = pack_small(probs[q], hd.data(), dd, off, b->hbuf + hv, b->hbuf + nvec + hs, table[q],
-                     b->dims);
+    pack_small(probs[q], shapes[q], lays[q], pack.at[q], hd.data(), dd, hhyp + hv,
+               hhyp + nvec + hs, table[q]);
     b->dsb_off.push_back((int)hv);
     b->sc_off.push_back((int)(nvec + hs));
     hv += 3 * probs[q].hyp.num_genes;
@@ -268,17 +252,13 @@ int lfm_batch_create(lfm_ctx* ctx, int64_t nprob, const lfm_problem* probs, lfm_
   b->use_args = ctx->knobs.small_kernarg && nprob <= SMALL_ARG_PROBS &&
                 nhyp <= SMALL_ARG_HYP;
   b->table = table;
-  // the gradient / fit kernels: every problem's augmented matrix on one or two waves
-  // (n + 1 <= 128) and its LDS map within a CU's 160 KB
-  if (b->dims.maxn <= SMALL_GRAD_MAX) {
-    b->lds_grad = small_grad_lds(table.data(), (int)nprob, 0);
-    b->lds_fit = small_grad_lds(table.data(), (int)nprob, 1);
-    if (b->lds_grad > 160 * 1024) b->lds_grad = 0;
-    if (b->lds_fit > 160 * 1024) b->lds_fit = 0;
-  }
+  b->shapes = shapes;
+  b->dims = small_dims(shapes);
+  b->lds_grad = small_grad_lds(shapes, 0);
+  b->lds_fit = small_grad_lds(shapes, 1);
   std::vector<int> offs(b->dsb_off);
   offs.insert(offs.end(), b->sc_off.begin(), b->sc_off.end());
-  e = hipMemcpyAsync(b->dmem, hd.data(), (size_t)nd * 8, hipMemcpyHostToDevice, ctx->stream);
+  e = hipMemcpyAsync(b->dmem, hd.data(), nd * 8, hipMemcpyHostToDevice, ctx->stream);
   if (e == hipSuccess)
     e = hipMemcpyAsync(b->dprobs, table.data(), (size_t)nprob * sizeof(SmallProb),
                        hipMemcpyHostToDevice, ctx->stream);
@@ -324,7 +304,7 @@ int lfm_batch_mll_f64(lfm_ctx* ctx, lfm_batch* batch, const double* hyp, int neg
   if (batch->device != ctx->device) return set_err(ctx, LFM_E_ARG, "batch of another device");
   DeviceGuard g(ctx->device);
   const int64_t np = batch->nprob;
-  double* hres = batch->hbuf + batch->nhyp;
+  double* hres = batch->hbuf + batch->lay.out;
   mark_pending(hres, np);
   int r = batch_launch(ctx, batch, hyp, negative, hres);
   if (r) return r;
@@ -345,29 +325,30 @@ int lfm_batch_mll_grad_f64(lfm_ctx* ctx, lfm_batch* batch, const double* hyp, in
                                    "map within 160 KB of LDS; use lfm_mll_grad_f64");
   DeviceGuard g(ctx->device);
   const int64_t np = batch->nprob;
-  double* hres = batch->hbuf + batch->nhyp;
+  double* hres = batch->hbuf + batch->lay.out;
+  double* hgrad = batch->hbuf + batch->lay.grad;
   int* hst = batch_words(batch);
   if (int e = batch_prev_ok(ctx, batch)) return e;
   batch_reset(batch);
   mark_pending(hres, np);
-  mark_pending(batch->hgrad, batch->nhyp);
+  mark_pending(hgrad, batch->nhyp);
   int r;
   if (batch->use_args) {
     SmallArgs a;
     fill_small_args(batch, hyp, a);
     a.tabs = 1;
     r = launch_small_grad(ctx, &a, nullptr, nullptr, (int)np, batch->lds_grad, negative, hres,
-                          batch->hgrad, hst);
+                          hgrad, hst);
   } else {
     std::memcpy(batch->hbuf, hyp, (size_t)batch->nhyp * 8);
     r = launch_small_grad(ctx, nullptr, batch->dprobs, batch->doffs, (int)np, batch->lds_grad,
-                          negative, hres, batch->hgrad, hst);
+                          negative, hres, hgrad, hst);
   }
   if (r) return r;
   hipEventRecord(batch->done, ctx->stream);
-  r = batch_wait(ctx, np, hst, hres, np, batch->hgrad, batch->nhyp);
+  r = batch_wait(ctx, np, hst, hres, np, hgrad, batch->nhyp);
   if (r) return r;
-  std::memcpy(grad, batch->hgrad, (size_t)batch->nhyp * 8);
+  std::memcpy(grad, hgrad, (size_t)batch->nhyp * 8);
   std::memcpy(value, hres, (size_t)np * 8);
   return batch_status(ctx, hst, np, status);
 }
@@ -387,22 +368,19 @@ int lfm_batch_fit_f64(lfm_ctx* ctx, lfm_batch* batch, const lfm_adam* opt, int n
   DeviceGuard g(ctx->device);
   if (int e = batch_prev_ok(ctx, batch)) return e;
   const int64_t np = batch->nprob, nh = batch->nhyp;
-  const size_t b_par = 3 * (size_t)nh * 8, b_bias = 2 * (size_t)nsteps * 8;
-  const size_t b_hist = (size_t)nsteps * np * 8, b_st = (size_t)np * sizeof(int);
-  const size_t need = b_par + b_bias + b_hist + b_st;
-  if (batch->fit_bytes < need) {
+  const FitLayout L = fit_layout(nh, np, nsteps);
+  if (batch->fit_bytes < L.bytes) {
     hipStreamSynchronize(ctx->stream);
     if (batch->fitbuf) hipFree(batch->fitbuf);
     batch->fitbuf = nullptr;
     batch->fit_bytes = 0;
-    hipError_t e = hipMalloc((void**)&batch->fitbuf, need);
+    hipError_t e = hipMalloc((void**)&batch->fitbuf, L.bytes);
     if (e != hipSuccess) return hip_fail(ctx, e, "lfm_batch_fit_f64: device buffer");
-    batch->fit_bytes = need;
+    batch->fit_bytes = L.bytes;
   }
-  double* d_par = reinterpret_cast<double*>(batch->fitbuf);
-  double* d_bias = d_par + 3 * nh;
-  double* d_hist = d_bias + 2 * nsteps;
-  int* d_st = reinterpret_cast<int*>(d_hist + nsteps * np);
+  double* d_fit = reinterpret_cast<double*>(batch->fitbuf);  // raw first
+  const size_t b_par = L.bias * 8, b_bias = (L.hist - L.bias) * 8;
+  const size_t b_hist = (L.status - L.hist) * 8, b_st = (size_t)np * sizeof(int);
   // optax's bias corrections 1 - b^count, count = step0 + s + 1, with the host's pow (the
   // restatement's numbers: dis_project_amd/trainer.py adam)
   std::vector<double> bias((size_t)2 * nsteps), par((size_t)3 * nh);
@@ -412,22 +390,22 @@ int lfm_batch_fit_f64(lfm_ctx* ctx, lfm_batch* batch, const lfm_adam* opt, int n
     bias[2 * s + 1] = 1.0 - std::pow(opt->b2, count);
   }
   std::memcpy(par.data(), raw, nh * 8);
-  std::memcpy(par.data() + nh, mu, nh * 8);
-  std::memcpy(par.data() + 2 * nh, nu, nh * 8);
-  hipError_t e = hipMemcpyAsync(d_par, par.data(), b_par, hipMemcpyHostToDevice, ctx->stream);
+  std::memcpy(par.data() + L.mu, mu, nh * 8);
+  std::memcpy(par.data() + L.nu, nu, nh * 8);
+  hipError_t e = hipMemcpyAsync(d_fit, par.data(), b_par, hipMemcpyHostToDevice, ctx->stream);
   if (e == hipSuccess)
-    e = hipMemcpyAsync(d_bias, bias.data(), b_bias, hipMemcpyHostToDevice, ctx->stream);
+    e = hipMemcpyAsync(d_fit + L.bias, bias.data(), b_bias, hipMemcpyHostToDevice, ctx->stream);
   if (e != hipSuccess) return hip_fail(ctx, e, "lfm_batch_fit_f64: upload");
   SmallFitLaunch f{};
   f.probs = batch->dprobs;
   f.offs = batch->doffs;
   f.nprob = (int)np;
-  f.raw = d_par;
-  f.mu = d_par + nh;
-  f.nu = d_par + 2 * nh;
-  f.history = d_hist;
-  f.bias = d_bias;
-  f.status = d_st;
+  f.raw = d_fit;
+  f.mu = d_fit + L.mu;
+  f.nu = d_fit + L.nu;
+  f.history = d_fit + L.hist;
+  f.bias = d_fit + L.bias;
+  f.status = reinterpret_cast<int*>(d_fit + L.status);
   f.lr = opt->learning_rate;
   f.b1 = opt->b1;
   f.b2 = opt->b2;
@@ -442,18 +420,18 @@ int lfm_batch_fit_f64(lfm_ctx* ctx, lfm_batch* batch, const lfm_adam* opt, int n
   if (r) return r;
   hipEventRecord(batch->done, ctx->stream);
   std::vector<int> st((size_t)np);
-  e = hipMemcpyAsync(par.data(), d_par, b_par, hipMemcpyDeviceToHost, ctx->stream);
+  e = hipMemcpyAsync(par.data(), d_fit, b_par, hipMemcpyDeviceToHost, ctx->stream);
   if (e == hipSuccess)
-    e = hipMemcpyAsync(history, d_hist, b_hist, hipMemcpyDeviceToHost, ctx->stream);
+    e = hipMemcpyAsync(history, f.history, b_hist, hipMemcpyDeviceToHost, ctx->stream);
   if (e == hipSuccess)
-    e = hipMemcpyAsync(st.data(), d_st, b_st, hipMemcpyDeviceToHost, ctx->stream);
+    e = hipMemcpyAsync(st.data(), f.status, b_st, hipMemcpyDeviceToHost, ctx->stream);
   if (e != hipSuccess) return hip_fail(ctx, e, "lfm_batch_fit_f64: download");
   r = finish(ctx);
   if (r) return r;
   // the packed layout's jitter slots pass through unchanged (a static field, model.py:64)
   std::memcpy(raw, par.data(), nh * 8);
-  std::memcpy(mu, par.data() + nh, nh * 8);
-  std::memcpy(nu, par.data() + 2 * nh, nh * 8);
+  std::memcpy(mu, par.data() + L.mu, nh * 8);
+  std::memcpy(nu, par.data() + L.nu, nh * 8);
   return batch_status(ctx, st.data(), np, status,
                       "Cholesky failed during the fit of a batch problem (its loss "
                       "and parameters are NaN from that step on, as JAX's)",
@@ -473,85 +451,60 @@ int lfm_batch_posterior_f64(lfm_ctx* ctx, lfm_batch* batch, const double* hyp,
   if (batch->dims.maxn > SMALL_GRAD_MAX || np > INT_MAX / 4)
     return set_err(ctx, LFM_E_ARG, "lfm_batch_posterior_f64: every problem needs n <= 127; use "
                                    "lfm_posterior_f64");
-  // per problem: its offsets in the packed arrays; one pass of the kernel covers `unit` test
-  // columns (64, or 256 when 64 would make more than 4096 workgroups)
-  std::vector<PostProb> pp((size_t)np);
-  int64_t sm = 0, sn = 0, sv = 0, sc = 0, ntiles = 0, wg64 = 0;
-  for (int64_t p = 0; p < np; ++p) {
-    const SmallProb& sp = batch->table[p];
-    if (m[p] < 1 || m[p] % sp.G != 0 || m[p] > (1 << 20))
+  const PostPlan P = plan_small_post(batch->shapes, nh, m, diag_vec != nullptr, cov != nullptr);
+  switch (P.reject) {
+    case PostPlan::OK: break;
+    case PostPlan::BAD_M:
       return set_err(ctx, LFM_E_ARG, "lfm_batch_posterior_f64: m[p] must be a multiple of "
                                      "num_genes in [1, 2^20] (mean_function, model.py:145-149)");
-    if (!small_post_cols(sp.n, sp.G, sp.T))
+    case PostPlan::NO_FIT:
       return set_err(ctx, LFM_E_ARG, "lfm_batch_posterior_f64: a problem's LDS map is past 160 KB");
-    const int64_t tb = (m[p] + 15) / 16;
-    pp[p] = PostProb{sm, sv, sc, (int)m[p], (int)sn, (int)ntiles, 0};
-    sm += m[p];
-    sn += sp.n;
-    sv += cov ? sp.n * m[p] : 0;
-    sc += cov ? m[p] * m[p] : 0;
-    ntiles += cov ? tb * (tb + 1) / 2 : 0;
-    wg64 += (m[p] + 63) / 64;
-    if (sm > ((int64_t)1 << 28) || sc > ((int64_t)1 << 29) || ntiles > INT_MAX / 2)
+    case PostPlan::TOO_LARGE:
       return set_err(ctx, LFM_E_ARG, "lfm_batch_posterior_f64: test inputs too large");
   }
-  const int unit = wg64 <= 4096 ? 64 : 256;
-  int64_t nsplit = 1;
-  for (int64_t p = 0; p < np; ++p) {
-    const SmallProb& sp = batch->table[p];
-    const int u = std::min(unit, small_post_cols(sp.n, sp.G, sp.T));
-    nsplit = std::max(nsplit, (m[p] + u - 1) / u);
-  }
-  nsplit = std::min<int64_t>(nsplit, 1024);  // a workgroup takes every nsplit-th pass
   DeviceGuard g(ctx->device);
   DeviceTenancy tenancy(ctx, false);  // shared
   if (int e = batch_prev_ok(ctx, batch)) return e;
-  // inputs, staged in pinned memory and uploaded in one copy: hyp | diag_add | diag_vec | t |
-  // the problem table; then the outputs: mean | var | V | cov | status
-  const size_t n_in = (size_t)nh + np + (diag_vec ? sn : 0) + 3 * sm;
-  const size_t b_in = n_in * 8 + (size_t)np * sizeof(PostProb);
-  const size_t n_out = 2 * (size_t)sm + sv + sc;
-  const size_t b_all = b_in + n_out * 8 + (size_t)np * sizeof(int);
-  int r = ctx->hpin.reserve(ctx, std::max<size_t>(b_in, 64 * sizeof(double)));
+  int r = ctx->hpin.reserve(ctx, std::max<size_t>(P.in_bytes, 64 * sizeof(double)));
   if (r) return r;
-  r = ctx->xin.reserve(ctx, b_all);
+  r = ctx->xin.reserve(ctx, P.all_bytes);
   if (r) return r;
+  // the inputs, staged in pinned memory and uploaded in one copy
   double* hp = ctx->hpin;
   std::memcpy(hp, hyp, nh * 8);
-  std::memcpy(hp + nh, diag_add, np * 8);
-  if (diag_vec) std::memcpy(hp + nh + np, diag_vec, sn * 8);
-  std::memcpy(hp + nh + np + (diag_vec ? sn : 0), t, 3 * sm * 8);
-  std::memcpy(hp + n_in, pp.data(), (size_t)np * sizeof(PostProb));
-  double* d_in = ctx->xin;
-  hipError_t e = hipMemcpyAsync(d_in, hp, b_in, hipMemcpyHostToDevice, ctx->stream);
+  std::memcpy(hp + P.dadd, diag_add, np * 8);
+  if (diag_vec) std::memcpy(hp + P.dv, diag_vec, P.sn * 8);
+  std::memcpy(hp + P.t, t, 3 * P.sm * 8);
+  std::memcpy(hp + P.table, P.pp.data(), (size_t)np * sizeof(PostProb));
+  double* d = ctx->xin;
+  hipError_t e = hipMemcpyAsync(d, hp, P.in_bytes, hipMemcpyHostToDevice, ctx->stream);
   if (e != hipSuccess) return hip_fail(ctx, e, "lfm_batch_posterior_f64: upload");
   SmallPostLaunch f{};
   f.probs = batch->dprobs;
   f.offs = batch->doffs;
-  f.pp = reinterpret_cast<const PostProb*>(d_in + n_in);
+  f.pp = reinterpret_cast<const PostProb*>(d + P.table);
   f.nprob = (int)np;
-  f.nsplit = (int)nsplit;
-  f.unit = unit;
-  f.ntiles = (int)ntiles;
-  f.hyp = d_in;
-  f.dadd = d_in + nh;
-  f.dv = diag_vec ? d_in + nh + np : nullptr;
-  f.t = d_in + nh + np + (diag_vec ? sn : 0);
-  double* d_out = reinterpret_cast<double*>(reinterpret_cast<char*>(d_in) + b_in);
-  f.mean = d_out;
-  f.var = d_out + sm;  // always computed (the copy back is the caller's choice)
-  f.V = cov ? d_out + 2 * sm : nullptr;
-  f.cov = cov ? d_out + 2 * sm + sv : nullptr;
-  f.status = reinterpret_cast<int*>(d_out + n_out);
-  r = launch_small_post(ctx, f, small_post_lds(batch->table.data(), (int)np));
+  f.nsplit = P.nsplit;
+  f.unit = P.unit;
+  f.ntiles = P.ntiles;
+  f.hyp = d;
+  f.dadd = d + P.dadd;
+  f.dv = diag_vec ? d + P.dv : nullptr;
+  f.t = d + P.t;
+  f.mean = d + P.mean;
+  f.var = d + P.var;  // always computed (the copy back is the caller's choice)
+  f.V = cov ? d + P.V : nullptr;
+  f.cov = cov ? d + P.cov : nullptr;
+  f.status = reinterpret_cast<int*>(d + P.status);
+  r = launch_small_post(ctx, f, P.lds_bytes);
   if (r) return r;
   hipEventRecord(batch->done, ctx->stream);
   std::vector<int> st((size_t)np);
-  e = hipMemcpyAsync(mean, f.mean, sm * 8, hipMemcpyDeviceToHost, ctx->stream);
+  e = hipMemcpyAsync(mean, f.mean, P.sm * 8, hipMemcpyDeviceToHost, ctx->stream);
   if (e == hipSuccess && var)
-    e = hipMemcpyAsync(var, f.var, sm * 8, hipMemcpyDeviceToHost, ctx->stream);
+    e = hipMemcpyAsync(var, f.var, P.sm * 8, hipMemcpyDeviceToHost, ctx->stream);
   if (e == hipSuccess && cov)
-    e = hipMemcpyAsync(cov, f.cov, sc * 8, hipMemcpyDeviceToHost, ctx->stream);
+    e = hipMemcpyAsync(cov, f.cov, P.sc * 8, hipMemcpyDeviceToHost, ctx->stream);
   if (e == hipSuccess)
     e = hipMemcpyAsync(st.data(), f.status, np * sizeof(int), hipMemcpyDeviceToHost, ctx->stream);
   if (e != hipSuccess) return hip_fail(ctx, e, "lfm_batch_posterior_f64: download");

@@ -318,8 +318,8 @@ int farm_graph_build(lfm_ctx* ctx, lfm_batch* batch, int negative, int64_t slots
   if (slots > np)
     e = hipMemsetAsync(dsend + np, 0xFF, (size_t)(slots - np) * 8, ctx->stream);
   if (e == hipSuccess)
-    r = launch_small_batch(ctx, batch->dprobs, (int)np, batch->dims.maxn, batch->dims.maxg,
-                           batch->dims.gridtab, negative, dsend, batch_words(batch));
+    r = launch_small_batch(ctx, batch->dprobs, (int)np, plan_small_mll(batch->dims), negative,
+                           dsend, batch_words(batch));
   else
     r = hip_fail(ctx, e, "farm graph: padding");
   if (!r) r = farm_allgather(ctx, dsend, drecv, slots);  // the test instrument is captured too

@@ -36,10 +36,7 @@ namespace lfm {
 //   Cm[j][k]   = S_j S_k l sqrt(pi)/2 / (D_j + D_k)       G*G
 // kxx(j,tau; k,tau') = Cm[j][k] * ( Wt[k][d] - Xt[k][d] Pt[k][tau] + Wt[j][-d]
 //        - Xt[j][-d] Pt[j][tau'] - Et[k][tau'] Et[j][tau] (Qt[k][tau'] + Qt[j][tau]) ).
-size_t tables_doubles(int G, int T) {
-  const size_t W = 2 * (size_t)T - 1;
-  return 2 * (size_t)G * W + 3 * (size_t)G * T + (size_t)G * G;
-}
+// Their size: tables_doubles (lfm_small_plan.h, which budgets them in LDS).
 
 __global__ void tables_kernel(HypDev p, int T, double dt, const double* __restrict__ times,
                               double* __restrict__ tab, float* __restrict__ tab32) {

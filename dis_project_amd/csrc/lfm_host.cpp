@@ -292,6 +292,118 @@ bool plan_s3_keep(S3Plan& kept, const std::vector<std::pair<int64_t, int>>& step
   return true;
 }
 
+// ------------------------------------------------------------ the small-problem path
+SmallDims small_dims(const std::vector<SmallShape>& shapes) {
+  SmallDims d;
+  for (const SmallShape& s : shapes) {
+    d.maxn = std::max(d.maxn, s.n);
+    d.maxg = std::max(d.maxg, s.G);
+    if (s.T) d.gridtab = std::max(d.gridtab, (int)small_grid_extra(s.n, s.G, s.T));
+  }
+  return d;
+}
+
+SmallMllPlan plan_small_mll(const SmallDims& d) {
+  const int tabs = d.maxn + 1 <= 64;
+  return {(small_map(nullptr, d.maxn, d.maxg, 0, tabs, 0, 0, nullptr) + (size_t)d.gridtab) *
+              sizeof(double),
+          tabs};
+}
+
+size_t small_grad_lds(const std::vector<SmallShape>& shapes, int fit) {
+  size_t mx = 0;
+  for (const SmallShape& s : shapes) {
+    if (s.n > SMALL_GRAD_MAX) return 0;
+    mx = std::max(mx, small_map(nullptr, s.n, s.G, s.T, 1, 1, fit, nullptr));
+  }
+  return mx * sizeof(double) > SMALL_LDS_BYTES ? 0 : mx * sizeof(double);
+}
+
+SmallPack plan_small_pack(const std::vector<SmallShape>& shapes, bool hyp_inline) {
+  SmallPack P;
+  P.at.reserve(shapes.size());
+  size_t off = 0;
+  for (const SmallShape& s : shapes) {
+    const size_t n = (size_t)s.n, nh = hyp_inline ? 3 * (size_t)s.G + 3 : 0;
+    const size_t grid = off + 4 * n + nh;
+    P.at.push_back({off, off + 3 * n, off + 4 * n, grid - (nh ? 3 : 0), grid});
+    off = grid + (s.T ? (size_t)s.T + ((size_t)s.n / s.T + 1) / 2 : 0);
+    P.bound += 4 * n + nh + (size_t)small_grid_doubles(s.n);
+  }
+  return P;
+}
+
+BatchLayout batch_layout(int64_t nhyp, int64_t nprob) {
+  BatchLayout L;
+  L.out = (size_t)nhyp;
+  L.status = L.out + (size_t)nprob;
+  L.grad = L.status + (size_t)nprob;
+  L.bytes = (L.grad + (size_t)nhyp) * sizeof(double);
+  return L;
+}
+
+FitLayout fit_layout(int64_t nhyp, int64_t nprob, int64_t nsteps) {
+  FitLayout L;
+  L.mu = (size_t)nhyp;
+  L.nu = 2 * (size_t)nhyp;
+  L.bias = 3 * (size_t)nhyp;
+  L.hist = L.bias + 2 * (size_t)nsteps;
+  L.status = L.hist + (size_t)nsteps * nprob;
+  L.bytes = L.status * sizeof(double) + (size_t)nprob * sizeof(int);
+  return L;
+}
+
+PostPlan plan_small_post(const std::vector<SmallShape>& shapes, int64_t nhyp, const int64_t* m,
+                         bool has_dv, bool has_cov) {
+  auto rejected = [](PostPlan::Reject why) {
+    PostPlan R;
+    R.reject = why;
+    return R;
+  };
+  const size_t np = shapes.size();
+  PostPlan P;
+  P.pp.resize(np);
+  // nsplit for either unit: which one holds is known once every problem's passes are counted
+  int64_t ntiles = 0, wg64 = 0, split64 = 1, split256 = 1;
+  size_t lds = 0;
+  for (size_t p = 0; p < np; ++p) {
+    const SmallShape& s = shapes[p];
+    if (m[p] < 1 || m[p] % s.G != 0 || m[p] > (1 << 20)) return rejected(PostPlan::BAD_M);
+    const int cols = small_post_cols(s.n, s.G, s.T);
+    if (!cols) return rejected(PostPlan::NO_FIT);
+    const int64_t tb = (m[p] + 15) / 16;
+    P.pp[p] = PostProb{P.sm, P.sv, P.sc, (int)m[p], (int)P.sn, (int)ntiles, 0};
+    P.sm += m[p];
+    P.sn += s.n;
+    P.sv += has_cov ? s.n * m[p] : 0;
+    P.sc += has_cov ? m[p] * m[p] : 0;
+    ntiles += has_cov ? tb * (tb + 1) / 2 : 0;
+    wg64 += (m[p] + 63) / 64;
+    if (P.sm > ((int64_t)1 << 28) || P.sc > ((int64_t)1 << 29) || ntiles > INT_MAX / 2)
+      return rejected(PostPlan::TOO_LARGE);
+    const int u64 = std::min(64, cols);
+    split64 = std::max(split64, (m[p] + u64 - 1) / u64);
+    split256 = std::max(split256, (m[p] + cols - 1) / cols);
+    lds = std::max(lds, small_post_base(s.n, s.G, s.T) + (size_t)s.n * cols);
+  }
+  P.unit = wg64 <= 4096 ? 64 : 256;
+  P.nsplit = (int)std::min<int64_t>(P.unit == 64 ? split64 : split256, 1024);
+  P.ntiles = (int)ntiles;
+  P.lds_bytes = lds * sizeof(double);
+  P.dadd = (size_t)nhyp;
+  P.dv = P.dadd + np;
+  P.t = P.dv + (has_dv ? (size_t)P.sn : 0);
+  P.table = P.t + 3 * (size_t)P.sm;
+  P.in_bytes = P.table * sizeof(double) + np * sizeof(PostProb);
+  P.mean = P.in_bytes / sizeof(double);
+  P.var = P.mean + (size_t)P.sm;
+  P.V = P.var + (size_t)P.sm;
+  P.cov = P.V + (size_t)P.sv;
+  P.status = P.cov + (size_t)P.sc;
+  P.all_bytes = P.status * sizeof(double) + np * sizeof(int);
+  return P;
+}
+
 namespace {
 // flock, restarted when a signal interrupts the wait; 0 or the errno of the failure
 int flock_retry(int fd, int op) {

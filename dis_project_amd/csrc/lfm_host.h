@@ -1,7 +1,9 @@
 // lfm_host.h — host-only logic of liblfm: x-layout detection, the factorisation's step plan,
 // the host mirror of the trailing update's unit enumeration, the side-CU helper's sizing and
 // schedule 3's whole launch plan (plan_s3: every unit count, grid, buffer and flag offset,
-// device-counter target and profiling figure of a call, which lfm_chol_sched.hip only reads).
+// device-counter target and profiling figure of a call, which lfm_chol_sched.hip only reads);
+// with lfm_small_plan.h the small-problem path's LDS map, staging and buffer layouts and its
+// launch plans (plan_small_*, which lfm_small.hip and lfm_batch.hip only read).
 // Plain C++ (no HIP types), so lfm_host.cpp also builds into the host sanitizer check
 // (tests/native, `make -C tests/native asan`) with g++ -fsanitize=address,undefined.
 #pragma once
@@ -16,11 +18,7 @@
 #include <utility>
 #include <vector>
 
-#if defined(__HIPCC__)
-#define LFM_HD __host__ __device__
-#else
-#define LFM_HD
-#endif
+#include "lfm_small_plan.h"  // LFM_HD; the small-problem path's layout and plans
 
 namespace lfm {
 
@@ -55,6 +53,10 @@ struct GridLayout {
 };
 
 GridLayout detect_grid(const double* x, int64_t n, int64_t G);
+// SmallShape::T of a small problem with this layout: on the grid path when its tables fit
+inline int small_grid_T(const GridLayout& lay, int64_t G) {
+  return lay.ok && tables_doubles((int)G, lay.T) <= (size_t)SMALL_GRID_TAB_MAX ? lay.T : 0;
+}
 
 // Super-panel plan of a blocked factorisation over nblk block columns of width nb: (first
 // block column, width in block columns) per step. Width wbulk (the first bulk step 4) while

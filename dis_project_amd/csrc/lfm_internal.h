@@ -1,4 +1,6 @@
-// lfm_internal.h — shared declarations of the HIP implementation behind include/lfm.h.
+// lfm_internal.h — shared declarations of the HIP implementation behind include/lfm.h: the
+// context, the kernel units' launch wrappers and their argument structs. Every size, offset and
+// grid they are launched with comes from the plain-C++ plans of lfm_host.h / lfm_small_plan.h.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -262,13 +264,6 @@ struct SmallProb {
   const double* times = nullptr;  // [T]
   const int* bg = nullptr;        // [n / T] gene of each block
 };
-// doubles small_grid_pack (lfm_batch.hip) uses at most for a problem's times and block genes
-inline int64_t small_grid_doubles(int64_t n) { return n + (n + 1) / 2; }
-// largest per-problem grid table (doubles) in LDS: with n = 128 beside it the launch stays
-// within a CU's 160 KB (launch_small_batch)
-constexpr int SMALL_GRID_TAB_MAX = 2048;
-constexpr int SMALL_MAX = 128;  // largest n handled by small_mll_kernel
-constexpr int SMALL_GRAD_MAX = 127;  // largest n of the batched gradient / fit (two waves)
 
 // gram kernels (lfm_gram.hip)
 int launch_tables(lfm_ctx* ctx, const HypDev& h, const GridLayout& lay, const double* d_times,
@@ -309,7 +304,6 @@ enum CholMode { CHOL_MLL = 0, CHOL_INVERSE = 1, CHOL_SCHUR = 2 };
 int chol_factor_solve(lfm_ctx* ctx, double* A, int64_t lda, int64_t n, int64_t Mp, int negative,
                       double* d_out, int mode = CHOL_MLL, const GramGen* gen = nullptr);
 bool chol_fuses_gram(const lfm_ctx* ctx, int mode, const GridLayout& lay, int64_t n);
-size_t tables_doubles(int G, int T);
 
 // gradient kernels (lfm_grad.hip)
 int launch_border_init(lfm_ctx* ctx, double* A, int64_t lda, int64_t Mp);
@@ -332,40 +326,34 @@ struct SmallArgs {
   double* grad;  // small_grad_kernel_args: the gradient, packed as hyp
 };
 static_assert(sizeof(SmallArgs) <= 4096, "kernel argument block");
-// value and gradient of a batch of small problems (n <= SMALL_GRAD_MAX = 127; the launch's LDS
-// map within 160 KB): a = the kernel-argument form
-// (problem table and hyperparameters in the arguments) or NULL (d_probs, d_offs: the table and
-// each problem's offsets of its vectors [0, nprob) and scalars [nprob, 2 nprob) in the packed
-// layout, hyperparameters read through SmallProb::dsb / sc)
+// value and gradient of a batch of small problems (lds: small_grad_lds, non-zero): a = the
+// kernel-argument form (problem table and hyperparameters in the arguments) or NULL (d_probs,
+// d_offs: the table and each problem's offsets of its vectors [0, nprob) and scalars
+// [nprob, 2 nprob) in the packed layout, hyperparameters read through SmallProb::dsb / sc)
 int launch_small_grad(lfm_ctx* ctx, SmallArgs* a, const SmallProb* d_probs, const int* d_offs,
                       int nprob, size_t lds, int negative, double* out, double* grad, int* status);
-// LDS bytes of the gradient (fit = 0) or fit (fit = 1) launch over these problems (host table)
-size_t small_grad_lds(const SmallProb* probs, int nprob, int fit);
-// the fit kernel's launch: every problem's Adam steps on the device (lfm_small.hip FitArgs)
+// the fit kernel's arguments: every problem's Adam steps on the device (small_fit_kernel)
 struct SmallFitLaunch {
   const SmallProb* probs;
-  const int* offs;
+  const int* offs;  // [2 nprob]: each problem's offset of its vectors / scalars (packed layout)
   int nprob;
-  double *raw, *mu, *nu, *history;
-  const double* bias;
-  int* status;
+  double *raw, *mu, *nu;  // [nhyp] each, in / out
+  double* history;        // [nsteps][nprob]
+  const double* bias;     // [nsteps][2]
+  int* status;            // [nprob]: 1 + the first step whose factor failed, or 0
   double lr, b1, b2, eps, eps_root;
   int64_t step0, nsteps, spe;
   int fix, negative;
 };
 int launch_small_fit(lfm_ctx* ctx, const SmallFitLaunch& f, size_t lds);
-int launch_small_args(lfm_ctx* ctx, SmallArgs& a, int nprob, int maxn, int maxg, int gridtab);
-// The batched posterior (lfm_batch_posterior_f64; lfm_small.hip small_post_kernel). One entry
-// per problem: where its test inputs, outputs and workspace start in the call's packed arrays.
-struct PostProb {
-  int64_t t_off;    // rows of t / entries of mean and var before this problem's (sum of m)
-  int64_t v_off;    // doubles of V = L^{-1} K(x, t) before this problem's n x m block
-  int64_t cov_off;  // doubles of cov before this problem's m x m block (sum of m^2)
-  int m;            // test rows
-  int dv_off;       // entries of diag_vec before this problem's (sum of n)
-  int tile0;        // covariance launch: 16 x 16 lower-triangle tiles before this problem's
-  int pad;
-};
+// the MLL of a batch of small problems (plan: plan_small_mll of the batch's SmallDims), the
+// problem table and hyperparameters in the kernel arguments or in device memory
+int launch_small_args(lfm_ctx* ctx, SmallArgs& a, int nprob, const SmallMllPlan& plan);
+int launch_small_batch(lfm_ctx* ctx, const SmallProb* d_probs, int nprob, const SmallMllPlan& plan,
+                       int negative, double* d_out, int* d_status);
+void small_batch_attrs();  // the MLL kernels' LDS limit raised (before launches / capture)
+// The batched posterior's arguments (small_post_kernel, small_post_cov_kernel), filled from a
+// PostPlan
 struct SmallPostLaunch {
   const SmallProb* probs;  // the batch's table (x, y, the grid layout; dsb / sc unused)
   const int* offs;         // [2 nprob]: each problem's vectors / scalars in the packed hyp
@@ -379,17 +367,7 @@ struct SmallPostLaunch {
   double *mean, *var, *V, *cov;  // var or cov may be NULL (V: only with cov)
   int* status;             // [nprob]: 1 + the first failing pivot, or 0
 };
-// columns of the K(x, t) panel a problem's workgroup keeps in LDS beside its map (a power of two,
-// 16 ... 256; 0: the problem does not fit), and the launch's LDS bytes over these problems
-int small_post_cols(int n, int G, int T);
-size_t small_post_lds(const SmallProb* probs, int nprob);
 int launch_small_post(lfm_ctx* ctx, const SmallPostLaunch& f, size_t lds);
-void small_batch_attrs();  // the MLL kernels' 160 KB LDS attribute (before launches / capture)
-// gridtab: the largest small_grid_extra of the problems (doubles; 0: none on the grid path)
-// LDS doubles a grid-layout problem adds to its map: the gram tables, the times, the block genes
-size_t small_grid_extra(int n, int G, int T);
-int launch_small_batch(lfm_ctx* ctx, const SmallProb* d_probs, int nprob, int maxn, int maxg,
-                       int gridtab, int negative, double* d_out, int* d_status);
 
 // Path of the advisory lock file behind schedule 3's cross-process tenancy (lfm_ctx.hip;
 // empty if the device has no PCI bus id)

@@ -347,86 +347,8 @@ __device__ __forceinline__ void small_factor_regs2(const double* __restrict__ sm
   *bad_out = f.bad;
 }
 
-// LDS map of one problem (doubles from the dynamic shared memory base), shared by the MLL,
-// gradient and fit kernels:
-//   A      [M x ld]         Sigma's lower triangle and the residual row n (M = n + 1; ld the odd
-//                           one of n + 2, n + 3: a wave's accesses down a column, lane r at row r,
-//                           are then free of LDS bank conflicts)
-//   red    [16]             reductions
-//   hyp    [3G + 3]         D S B, l, obs_stddev, jitter (the constrained parameters)
-//   ktab   [3G + n + nG]    KxxTab's per-gene / per-row factors (tabs: n + 1 <= 64 in the launch)
-//   colbuf [128 / 512]      the factor's column buffer(s): one wave 128; two waves (n + 1 > 64)
-//                           two of 256 (rows, a zero tail, the next pivot in slot 255)
-//   xs, ys [3n], [n]
-//   gt     [2GW + 3GT + G^2] the grid layout's gram tables (grid problems, W = 2T - 1)
-//   tms, bgs [T], [n / T]    the grid layout's times and block genes (grid problems)
-// the gradient and the fit (GRAD) add, past this problem's gram tables:
-//   gg     [6GW + 8GT]      the grid layout's derivative tables (grad_table_entry)
-//   al, wd [128 each]       alpha = Sigma^{-1} r, diag(W)
-//   accw   [4][2G + 1]      the waves' partial sums of 1/2 tr(W dSigma / d{D, S, l})
-//   wb     [(n + 1) x ldw]  one wave: W's rows as the sweep leaves them (small_sweep_w)
-//   gout   [3G + 3]         the gradient in the packed layout (dD dS dB, dl, d obs_stddev, 0)
-// and the fit (FIT): raw, mu, nu [3G + 3 each] (the unconstrained parameters, Adam's moments).
-// (`spare` is never set or read: without the member the compiler allocates the gradient kernels'
-// registers differently, 22 AGPRs instead of 14, so it stays until that is measured)
-struct SmallMap {
-  double *A, *red, *hyp, *ktab, *colbuf, *xs, *ys, *gt;
-  double *gg, *al, *wd, *accw, *gout, *raw, *mu, *nu, *tms, *spare, *wb;
-  int* bgs;
-  int n, ld, G;
-};
-// the four-wave sweep's buffers (small_sweep4): per step parity a row buffer (256) and its
-// copy shifted by one (258), then per parity the crossing slots (128), then two wave sums
-constexpr int SWEEP4_LDS = 2 * 520 + 2 * 128 + 8;
-// the sweep's register width for n + 1 rows (one wave), and the row stride of its W buffer:
-// slot q of lane i's row lands at wb[i ldw + q - 1] (compile-time offsets, odd stride)
-__host__ __device__ constexpr int small_sweep_mr(int n) { return n + 1 <= 32 ? 32 : 64; }
-__host__ __device__ constexpr int small_wb_ld(int n) { return small_sweep_mr(n) | 1; }
-// doubles of the map (sm = nullptr: the size only)
-__host__ __device__ inline size_t small_map(double* sm, int n, int G, int T, int tabs, int grad,
-                                            int fit, SmallMap* m) {
-  size_t o = 0;
-  auto take = [&](size_t k) {
-    double* p = sm ? sm + o : nullptr;
-    o += k;
-    return p;
-  };
-  const size_t W = T > 0 ? 2 * (size_t)T - 1 : 0;
-  SmallMap q{};
-  q.n = n;
-  q.ld = (n + 2) | 1;
-  q.G = G;
-  q.A = take((size_t)(n + 1) * q.ld);
-  q.red = take(16);
-  q.hyp = take(3 * (size_t)G + 3);
-  q.ktab = take(tabs ? 3 * (size_t)G + n + (size_t)n * G : 0);
-  o = (o + 1) & ~(size_t)1;  // 16-B aligned: the sweep reads its row buffers 16 B at a time
-  // one wave: the factor's 128 or the sweep's two row buffers (2 x 64 and its copy shifted by
-  // one, 2 x 64 + 2); two waves: two 256-slot column buffers
-  q.colbuf = take(n + 1 > 64 ? (grad ? SWEEP4_LDS : 512) : 264);
-  q.xs = take(3 * (size_t)n);
-  q.ys = take((size_t)n);
-  q.gt = take(T > 0 ? 2 * (size_t)G * W + 3 * (size_t)G * T + (size_t)G * G : 0);
-  // the grid layout's times and block genes, staged with x and y (read every element / step)
-  q.tms = take(T > 0 ? (size_t)T : 0);
-  q.bgs = reinterpret_cast<int*>(take(T > 0 ? ((size_t)n / T + 1) / 2 + 1 : 0));
-  if (grad) {
-    q.gg = take(T > 0 ? 6 * (size_t)G * W + 8 * (size_t)G * T : 0);
-    q.al = take(128);
-    q.wd = take(128);
-    // one wave (n + 1 <= 64): W's rows as the sweep leaves them, row stride ldw (small_wb_ld)
-    q.wb = take(n + 1 <= 64 ? (size_t)(n + 1) * small_wb_ld(n) : 0);
-    q.accw = take(4 * (2 * (size_t)G + 1));
-    q.gout = take(3 * (size_t)G + 3);
-  }
-  if (fit) {
-    q.raw = take(3 * (size_t)G + 3);
-    q.mu = take(3 * (size_t)G + 3);
-    q.nu = take(3 * (size_t)G + 3);
-  }
-  if (m) *m = q;
-  return o;
-}
+// SmallMap / small_map, one problem's LDS map (the MLL, gradient, fit and posterior kernels'),
+// and every launch size derived from it: lfm_small_plan.h
 
 // The MLL from a two-wave factor (every thread: pr / zr its row's pivot and z entry, rows < n):
 // per-wave sums, then wave 0's + wave 1's in that order; returned to every thread.
@@ -1367,19 +1289,6 @@ __global__ __launch_bounds__(256) void small_grad_kernel_args(SmallArgs a) {
 //     included), if fix_params, raw true_s[3] = 1.0 and raw true_d[3] = 0.8 (the unconstrained
 //     leaves: the reference's quirk; no-op for G <= 3, as JAX drops out-of-bounds updates)
 // The jitter slot holds the static jitter (constrained) and is never updated.
-struct FitArgs {
-  const SmallProb* probs;
-  const int* offs;  // [2 nprob]: each problem's offset of its vectors / scalars (packed layout)
-  int nprob;
-  double *raw, *mu, *nu;  // [nhyp] each, in / out
-  double* history;        // [nsteps][nprob]
-  const double* bias;     // [nsteps][2]
-  int* status;            // [nprob]: 1 + the first step whose factor failed, or 0
-  double lr, b1, b2, eps, eps_root;
-  int64_t step0, nsteps, spe;
-  int fix, negative;
-};
-
 __device__ __forceinline__ double softplus_d(double x) {
   // np.logaddexp(0, x): x + log1p(exp(-x)) for x >= 0, log1p(exp(x)) below
   return x >= 0.0 ? x + log1p(exp(-x)) : log1p(exp(x));
@@ -1389,7 +1298,7 @@ __device__ __forceinline__ double sigmoid_d(double x) {
   return x >= 0.0 ? 1.0 / (1.0 + e) : e / (1.0 + e);
 }
 
-__global__ __launch_bounds__(256) void small_fit_kernel(FitArgs a) {
+__global__ __launch_bounds__(256) void small_fit_kernel(SmallFitLaunch a) {
   #pragma clang fp contract(off)
   extern __shared__ __attribute__((aligned(16))) double sm[];
   const int b = blockIdx.x, tid = threadIdx.x;
@@ -1456,16 +1365,8 @@ __global__ __launch_bounds__(256) void small_fit_kernel(FitArgs a) {
   if (tid == 0) a.status[b] = first_bad;
 }
 
-// LDS of the gradient / fit launches: the largest problem's map
-size_t small_grad_lds(const SmallProb* probs, int nprob, int fit) {
-  size_t mx = 0;
-  for (int p = 0; p < nprob; ++p)
-    mx = std::max(mx, small_map(nullptr, probs[p].n, probs[p].G, probs[p].T, 1, 1, fit, nullptr));
-  return mx * sizeof(double);
-}
-
 static void small_attr(const void* f) {
-  hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+  hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, SMALL_LDS_BYTES);
 }
 
 int launch_small_grad(lfm_ctx* ctx, SmallArgs* a, const SmallProb* d_probs, const int* d_offs,
@@ -1475,7 +1376,8 @@ int launch_small_grad(lfm_ctx* ctx, SmallArgs* a, const SmallProb* d_probs, cons
     small_attr(reinterpret_cast<const void*>(&small_grad_kernel));
     small_attr(reinterpret_cast<const void*>(&small_grad_kernel_args));
   });
-  if (lds > 160 * 1024) return set_err(ctx, LFM_E_ARG, "small gradient batch: LDS past 160 KB");
+  if (lds > SMALL_LDS_BYTES)
+    return set_err(ctx, LFM_E_ARG, "small gradient batch: LDS past 160 KB");
   hipEvent_t ev;
   prof_begin(ctx, K_SMALL_GRAD, &ev, ctx->stream);
   if (a) {
@@ -1493,32 +1395,12 @@ int launch_small_grad(lfm_ctx* ctx, SmallArgs* a, const SmallProb* d_probs, cons
 }
 
 int launch_small_fit(lfm_ctx* ctx, const SmallFitLaunch& f, size_t lds) {
-  if (lds > 160 * 1024) return set_err(ctx, LFM_E_ARG, "small fit batch: LDS past 160 KB");
+  if (lds > SMALL_LDS_BYTES) return set_err(ctx, LFM_E_ARG, "small fit batch: LDS past 160 KB");
   static std::once_flag once;
   std::call_once(once, [] { small_attr(reinterpret_cast<const void*>(&small_fit_kernel)); });
-  FitArgs a{};
-  a.probs = f.probs;
-  a.offs = f.offs;
-  a.nprob = f.nprob;
-  a.raw = f.raw;
-  a.mu = f.mu;
-  a.nu = f.nu;
-  a.history = f.history;
-  a.bias = f.bias;
-  a.status = f.status;
-  a.lr = f.lr;
-  a.b1 = f.b1;
-  a.b2 = f.b2;
-  a.eps = f.eps;
-  a.eps_root = f.eps_root;
-  a.step0 = f.step0;
-  a.nsteps = f.nsteps;
-  a.spe = f.spe;
-  a.fix = f.fix;
-  a.negative = f.negative;
   hipEvent_t ev;
   prof_begin(ctx, K_SMALL_GRAD, &ev, ctx->stream);
-  hipLaunchKernelGGL(small_fit_kernel, dim3(f.nprob), dim3(256), lds, ctx->stream, a);
+  hipLaunchKernelGGL(small_fit_kernel, dim3(f.nprob), dim3(256), lds, ctx->stream, f);
   prof_end(ctx, K_SMALL_GRAD, ev, 0, 0, ctx->stream);
   return hip_fail(ctx, hipGetLastError(), "small_fit_kernel");
 }
@@ -1542,34 +1424,13 @@ int launch_small_fit(lfm_ctx* ctx, const SmallFitLaunch& f, size_t lds) {
 // problems' covariances: cov_ij = k(t_i, t_j) - sum_k V_ki V_kj from V in HBM (the same sums in
 // the same order: diag(cov) is var bit for bit), written to (i, j) and (j, i).
 // Not positive definite: status[p] = 1 + the failing column, the problem's outputs NaN.
-__host__ __device__ inline size_t small_post_base(int n, int G, int T) {
-  // the problem's map, then invd [n]; the panel follows
-  return small_map(nullptr, n, G, T, n + 1 <= 64, 0, 0, nullptr) + (size_t)n;
-}
-__host__ __device__ inline int small_post_cols_hd(int n, int G, int T) {
-  const size_t base = small_post_base(n, G, T), cap = 160 * 1024 / sizeof(double);
-  for (int c = 256; c >= 16; c >>= 1)
-    if (base + (size_t)n * c <= cap) return c;
-  return 0;
-}
-int small_post_cols(int n, int G, int T) { return small_post_cols_hd(n, G, T); }
-size_t small_post_lds(const SmallProb* probs, int nprob) {
-  size_t mx = 0;
-  for (int p = 0; p < nprob; ++p) {
-    const SmallProb& q = probs[p];
-    mx = std::max(mx, small_post_base(q.n, q.G, q.T) +
-                          (size_t)q.n * small_post_cols_hd(q.n, q.G, q.T));
-  }
-  return mx * sizeof(double);
-}
-
 __global__ __launch_bounds__(256) void small_post_kernel(SmallPostLaunch a) {
   extern __shared__ __attribute__((aligned(16))) double sm[];
   const int p = blockIdx.x, split = blockIdx.y, tid = threadIdx.x;
   const SmallProb P = a.probs[p];
   const PostProb pq = a.pp[p];
   const int n = P.n, M = n + 1, G = P.G;
-  const int unit = min(a.unit, small_post_cols_hd(n, G, P.T));  // a power of two
+  const int unit = min(a.unit, small_post_cols(n, G, P.T));  // a power of two
   if ((int64_t)split * unit >= pq.m) return;  // no pass of this problem left for this split
   const int tabs = M <= 64;
   SmallMap m;
@@ -1709,7 +1570,8 @@ __global__ __launch_bounds__(256) void small_post_cov_kernel(SmallPostLaunch a) 
 }
 
 int launch_small_post(lfm_ctx* ctx, const SmallPostLaunch& f, size_t lds) {
-  if (lds > 160 * 1024) return set_err(ctx, LFM_E_ARG, "small posterior batch: LDS past 160 KB");
+  if (lds > SMALL_LDS_BYTES)
+    return set_err(ctx, LFM_E_ARG, "small posterior batch: LDS past 160 KB");
   static std::once_flag once;
   std::call_once(once, [] { small_attr(reinterpret_cast<const void*>(&small_post_kernel)); });
   hipEvent_t ev;
@@ -1721,22 +1583,8 @@ int launch_small_post(lfm_ctx* ctx, const SmallPostLaunch& f, size_t lds) {
   return hip_fail(ctx, hipGetLastError(), "small_post_kernel");
 }
 
-size_t small_grid_extra(int n, int G, int T) {
-  return small_map(nullptr, n, G, T, 0, 0, 0, nullptr) - small_map(nullptr, n, G, 0, 0, 0, 0, nullptr);
-}
-
-static size_t small_lds(int maxn, int maxg, int gridtab, int* tabs_out) {
-  // tables (KxxTab) when every problem has n + 1 <= 64 rows; every other part of a problem's map
-  // grows with n and G, so the largest n and G bound every problem's map (the grid part apart:
-  // + gridtab, the largest small_grid_extra)
-  const int tabs = maxn + 1 <= 64;
-  *tabs_out = tabs;
-  return (small_map(nullptr, maxn, maxg, 0, tabs, 0, 0, nullptr) + (size_t)gridtab) *
-         sizeof(double);
-}
-
-// the MLL kernels' LDS limit raised to a CU's 160 KB, once per process (before any launch or
-// stream capture that uses them)
+// the MLL kernels' LDS limit raised to a CU's (SMALL_LDS_BYTES), once per process (before any
+// launch or stream capture that uses them)
 void small_batch_attrs() {
   static std::once_flag once;
   std::call_once(once, [] {
@@ -1745,12 +1593,11 @@ void small_batch_attrs() {
   });
 }
 
-int launch_small_args(lfm_ctx* ctx, SmallArgs& a, int nprob, int maxn, int maxg, int gridtab) {
-  int tabs;
-  const size_t lds = small_lds(maxn, maxg, gridtab, &tabs);
-  if (lds > 160 * 1024 || nprob > SMALL_ARG_PROBS)
+int launch_small_args(lfm_ctx* ctx, SmallArgs& a, int nprob, const SmallMllPlan& plan) {
+  const size_t lds = plan.lds_bytes;
+  if (lds > SMALL_LDS_BYTES || nprob > SMALL_ARG_PROBS)
     return set_err(ctx, LFM_E_ARG, "small batch (kernel arguments): past its limits");
-  a.tabs = tabs;
+  a.tabs = plan.tabs;
   small_batch_attrs();
   hipEvent_t ev;
   prof_begin(ctx, K_SMALL, &ev, ctx->stream);
@@ -1759,18 +1606,17 @@ int launch_small_args(lfm_ctx* ctx, SmallArgs& a, int nprob, int maxn, int maxg,
   return hip_fail(ctx, hipGetLastError(), "small_mll_kernel_args");
 }
 
-int launch_small_batch(lfm_ctx* ctx, const SmallProb* d_probs, int nprob, int maxn, int maxg,
-                       int gridtab, int negative, double* d_out, int* d_status) {
-  int tabs;
-  const size_t lds = small_lds(maxn, maxg, gridtab, &tabs);
-  if (lds > 160 * 1024)
+int launch_small_batch(lfm_ctx* ctx, const SmallProb* d_probs, int nprob, const SmallMllPlan& plan,
+                       int negative, double* d_out, int* d_status) {
+  const size_t lds = plan.lds_bytes;
+  if (lds > SMALL_LDS_BYTES)
     return set_err(ctx, LFM_E_ARG, "small batch: LDS past 160 KB (n <= 128, grid tables <= "
                                    "SMALL_GRID_TAB_MAX)");
   small_batch_attrs();
   hipEvent_t ev;
   prof_begin(ctx, K_SMALL, &ev, ctx->stream);
   hipLaunchKernelGGL(small_mll_kernel, dim3(nprob), dim3(256), lds, ctx->stream,
-                     d_probs, negative, d_out, d_status, tabs);
+                     d_probs, negative, d_out, d_status, plan.tabs);
   prof_end(ctx, K_SMALL, ev, 0, 0, ctx->stream);
   return hip_fail(ctx, hipGetLastError(), "small_mll_kernel");
 }

@@ -5,6 +5,7 @@
 #include <fcntl.h>
 #include <unistd.h>
 
+#include <algorithm>
 #include <atomic>
 #include <cerrno>
 #include <chrono>
@@ -12,6 +13,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <climits>
 #include <map>
 #include <random>
@@ -862,7 +864,430 @@ static void check_tenancy() {
   std::printf("tenancy lock: ok\n");
 }
 
+// ------------------------------------------------------------ the small-problem path
+// Every shape the small kernels take: n = 1..128, G | n, T = 0 or T | n with its grid tables
+// within SMALL_GRID_TAB_MAX (lfm_batch_create's admission, small_grid_T)
+static std::vector<SmallShape> small_shape_set(int nmax) {
+  std::vector<SmallShape> out;
+  for (int n = 1; n <= nmax; ++n)
+    for (int G = 1; G <= n; ++G) {
+      if (n % G) continue;
+      out.push_back({n, G, 0});
+      for (int T = 1; T <= n; ++T)
+        if (n % T == 0 && tables_doubles(G, T) <= (size_t)SMALL_GRID_TAB_MAX)
+          out.push_back({n, G, T});
+    }
+  return out;
+}
+
+// the regions of one map (doubles from the base) with the sizes the kernels use, stated here
+// from the layout's description, not from small_map's arithmetic
+struct Region {
+  const char* name;
+  size_t at, len;
+};
+static std::vector<Region> map_regions(const double* base, const SmallMap& m, const SmallShape& s,
+                                       int tabs, int grad, int fit) {
+  const size_t n = s.n, G = s.G, T = s.T, W = T ? 2 * T - 1 : 0, nh = 3 * G + 3;
+  std::vector<Region> r;
+  auto add = [&](const char* name, const void* p, size_t len) {
+    if (len) r.push_back({name, (size_t)((const double*)p - base), len});
+  };
+  add("A", m.A, (n + 1) * (size_t)m.ld);
+  add("red", m.red, 16);
+  add("hyp", m.hyp, nh);
+  add("ktab", m.ktab, tabs ? 3 * G + n + n * G : 0);
+  add("colbuf", m.colbuf, n + 1 > 64 ? (grad ? (size_t)SWEEP4_LDS : 512) : 264);
+  add("xs", m.xs, 3 * n);
+  add("ys", m.ys, n);
+  add("gt", m.gt, T ? tables_doubles((int)G, (int)T) : 0);
+  add("tms", m.tms, T);
+  add("bgs", m.bgs, T ? (n / T + 1) / 2 : 0);  // n / T ints
+  if (grad) {
+    add("gg", m.gg, 6 * G * W + 8 * G * T);
+    add("al", m.al, 128);
+    add("wd", m.wd, 128);
+    add("wb", m.wb, n + 1 <= 64 ? (n + 1) * (size_t)small_wb_ld((int)n) : 0);
+    add("accw", m.accw, 4 * (2 * G + 1));
+    add("gout", m.gout, nh);
+  }
+  if (fit) {
+    add("raw", m.raw, nh);
+    add("mu", m.mu, nh);
+    add("nu", m.nu, nh);
+  }
+  return r;
+}
+
+// regions inside [0, size) and pairwise disjoint; returns false on the first violation
+static bool regions_ok(std::vector<Region> r, size_t size, const char** bad) {
+  std::sort(r.begin(), r.end(), [](const Region& a, const Region& b) { return a.at < b.at; });
+  for (size_t i = 0; i < r.size(); ++i) {
+    *bad = r[i].name;
+    if (r[i].at + r[i].len > size) return false;
+    if (i + 1 < r.size() && r[i].at + r[i].len > r[i + 1].at) return false;
+  }
+  return true;
+}
+
+static void check_small_map() {
+  const std::vector<SmallShape> set = small_shape_set(SMALL_MAX);
+  const int modes[4][3] = {{0, 0, 0}, {1, 0, 0}, {1, 1, 0}, {1, 1, 1}};
+  std::vector<double> lds(64 * 1024);
+  for (const SmallShape& s : set) {
+    size_t size_grad = 0;
+    SmallMap mg{};
+    for (const auto& md : modes) {
+      SmallMap m{};
+      const size_t size = small_map(lds.data(), s.n, s.G, s.T, md[0], md[1], md[2], &m);
+      CHECK(size == small_map(nullptr, s.n, s.G, s.T, md[0], md[1], md[2], nullptr),
+            "map size with / without a base (%d,%d,%d)", s.n, s.G, s.T);
+      CHECK(size <= lds.size(), "map of (%d,%d,%d) is %zu doubles", s.n, s.G, s.T, size);
+      const char* bad = "";
+      CHECK(regions_ok(map_regions(lds.data(), m, s, md[0], md[1], md[2]), size, &bad),
+            "map (%d,%d,%d) mode %d%d%d: region %s overlaps or leaves the map", s.n, s.G, s.T,
+            md[0], md[1], md[2], bad);
+      CHECK((m.colbuf - lds.data()) % 2 == 0, "colbuf not 16-byte aligned (%d,%d,%d)", s.n, s.G,
+            s.T);
+      CHECK(m.n == s.n && m.G == s.G && m.ld == ((s.n + 2) | 1) && m.spare == nullptr,
+            "map header (%d,%d,%d)", s.n, s.G, s.T);
+      if (md[1] && !md[2]) {
+        size_grad = size;
+        mg = m;
+      }
+      if (md[2]) {
+        // the fit map = the gradient map + raw, mu, nu: small_value_grad_step's rebuild (fit = 1)
+        // sees small_grad_one's offsets (fit = 0)
+        const size_t nh = 3 * (size_t)s.G + 3;
+        SmallMap e = mg;
+        e.raw = lds.data() + size_grad;
+        e.mu = e.raw + nh;
+        e.nu = e.mu + nh;
+        CHECK(size == size_grad + 3 * nh && std::memcmp(&e, &m, sizeof(SmallMap)) == 0,
+              "fit map is not the gradient map + 3 trailing regions (%d,%d,%d)", s.n, s.G, s.T);
+      }
+    }
+    CHECK(small_grid_extra(s.n, s.G, s.T) ==
+              (s.T ? tables_doubles(s.G, s.T) + s.T + ((size_t)s.n / s.T + 1) / 2 + 1 : 0),
+          "small_grid_extra(%d,%d,%d)", s.n, s.G, s.T);
+    // the times [T] and the block genes (n / T ints) fit the staging area's grid slots
+    CHECK(s.T == 0 || s.T + (s.n / s.T + 1) / 2 <= small_grid_doubles(s.n),
+          "small_grid_doubles(%d) below the grid part at T = %d", s.n, s.T);
+  }
+  std::printf("small map: %zu shapes x 4 modes disjoint, aligned, fit = gradient + 3\n",
+              set.size());
+}
+
+// plan_small_mll of a batch's SmallDims holds each member's own map, within the limit. Pairs:
+// every shape with n in kN x every shape with n in kN (the extremes 1 and 128 included).
+static void check_small_bound() {
+  const std::set<int> kN = {1, 2, 7, 28, 31, 32, 33, 62, 63, 64, 65, 96, 120, 126, 127, 128};
+  std::vector<SmallShape> sub;
+  for (const SmallShape& s : small_shape_set(SMALL_MAX))
+    if (kN.count(s.n)) sub.push_back(s);
+  size_t pairs = 0, worst = 0;
+  for (const SmallShape& a : sub)
+    for (const SmallShape& b : sub) {
+      const SmallMllPlan pl = plan_small_mll(small_dims({a, b}));
+      for (const SmallShape& s : {a, b})
+        CHECK(pl.lds_bytes >= 8 * small_map(nullptr, s.n, s.G, s.T, pl.tabs, 0, 0, nullptr),
+              "plan_small_mll of (%d,%d,%d)+(%d,%d,%d) below a member's map", a.n, a.G, a.T, b.n,
+              b.G, b.T);
+      CHECK(pl.tabs == (std::max(a.n, b.n) + 1 <= 64), "tabs");
+      CHECK(pl.lds_bytes <= SMALL_LDS_BYTES, "admitted pair (%d,%d,%d)+(%d,%d,%d): %zu bytes",
+            a.n, a.G, a.T, b.n, b.G, b.T, pl.lds_bytes);
+      worst = std::max(worst, pl.lds_bytes);
+      ++pairs;
+    }
+  // the plan grows with each of maxn, maxg and gridtab, so the extreme of the whole shape set
+  // bounds every batch: n = G = 128 beside the largest grid part of any shape
+  size_t gmax = 0;
+  for (const SmallShape& s : small_shape_set(SMALL_MAX))
+    gmax = std::max(gmax, small_grid_extra(s.n, s.G, s.T));
+  const size_t top = plan_small_mll(SmallDims{SMALL_MAX, SMALL_MAX, (int)gmax}).lds_bytes;
+  CHECK(top <= SMALL_LDS_BYTES, "the extreme batch (grid part %zu doubles) takes %zu bytes", gmax,
+        top);
+  worst = std::max(worst, top);
+  // golden: the parent's small_lds / tabs, small_grad_lds
+  const int g[5][5] = {{28, 5, 0, 11936, 1}, {63, 9, 0, 43040, 1}, {64, 8, 0, 41328, 0},
+                       {128, 16, 0, 143920, 0}, {28, 4, 214, 13376, 1}};
+  for (const auto& c : g) {
+    const SmallMllPlan pl = plan_small_mll(SmallDims{c[0], c[1], c[2]});
+    CHECK((int)pl.lds_bytes == c[3] && pl.tabs == c[4], "plan_small_mll(%d,%d,%d) = %zu / %d",
+          c[0], c[1], c[2], pl.lds_bytes, pl.tabs);
+  }
+  CHECK(small_grid_extra(28, 4, 7) == 214 && small_dims({{28, 4, 7}}).gridtab == 214, "gridtab");
+  const int gl[4][5] = {{28, 4, 7, 27776, 28136}, {63, 9, 7, 93000, 93720},
+                        {64, 8, 8, 69200, 69848}, {127, 1, 0, 151024, 151168}};
+  for (const auto& c : gl)
+    CHECK((int)small_grad_lds({{c[0], c[1], c[2]}}, 0) == c[3] &&
+              (int)small_grad_lds({{c[0], c[1], c[2]}}, 1) == c[4],
+          "small_grad_lds(%d,%d,%d)", c[0], c[1], c[2]);
+  // 0: n = 128 (two waves hold n + 1 <= 128 rows), or a map past the limit
+  CHECK(small_grad_lds({{28, 4, 7}, {128, 16, 0}}, 0) == 0, "small_grad_lds at n = 128");
+  for (const SmallShape& s : sub)
+    for (int fit = 0; fit < 2; ++fit) {
+      const size_t own = 8 * small_map(nullptr, s.n, s.G, s.T, 1, 1, fit, nullptr);
+      CHECK(small_grad_lds({s}, fit) == (s.n > SMALL_GRAD_MAX || own > SMALL_LDS_BYTES ? 0 : own),
+            "small_grad_lds(%d,%d,%d)", s.n, s.G, s.T);
+    }
+  std::printf("small bound: %zu pairs, largest launch %zu bytes\n", pairs, worst);
+}
+
+// the kernel's tri_index (lfm_small.hip)
+static void tri_index(int q, int* i_out, int* c_out) {
+  int i = (int)((std::sqrt(8.0 * q + 1.0) - 1.0) * 0.5);
+  while (i * (i + 1) / 2 > q) --i;
+  while ((i + 1) * (i + 2) / 2 <= q) ++i;
+  *i_out = i;
+  *c_out = q - i * (i + 1) / 2;
+}
+
+// lfm_batch_posterior_f64's admission as the parent wrote it inline
+static PostPlan::Reject post_reject(const std::vector<SmallShape>& sh,
+                                    const std::vector<int64_t>& m, bool cov) {
+  int64_t sm = 0, sc = 0, ntiles = 0;
+  for (size_t p = 0; p < sh.size(); ++p) {
+    if (m[p] < 1 || m[p] % sh[p].G != 0 || m[p] > (1 << 20)) return PostPlan::BAD_M;
+    if (!small_post_cols(sh[p].n, sh[p].G, sh[p].T)) return PostPlan::NO_FIT;
+    const int64_t tb = (m[p] + 15) / 16;
+    sm += m[p];
+    sc += cov ? m[p] * m[p] : 0;
+    ntiles += cov ? tb * (tb + 1) / 2 : 0;
+    if (sm > ((int64_t)1 << 28) || sc > ((int64_t)1 << 29) || ntiles > INT_MAX / 2)
+      return PostPlan::TOO_LARGE;
+  }
+  return PostPlan::OK;
+}
+
+static void check_post_plan(const std::vector<SmallShape>& sh, const std::vector<int64_t>& m,
+                            int64_t nhyp, bool dv, bool cov) {
+  const PostPlan P = plan_small_post(sh, nhyp, m.data(), dv, cov);
+  CHECK(P.reject == post_reject(sh, m, cov), "posterior plan: reject %d", (int)P.reject);
+  if (P.reject) return;
+  const size_t np = sh.size();
+  int64_t sm = 0, sn = 0, sv = 0, sc = 0, ntiles = 0, wg64 = 0;
+  size_t lds = 0;
+  for (size_t p = 0; p < np; ++p) {
+    const PostProb& q = P.pp[p];
+    CHECK(q.t_off == sm && q.v_off == sv && q.cov_off == sc && q.m == m[p] && q.dv_off == sn &&
+              q.tile0 == ntiles && q.pad == 0,
+          "PostProb %zu", p);
+    const int64_t tb = (m[p] + 15) / 16;
+    sm += m[p];
+    sn += sh[p].n;
+    sv += cov ? sh[p].n * m[p] : 0;
+    sc += cov ? m[p] * m[p] : 0;
+    ntiles += cov ? tb * (tb + 1) / 2 : 0;
+    wg64 += (m[p] + 63) / 64;
+  }
+  CHECK(P.sm == sm && P.sn == sn && P.sv == sv && P.sc == sc && P.ntiles == ntiles, "sums");
+  CHECK(P.unit == (wg64 <= 4096 ? 64 : 256) && P.nsplit >= 1 && P.nsplit <= 1024, "unit / nsplit");
+  // the call's buffer, in bytes: disjoint, inside, aligned
+  struct B {
+    size_t at, len;
+  };
+  const std::vector<B> in = {{0, (size_t)nhyp * 8}, {P.dadd * 8, np * 8},
+                             {P.dv * 8, dv ? (size_t)sn * 8 : 0}, {P.t * 8, (size_t)sm * 24},
+                             {P.table * 8, np * sizeof(PostProb)}};
+  const std::vector<B> out = {{P.mean * 8, (size_t)sm * 8}, {P.var * 8, (size_t)sm * 8},
+                              {P.V * 8, (size_t)sv * 8}, {P.cov * 8, (size_t)sc * 8},
+                              {P.status * 8, np * sizeof(int)}};
+  size_t end = 0;
+  for (const B& b : in) {
+    CHECK(b.at == end && b.at % 8 == 0, "posterior inputs: not back to back");
+    end = b.at + b.len;
+  }
+  CHECK(end == P.in_bytes, "in_bytes");
+  for (const B& b : out) {
+    CHECK(b.at >= end && b.at % 8 == 0, "posterior outputs overlap");
+    end = std::max(end, b.at + b.len);
+  }
+  CHECK(end == P.all_bytes, "all_bytes");
+  // small_post_kernel's passes: grid (problem, split), j0 = split unit; j0 += nsplit unit
+  int64_t passes = 1;  // the most any problem has
+  for (size_t p = 0; p < np; ++p) {
+    const int cols = small_post_cols(sh[p].n, sh[p].G, sh[p].T);
+    const int unit = std::min(P.unit, cols);
+    lds = std::max(lds, 8 * (small_post_base(sh[p].n, sh[p].G, sh[p].T) + (size_t)sh[p].n * cols));
+    CHECK(8 * (small_post_base(sh[p].n, sh[p].G, sh[p].T) + (size_t)sh[p].n * unit) <= P.lds_bytes,
+          "panel of problem %zu past the launch's LDS", p);
+    std::vector<unsigned char> seen((size_t)m[p], 0);
+    bool once = true;
+    for (int split = 0; split < P.nsplit; ++split) {
+      if ((int64_t)split * unit >= m[p]) continue;
+      for (int64_t j0 = (int64_t)split * unit; j0 < m[p]; j0 += (int64_t)P.nsplit * unit)
+        for (int64_t j = j0; j < j0 + unit && j < m[p]; ++j) once = once && seen[j]++ == 0;
+    }
+    for (unsigned char c : seen) once = once && c == 1;
+    CHECK(once, "test columns of problem %zu not covered exactly once", p);
+    passes = std::max(passes, (m[p] + unit - 1) / unit);
+  }
+  CHECK(P.nsplit == std::min<int64_t>(passes, 1024), "nsplit %d, the most passes of a problem %lld",
+        P.nsplit, (long long)passes);
+  CHECK(P.lds_bytes == lds && lds <= SMALL_LDS_BYTES, "posterior LDS %zu", P.lds_bytes);
+  // small_post_cov_kernel: tile -> the last problem whose first tile is not past it
+  size_t p_true = 0;
+  for (int tile = 0; tile < P.ntiles; ++tile) {
+    int lo = 0, hi = (int)np - 1;
+    while (lo < hi) {
+      const int mid = (lo + hi + 1) >> 1;
+      if (P.pp[mid].tile0 <= tile) lo = mid;
+      else hi = mid - 1;
+    }
+    const int64_t tb = (m[lo] + 15) / 16;
+    while (tile >= P.pp[p_true].tile0 + ((m[p_true] + 15) / 16) * ((m[p_true] + 15) / 16 + 1) / 2)
+      ++p_true;
+    int ti, tj;
+    tri_index(tile - P.pp[lo].tile0, &ti, &tj);
+    CHECK((size_t)lo == p_true && tj >= 0 && tj <= ti && ti < tb, "tile %d -> problem %d (%d,%d)",
+          tile, lo, ti, tj);
+  }
+}
+
+static void check_small_post() {
+  const std::vector<SmallShape> all = small_shape_set(SMALL_GRAD_MAX);
+  std::vector<SmallShape> fits;
+  const SmallShape* nofit = nullptr;
+  for (const SmallShape& s : all) {
+    const int c = small_post_cols(s.n, s.G, s.T);
+    const size_t base = small_post_base(s.n, s.G, s.T), cap = SMALL_LDS_BYTES / 8;
+    CHECK(c == 0 || (c >= 16 && c <= 256 && (c & (c - 1)) == 0), "cols %d", c);
+    CHECK(base + (size_t)s.n * c <= cap, "panel of (%d,%d,%d) past the limit", s.n, s.G, s.T);
+    CHECK(c == 256 || base + (size_t)s.n * (c ? 2 * c : 16) > cap, "cols of (%d,%d,%d) not maximal",
+          s.n, s.G, s.T);
+    if (c) fits.push_back(s);
+    else if (!nofit) nofit = &s;
+  }
+  CHECK(small_post_cols(28, 4, 7) == 256 && small_post_cols(120, 8, 15) == 16 &&
+            small_post_cols(127, 1, 0) == 16, "golden small_post_cols");
+  // golden: the C5 calls (15 problems, n = 28 on the 4 x 7 grid)
+  const std::vector<SmallShape> c5(15, SmallShape{28, 4, 7});
+  for (int cov = 0; cov < 2; ++cov) {
+    const std::vector<int64_t> m(15, cov ? 400 : 100);
+    const PostPlan P = plan_small_post(c5, 15 * 15, m.data(), false, cov);
+    CHECK(P.reject == PostPlan::OK && P.unit == 64 && P.nsplit == (cov ? 7 : 2) &&
+              P.ntiles == (cov ? 4875 : 0) && P.lds_bytes == 70944,
+          "golden C5 posterior plan (cov %d): %d %d %d %zu", cov, P.unit, P.nsplit, P.ntiles,
+          P.lds_bytes);
+  }
+  std::mt19937_64 rng(11);
+  int plans = 0;
+  for (int np = 1; np <= 16; ++np)
+    for (int rep = 0; rep < 6; ++rep) {
+      std::vector<SmallShape> sh;
+      int64_t nhyp = 0;
+      for (int p = 0; p < np; ++p) {
+        sh.push_back(fits[rng() % fits.size()]);
+        nhyp += 3 * sh.back().G + 3;
+      }
+      // m: G, 16 G - G, the multiples of G around 64 k (k = 1, 2, 5), and (mode 5; with cov it
+      // is past the limits and must be rejected so) one giving wg64 > 4096
+      for (int mode = 0; mode < 6; ++mode) {
+        std::vector<int64_t> m;
+        for (int p = 0; p < np; ++p) {
+          const int64_t ks[3] = {1, 2, 5};
+          const int64_t G = sh[p].G, k64 = 64 * ks[rng() % 3];
+          const int64_t near = std::max<int64_t>(k64 / G, 1) * G;
+          m.push_back(mode == 0   ? G
+                      : mode == 1 ? 15 * G
+                      : mode == 2 ? std::max(near - G, G)
+                      : mode == 3 ? near + G
+                      : mode == 4 ? near
+                                  : (4100 * 64 / np + 64) / G * G + G);
+        }
+        for (int dv = 0; dv < 2; ++dv)
+          for (int cov = 0; cov < 2; ++cov) {
+            check_post_plan(sh, m, nhyp, dv, cov);
+            ++plans;
+          }
+      }
+    }
+  // the rejections, in the parent's precedence
+  const SmallShape ok = {28, 4, 7};
+  auto rej = [&](std::vector<SmallShape> sh, std::vector<int64_t> m, bool cov) {
+    return plan_small_post(sh, 15, m.data(), false, cov).reject;
+  };
+  CHECK(rej({ok}, {30}, false) == PostPlan::BAD_M, "m not a multiple of G");
+  CHECK(rej({ok}, {0}, false) == PostPlan::BAD_M, "m < 1");
+  CHECK(rej({ok}, {(1 << 20) + 4}, false) == PostPlan::BAD_M, "m > 2^20");
+  CHECK(rej({ok}, {1 << 20}, false) == PostPlan::OK, "m = 2^20");
+  CHECK(rej({ok}, {1 << 15}, true) == PostPlan::TOO_LARGE, "cov of 2^30 entries");
+  CHECK(rej({ok, ok}, {1 << 15, 30}, true) == PostPlan::TOO_LARGE, "sum limit before the next m");
+  CHECK(rej(std::vector<SmallShape>(257, ok), std::vector<int64_t>(257, 1 << 20), false) ==
+            PostPlan::TOO_LARGE, "sum of m > 2^28");
+  CHECK(nofit != nullptr, "no shape with n <= 127 whose posterior map is past the limit");
+  if (nofit) {
+    const int64_t G = nofit->G;
+    CHECK(rej({*nofit}, {G}, false) == PostPlan::NO_FIT, "map past the limit");
+    CHECK(rej({*nofit}, {0}, false) == PostPlan::BAD_M, "its own bad m first");
+    CHECK(rej({ok, *nofit}, {30, G}, false) == PostPlan::BAD_M, "an earlier bad m first");
+    CHECK(rej({*nofit, ok}, {G, 30}, false) == PostPlan::NO_FIT, "an earlier map first");
+  }
+  std::printf("small posterior: %zu shapes' columns, %d plans\n", all.size(), plans);
+}
+
+static void check_small_pack() {
+  const std::vector<SmallShape> set = small_shape_set(SMALL_MAX);
+  std::mt19937_64 rng(13);
+  for (int rep = 0; rep < 400; ++rep)
+    for (int inl = 0; inl < 2; ++inl) {
+      std::vector<SmallShape> sh;
+      for (int p = 0, np = 1 + (int)(rng() % 16); p < np; ++p) sh.push_back(set[rng() % set.size()]);
+      const SmallPack P = plan_small_pack(sh, inl);
+      size_t end = 0, bound = 0;
+      for (size_t p = 0; p < sh.size(); ++p) {
+        const size_t n = sh[p].n, G = sh[p].G, T = sh[p].T;
+        const SmallPack::Slot& a = P.at[p];
+        // x [3n] | y [n] | D S B [3G] | l obs_stddev jitter [3] | times [T], block genes [n / T]
+        CHECK(a.x == end && a.y == a.x + 3 * n && a.dsb == a.y + n, "pack: x y of problem %zu", p);
+        CHECK(inl ? a.sc == a.dsb + 3 * G && a.grid == a.sc + 3 : a.grid == a.dsb && a.sc == a.dsb,
+              "pack: hyperparameters of problem %zu", p);
+        end = a.grid + (T ? T + (n / T + 1) / 2 : 0);
+        bound += 4 * n + (inl ? 3 * G + 3 : 0) + n + (n + 1) / 2;
+      }
+      CHECK(P.bound == bound && end <= P.bound, "pack: the problems end at %zu, bound %zu", end,
+            P.bound);
+    }
+  // golden: the parent's pack_small over the 15 C5 problems and over a mixed batch (a grid, one
+  // off the grid, two more grids); per problem x, y, dsb, sc, grid
+  const std::vector<SmallShape> c5(15, SmallShape{28, 4, 7});
+  const SmallPack a = plan_small_pack(c5, true), b = plan_small_pack(c5, false);
+  for (size_t q = 0; q < 15; ++q) {
+    const SmallPack::Slot &s = a.at[q], &t = b.at[q];
+    CHECK(s.x == 136 * q && s.y == s.x + 84 && s.dsb == s.x + 112 && s.sc == s.x + 124 &&
+              s.grid == s.x + 127, "golden C5 pack (inline) %zu", q);
+    CHECK(t.x == 121 * q && t.y == t.x + 84 && t.grid == t.x + 112, "golden C5 pack %zu", q);
+  }
+  CHECK(a.at[14].grid + 9 == 2040 && b.at[14].grid + 9 == 1815, "golden C5 pack totals");
+  const std::vector<SmallShape> mix = {{28, 4, 7}, {35, 5, 0}, {64, 8, 8}, {120, 8, 15}};
+  const size_t gi[4][5] = {{0, 84, 112, 124, 127}, {136, 241, 276, 291, 294},
+                           {294, 486, 550, 574, 577}, {589, 949, 1069, 1093, 1096}};
+  const size_t gn[4][3] = {{0, 84, 112}, {121, 226, 261}, {261, 453, 517}, {529, 889, 1009}};
+  const SmallPack mi = plan_small_pack(mix, true), mn = plan_small_pack(mix, false);
+  for (size_t q = 0; q < 4; ++q) {
+    const SmallPack::Slot &s = mi.at[q], &t = mn.at[q];
+    CHECK(s.x == gi[q][0] && s.y == gi[q][1] && s.dsb == gi[q][2] && s.sc == gi[q][3] &&
+              s.grid == gi[q][4], "golden mixed pack (inline) %zu", q);
+    CHECK(t.x == gn[q][0] && t.y == gn[q][1] && t.grid == gn[q][2], "golden mixed pack %zu", q);
+  }
+  CHECK(mi.at[3].grid + 19 == 1115 && mn.at[3].grid + 19 == 1028, "golden mixed pack totals");
+  // the pinned buffer and the fit buffer: back to back, the int status words in their own doubles
+  const BatchLayout L = batch_layout(225, 15);
+  CHECK(L.out == 225 && L.status == 240 && L.grad == 255 && L.bytes == 480 * 8,
+        "batch_layout");
+  const FitLayout F = fit_layout(225, 15, 20);
+  CHECK(F.mu == 225 && F.nu == 450 && F.bias == 675 && F.hist == 715 && F.status == 1015 &&
+            F.bytes == 8180,
+        "fit_layout");
+  std::printf("small pack: 800 batches, golden C5 and mixed offsets, batch / fit layouts\n");
+}
+
 int main() {
+  check_small_map();
+  check_small_bound();
+  check_small_post();
+  check_small_pack();
   check_tenancy();
   check_enumeration();
   check_helper_clamp();

@@ -5,7 +5,14 @@ clamp, schedule 3's launch plan (plan_s3, over 1344 shapes: the flag array's fou
 every step's slots in them, workspace / X-buffer / matrix bounds, the lead units of each launch
 counted by enumeration against the target its chain waits for, a_done's target, the helper's
 share and its lead-free tail, the grids, the overlap mark; and three golden plans, the launches
-the library issued before the plan existed, flops included), the device tenancy lock: mutual
+the library issued before the plan existed, flops included), the small-problem path's layout
+and plans (lfm_small_plan.h: small_map's regions disjoint, inside the map and aligned over every
+(n, G, T) and mode, the fit map = the gradient map + three regions; plan_small_mll bounding
+each member's map within the LDS limit over pairs of shapes; small_post_cols maximal;
+plan_small_post's buffer regions, its passes covering every test column once as
+small_post_kernel enumerates them, the covariance kernel's tile search, the rejections in
+order; plan_small_pack's offsets; golden values from the library before the plans existed),
+the device tenancy lock: mutual
 exclusion, shared admission, cross-process waits and the turnstile) and the C++ oracle (oracle/lfm_cpu.cpp), built by tests/native/Makefile and run by
 tests/native/host_check.cpp. CPU only."""
 
