@@ -3,13 +3,15 @@
 // (1) the lane maps of v_mfma_f64_16x16x4_f64 / 4x4x4_4b (checked against host products),
 // (2) their sustained issue rates (TFLOP/s) with independent accumulators, (3) the pivot
 // rsqrt, (4) the trailing-update kernel alone (through liblfm's launch hook), (5) phase stamps
-// of the schedule-3 factorisation, (6) the schedule-3 tenancy state. No product call path
-// loads this library.
+// of the schedule-3 factorisation, (6) the schedule-3 tenancy state, (7) the grid gradient's
+// derivative tables as liblfm's table kernel writes them. No product call path loads this
+// library.
 #include <algorithm>
 #include <cstring>
 #include <string>
 #include <vector>
 
+#include "lfm_dual.h"
 #include "lfm_math.h"
 
 namespace lfm {
@@ -310,6 +312,37 @@ int probe_kxx_tab(lfm_ctx* ctx, const double* x, int64_t n, const lfm_hyp* hyp, 
   return hip_fail(ctx, e, "probe kxx tab");
 }
 
+// The grid gradient's 14 derivative tables as the product computes them: liblfm's own
+// grad_tables_kernel (lfm_grad.hip; its host handle resolves against liblfm.so), launched as
+// launch_grad launches it, on a hyp / T / dt / times given by the caller; out receives the
+// grad_tables_doubles(G, T) doubles of the layout in lfm_dual.h.
+__global__ void grad_tables_kernel(HypDev p, int T, double dt, const double* __restrict__ times,
+                                   double* __restrict__ tab);
+
+int probe_grad_tables(lfm_ctx* ctx, const lfm_hyp* hyp, int T, double dt, const double* times,
+                      double* out) {
+  const int G = (int)hyp->num_genes;
+  const size_t nh = 3 * (size_t)G, nt = grad_tables_doubles(G, T);
+  double* d = nullptr;
+  hipError_t e = hipMalloc((void**)&d, (nh + (size_t)T + nt) * sizeof(double));
+  if (e != hipSuccess) return hip_fail(ctx, e, "probe grad tables");
+  std::vector<double> hh(nh + T);
+  std::memcpy(hh.data(), hyp->true_d, G * 8);
+  std::memcpy(hh.data() + G, hyp->true_s, G * 8);
+  std::memcpy(hh.data() + 2 * G, hyp->true_b, G * 8);
+  std::memcpy(hh.data() + nh, times, (size_t)T * 8);
+  hipMemcpyAsync(d, hh.data(), (nh + T) * 8, hipMemcpyHostToDevice, ctx->stream);
+  const HypDev h{d, d + G, d + 2 * G, G, hyp->l};
+  hipLaunchKernelGGL(grad_tables_kernel, dim3((unsigned)std::min<size_t>((nt + 255) / 256, 4096)),
+                     dim3(256), 0, ctx->stream, h, T, dt, d + nh, d + nh + T);
+  e = hipGetLastError();
+  if (e == hipSuccess)
+    hipMemcpyAsync(out, d + nh + T, nt * 8, hipMemcpyDeviceToHost, ctx->stream);
+  const hipError_t es = hipStreamSynchronize(ctx->stream);
+  hipFree(d);
+  return hip_fail(ctx, e != hipSuccess ? e : es, "probe grad tables");
+}
+
 // Pseudo-random doubles in [-1/32, 1/32) (probe data: MFMA power, hence clocks, depends on it).
 __global__ void fill_hash_kernel(double* a, int64_t cnt) {
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < cnt; i += (int64_t)gridDim.x * 256) {
@@ -385,6 +418,15 @@ int lfm_probe_kxx_tab(lfm_ctx* ctx, const double* x, int64_t n, const lfm_hyp* h
     return LFM_E_ARG;
   DeviceGuard g(ctx->device);
   return probe_kxx_tab(ctx, x, n, hyp, out);
+}
+
+int lfm_probe_grad_tables(lfm_ctx* ctx, const lfm_hyp* hyp, int T, double dt, const double* times,
+                          double* out) {
+  if (!ctx || !hyp || !times || !out || T < 2 || T > 4096 || hyp->num_genes < 1 ||
+      hyp->num_genes > 4096 || !hyp->true_d || !hyp->true_s || !hyp->true_b)
+    return LFM_E_ARG;
+  DeviceGuard g(ctx->device);
+  return probe_grad_tables(ctx, hyp, T, dt, times, out);
 }
 
 // enable = 1 turns on s_memrealtime (100 MHz) stamps of the schedule-3 chain kernel's phases

@@ -2,7 +2,8 @@
 // Each function restates the reference expression it cites, in the same operation order,
 // with floating-point contraction off (no fused multiply-add): the reference's XLA-CPU
 // elementwise code rounds every product, and exact identities of the formula — e.g. the
-// t = 0 rows of h vanishing because erf is odd (SURVEY.md §4 KAT) — depend on it.
+// t = 0 rows of h vanishing because erf is odd (SURVEY.md §4 KAT) — depend on it. Past
+// gamma^2 = kGamma2Switch, where that order cancels, h and kernel_xf take the erfc form.
 #pragma once
 #include "lfm_internal.h"
 
@@ -11,12 +12,40 @@ namespace lfm {
 
 static constexpr double kSqrtPi = 1.7724538509055160273;
 
-// ------------------------------------------------------------- per-pair math
+// e^{A} erfc(z) without overflow: erfcx(z) e^{A - z^2} once erfc(z) underflows towards 0.
+__device__ __forceinline__ double exp_erfc(double A, double z) {
+  return z > 0.0 ? erfcx(z) * exp(A - z * z) : exp(A) * erfc(z);
+}
+
+// In the reference's order the sums erf(a - gamma) + erf(b + gamma) cancel to ~eps absolute and
+// are then multiplied by e^{gamma^2 - D delta}: the rounding of h grows with e^{gamma^2}. Up to
+// gamma^2 = kGamma2Switch (e^4 = 55; every benign point, the C5 rounds included, lies below)
+// the reference's order and bits are kept; beyond it h and kernel_xf take the erfc form of the
+// structured gram's tables (lfm_gram.hip), which does not cancel. At C3's ill-conditioned restarts
+// (gamma^2 up to 21) the reference order is off by up to 1e-2 absolute on entries of order 10.
+static constexpr double kGamma2Switch = 4.0;
+
+// h in the erfc form: erf(a - g) + erf(b + g) = erfc(g - a) - erfc(b + g) and
+// erf(t2/l - g) + erf(g) = erfc(g - t2/l) - erfc(g), each e^{A} erfc(z) through exp_erfc.
+// A row at t = 0 gives exactly 0, as the reference's order does (erf is odd).
+__device__ __forceinline__ double h_erfc(const HypDev& p, int j, int k, double t1, double t2) {
+  if (t1 == 0.0 || t2 == 0.0) return 0.0;
+  const double l = p.l;
+  const double g = p.D[k] * l / 2.0;
+  const double d = t2 - t1;
+  const double A = g * g - p.D[k] * d;
+  const double first = exp_erfc(A, g - d / l) - exp_erfc(A, t1 / l + g);
+  const double E = exp(-(p.D[k] * t2 + p.D[j] * t1));
+  const double Q = exp_erfc(g * g, g - t2 / l) - erfcx(g);
+  return (first - E * Q) / (p.D[j] + p.D[k]);
+}
+
 // h(j,k,t1,t2), model.py:315-365.
 __device__ __forceinline__ double h_ref(const HypDev& p, int j, int k, double t1, double t2) {
   #pragma clang fp contract(off)
   const double l = p.l;
   const double gk = p.D[k] * l / 2.0;                           // gamma(k), model.py:367-369
+  if (gk * gk > kGamma2Switch) return h_erfc(p, j, k, t1, t2);
   const double tdist = t2 - t1;
   const double multiplier = exp(gk * gk) / (p.D[j] + p.D[k]);
   const double first_multiplier = exp(-p.D[k] * tdist);
@@ -46,6 +75,11 @@ __device__ __forceinline__ double kxf_ref(const HypDev& p, double ta, double ga,
   const double gj = p.D[j] * l / 2.0;
   const double t_dist = tg - tl;
   const double first_term = 0.5 * l * kSqrtPi * p.S[j];
+  if (gj * gj > kGamma2Switch) {  // the erfc form (see kGamma2Switch); a gene row at t = 0 gives 0
+    if (tg == 0.0) return 0.0;
+    const double A = gj * gj - p.D[j] * t_dist;
+    return first_term * (exp_erfc(A, gj - t_dist / l) - exp_erfc(A, tl / l + gj));
+  }
   const double e1 = exp(gj * gj);
   const double e2 = exp(-p.D[j] * t_dist);
   const double erfs = erf((t_dist / l) - gj) + erf(tl / l + gj);
@@ -105,6 +139,9 @@ __device__ __forceinline__ double h_tab(const HypDev& p, const KxxTab& t, int j,
 __device__ __forceinline__ double kxx_tab(const HypDev& p, const KxxTab& t, double ta, int j,
                                           int a, double tb, int k, int b) {
   #pragma clang fp contract(off)
+  // past kGamma2Switch the tabulated erf values are not what h needs: the pair goes per pair
+  if (t.gam[j] * t.gam[j] > kGamma2Switch || t.gam[k] * t.gam[k] > kGamma2Switch)
+    return kxx_ref(p, ta, j, tb, k);
   const double mult = p.S[j] * p.S[k] * p.l * kSqrtPi * 0.5;
   const double se = exp(-(p.D[k] * tb + p.D[j] * ta));
   return mult * (h_tab(p, t, k, j, tb, ta, b, a, se) + h_tab(p, t, j, k, ta, tb, a, b, se));
@@ -131,11 +168,6 @@ __device__ __forceinline__ void small_tables(const HypDev& h, const double* __re
     e1[q] = erf(x[3 * i] / l + gam[g]);
   }
   __syncthreads();
-}
-
-// e^{A} erfc(z) without overflow: erfcx(z) e^{A - z^2} once erfc(z) underflows towards 0.
-__device__ __forceinline__ double exp_erfc(double A, double z) {
-  return z > 0.0 ? erfcx(z) * exp(A - z * z) : exp(A) * erfc(z);
 }
 
 // Entry idx of the grid-layout tables (layout and identities: lfm_gram.hip, tables_kernel),

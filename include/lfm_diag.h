@@ -53,6 +53,15 @@ int lfm_probe_rsq(lfm_ctx* ctx, const double* x, int64_t n, double* y);
  * per-gene tables small_mll_kernel uses for gene-gene pairs (KxxTab, lfm_math.h). */
 int lfm_probe_kxx_tab(lfm_ctx* ctx, const double* x, int64_t n, const lfm_hyp* hyp, double* out);
 
+/* The 14 derivative tables of the grid gradient (lfm_mll_grad_f64 on a dataset_3d layout with
+ * T % 256 == 0), computed by the product's own table kernel for hyp on the uniform grid
+ * times[T] (host) with spacing dt. out (host) receives num_genes * (6 (2T - 1) + 8T) doubles:
+ * the six Toeplitz tables Wt Xt dWt/dD dXt/dD dWt/dl dXt/dl, each [gene][d + T - 1] for
+ * d = tau' - tau in -(T-1)..T-1, then the eight time tables Pt dPt/dD dPt/dl Et dEt/dD Qt
+ * dQt/dD dQt/dl, each [gene][tau]. 2 <= T <= 4096. */
+int lfm_probe_grad_tables(lfm_ctx* ctx, const lfm_hyp* hyp, int T, double dt, const double* times,
+                          double* out);
+
 /* Layout probe: D = A(16x4) * B(4x16) on one wave through v_mfma_f64_16x16x4_f64;
  * A, B, D row-major host arrays. */
 int lfm_probe_mfma_f64_layout(lfm_ctx* ctx, const double* a, const double* b, double* d);

@@ -15,9 +15,42 @@ value that is right to fp64 rounding at any hyperparameters:
     difference d dt; the actual difference t_tau' - t_tau of the fp64 grid differs from it by a
     few ulp, which a first-order term restores (the second-order term is ~1e-28 relative).
   * ``mll_exact``: logdet, quadratic form and MLL from a long double column Cholesky.
+  * ``mll_grad_exact``: the gradient of log N(y; m, Sigma) in true_d, true_s, true_b, l and
+    obs_stddev, g = 1/2 tr(W dSigma) + a^T dm with a = Sigma^{-1} r and W = a a^T - Sigma^{-1}
+    from the long double Cholesky and a long double inverse, and the per-component scale
+    1/2 sum |W| |dSigma| + |a| |dm| of the same exact quantities. dK/dtheta comes by one of two
+    routes, which ``grid_vs_direct`` ties to each other:
+      - direct (``pair_grad_exact``): central differences of the reference formula itself in
+        mpmath at DIFF_DPS = 100 digits with step DIFF_H = 1e-25. The formula loses up to
+        e^{gamma^2 + 12 D} ~ 1e25 to cancellation, so a difference carries 1e-75 / 1e-25
+        = 1e-50 of round-off relative to its largest term and h^2 f''' / 6 = 1e-50 times a
+        ratio of derivatives (below 1e6 here) of truncation: both far below 1e-30. Any layout,
+        any flags; K is homogeneous in S, so dK/dS_g = K (multiplicity of g) / S_g.
+      - grid (``GridTables(..., grad=True)``): the D- and l-derivatives of the W, X, P, E, Q
+        tables and of Cm and Gt, differenced in mpmath the same way before rounding to long
+        double, combined by the product rule in long double. With f_k = Wt_k - Xt_k Pt_k,
+        d f_k / d delta = -D_k f_k + Gt, so the first-order grid-spacing term is
+        eps (-D_k f_k + Gt); its derivatives eps (-f_k - D_k df_k/dD_k) and
+        eps (-D_k df_k/dl + dGt/dl) are carried as well (gene j: the opposite sign).
+  * ``grad_tables_exact``: every entry of the 14 derivative tables of the grid gradient (the
+    layout of lfm_dual.h's grad_tables_doubles: Wt Xt dWt/dD dXt/dD dWt/dl dXt/dl per
+    (gene, d), then Pt dPt/dD dPt/dl Et dEt/dD Qt dQt/dD dQt/dl per (gene, tau)), differenced
+    in mpmath, and the magnitude M of the terms an evaluation from the identities sums. With
+    g = D l / 2, A = g^2 - D delta, z = g - delta / l, y = t / l + g, u = g - t / l,
+    c = 2 / sqrt(pi) (A - z^2 = -delta^2 / l^2, g^2 - u^2 = D t - t^2 / l^2):
+        dWt/dD = Wt (g l - delta) - c e^{-delta^2/l^2} l / 2
+        dWt/dl = Wt g D - c e^{-delta^2/l^2} (D / 2 + delta / l^2)
+        dXt/dD = Xt (g l - delta),   dXt/dl = Xt g D
+        dPt/dD = -c e^{-y^2} l / 2,  dPt/dl = -c e^{-y^2} (D / 2 - t / l^2)
+        dEt/dD = -t Et
+        dQt/dD = g l Qt - c (l / 2) (e^{D t - t^2/l^2} - 1)
+        dQt/dl = g D Qt - c ((D / 2 + t / l^2) e^{D t - t^2/l^2} - D / 2)
+    M is the sum of the absolute values of the products on the right, with g l - delta taken
+    as g l + |delta|, D / 2 -+ x as D / 2 + |x| and Qt as e^{g^2} (erfc(u) + erfc(g)).
 
-mpmath is needed by the generator (tests/golden/make_golden_exact.py) and by the CPU tests that
-regenerate a subsample; nothing here runs on a GPU box at test time.
+mpmath is needed by the generators (tests/golden/make_golden_exact.py and
+make_golden_exact_grad.py) and by the CPU tests that regenerate a subsample; nothing here runs
+on a GPU box at test time.
 """
 
 from __future__ import annotations
@@ -46,11 +79,16 @@ def _h(mp, Dj, Dk, L, t1, t2):
     return mult * (a - b)
 
 
+def _kxx_m(mp, Dj, Dk, Sj, Sk, L, Ta, Tb):
+    """kernel_xx (model.py:197-235) on mpf operands."""
+    mult = Sj * Sk * L * mp.sqrt(mp.pi) / 2
+    return mult * (_h(mp, Dk, Dj, L, Tb, Ta) + _h(mp, Dj, Dk, L, Ta, Tb))
+
+
 def _kxx(mp, D, S, l, j, ta, k, tb):
     Dj, Dk, L = mp.mpf(float(D[j])), mp.mpf(float(D[k])), mp.mpf(float(l))
     Ta, Tb = mp.mpf(float(ta)), mp.mpf(float(tb))
-    mult = mp.mpf(float(S[j])) * mp.mpf(float(S[k])) * L * mp.sqrt(mp.pi) / 2
-    return mult * (_h(mp, Dk, Dj, L, Tb, Ta) + _h(mp, Dj, Dk, L, Ta, Tb))
+    return _kxx_m(mp, Dj, Dk, mp.mpf(float(S[j])), mp.mpf(float(S[k])), L, Ta, Tb)
 
 
 def kxx_exact(D, S, l, j, ta, k, tb, dps=80):
@@ -71,26 +109,34 @@ def kernel_exact(xa, xb, D, S, l, dps=80):
     """The flag-switched kernel (model.py:152-312) of two rows (t, gene, flag), rounded to
     fp64; only the branch whose switch is non-zero is evaluated."""
     mp = _mp()
-    G = len(D)
-    f1, f2 = math.trunc(xa[2]), math.trunc(xb[2])
     with mp.workdps(dps):
-        val = mp.mpf(0)
-        if f1 * f2:
-            val += f1 * f2 * _kxx(mp, D, S, l, _gene(xa[1], G), xa[0], _gene(xb[1], G), xb[0])
-        if (1 - f1) * (1 - f2):
-            d = mp.mpf(float(xa[0])) - mp.mpf(float(xb[0]))
-            val += (1 - f1) * (1 - f2) * mp.exp(-(d * d) / (2 * mp.mpf(float(l))))
-        for sw, ra, rb in ((f1 * (1 - f2), xa, xb), ((1 - f1) * f2, xb, xa)):
-            if sw:
-                gene, lat = (rb, ra) if ra[2] == 0 else (ra, rb)
-                j = _gene(gene[1], G)
-                L, Dj = mp.mpf(float(l)), mp.mpf(float(D[j]))
-                tl = mp.mpf(float(lat[0]))
-                td = mp.mpf(float(gene[0])) - tl
-                gj = Dj * L / 2
-                val += sw * (L * mp.sqrt(mp.pi) / 2 * mp.mpf(float(S[j])) * mp.exp(gj * gj)
-                             * mp.exp(-Dj * td) * (mp.erf(td / L - gj) + mp.erf(tl / L + gj)))
-        return float(val)
+        return float(_kernel_m(mp, xa, xb, [mp.mpf(float(v)) for v in D],
+                               [mp.mpf(float(v)) for v in S], mp.mpf(float(l))))
+
+
+def _kernel_m(mp, xa, xb, Dm, Sm, L):
+    """kernel_exact on mpf hyperparameters (the lists Dm, Sm and L), unrounded."""
+    G = len(Dm)
+    f1, f2 = math.trunc(xa[2]), math.trunc(xb[2])
+    val = mp.mpf(0)
+    if f1 * f2:
+        j, k = _gene(xa[1], G), _gene(xb[1], G)
+        val += f1 * f2 * _kxx_m(mp, Dm[j], Dm[k], Sm[j], Sm[k], L, mp.mpf(float(xa[0])),
+                                mp.mpf(float(xb[0])))
+    if (1 - f1) * (1 - f2):
+        d = mp.mpf(float(xa[0])) - mp.mpf(float(xb[0]))
+        val += (1 - f1) * (1 - f2) * mp.exp(-(d * d) / (2 * L))
+    for sw, ra, rb in ((f1 * (1 - f2), xa, xb), ((1 - f1) * f2, xb, xa)):
+        if sw:
+            gene, lat = (rb, ra) if ra[2] == 0 else (ra, rb)
+            j = _gene(gene[1], G)
+            Dj = Dm[j]
+            tl = mp.mpf(float(lat[0]))
+            td = mp.mpf(float(gene[0])) - tl
+            gj = Dj * L / 2
+            val += sw * (L * mp.sqrt(mp.pi) / 2 * Sm[j] * mp.exp(gj * gj)
+                         * mp.exp(-Dj * td) * (mp.erf(td / L - gj) + mp.erf(tl / L + gj)))
+    return val
 
 
 def kernel_exact_pairs(x, rows, cols, D, S, l, y=None, dps=80):
@@ -174,13 +220,18 @@ def grid_of(x):
 class GridTables:
     """The gram tables of lfm_gram.hip's header at extended precision, for the genes in
     ``genes`` only: mpmath entries rounded to long double, plus the first-order term that
-    restores the actual time differences of the fp64 grid."""
+    restores the actual time differences of the fp64 grid. With ``grad`` also their D- and
+    l-derivatives (``dW[g] = (dWt/dD_g, dWt/dl)`` and so on, ``GtL``, ``CmD = dCm/dD_j =
+    dCm/dD_k``, ``CmL``), differenced in mpmath at DIFF_DPS digits before rounding, which
+    ``block_grad`` combines by the product rule."""
 
-    def __init__(self, t, D, S, l, genes, dps=50):
+    def __init__(self, t, D, S, l, genes, dps=50, grad=False):
         mp = _mp()
         t = np.asarray(t, np.float64)
         T = t.size
         self.T, self.genes = T, [int(g) for g in genes]
+        if grad:
+            self._init_grad(mp, t, D, S, l)
         with mp.workdps(dps):
             L = mp.mpf(float(l))
             tm = [mp.mpf(float(v)) for v in t]
@@ -232,6 +283,85 @@ class GridTables:
         fk = (Wk - Xk * Pk) * (1 - eps * self.D[k]) + eps * self.Gt[ik]
         fj = (Wj - Xj * Pj) * (1 + eps * self.D[j]) - eps * self.Gt[ij]
         return self.Cm[j, k] * ((fk + fj) - EE * QQ)
+
+    def _init_grad(self, mp, t, D, S, l):
+        T = self.T
+        with mp.workdps(DIFF_DPS):
+            h = mp.mpf(DIFF_H)
+            L = mp.mpf(float(l))
+            tm = [mp.mpf(float(v)) for v in t]
+            dt = (tm[-1] - tm[0]) / (T - 1) if T > 1 else mp.mpf(0)
+            deltas = [d * dt for d in range(-(T - 1), T)]
+
+            def ld(plus, minus):
+                return np.array([_to_ld((p - m) / (2 * h)) for p, m in zip(plus, minus)], dtype=LD)
+
+            def gt(Lv):
+                return [2 / (Lv * mp.sqrt(mp.pi)) * mp.exp(-(dl / Lv) ** 2) for dl in deltas]
+
+            self.GtL = ld(gt(L + h), gt(L - h))
+            self.dW, self.dX, self.dP, self.dE, self.dQ = {}, {}, {}, {}, {}
+            for g in self.genes:
+                Dg = mp.mpf(float(D[g]))
+                dp, dm = _gene_tables_m(mp, Dg + h, L, deltas, tm), _gene_tables_m(mp, Dg - h, L, deltas, tm)
+                lp, lm = _gene_tables_m(mp, Dg, L + h, deltas, tm), _gene_tables_m(mp, Dg, L - h, deltas, tm)
+                for name, store in (("W", self.dW), ("X", self.dX), ("P", self.dP),
+                                    ("E", self.dE), ("Q", self.dQ)):
+                    store[g] = (ld(dp[name], dm[name]), ld(lp[name], lm[name]))
+            self.CmD, self.CmL = {}, {}
+            for j in self.genes:
+                for k in self.genes:
+                    cm = (mp.mpf(float(S[j])) * mp.mpf(float(S[k])) * L * mp.sqrt(mp.pi) / 2
+                          / (mp.mpf(float(D[j])) + mp.mpf(float(D[k]))))
+                    # Cm = const l / (D_j + D_k)
+                    self.CmD[j, k] = _to_ld(-cm / (mp.mpf(float(D[j])) + mp.mpf(float(D[k]))))
+                    self.CmL[j, k] = _to_ld(cm / L)
+
+    def block_grad(self, j, k, taus=None, scale=False):
+        """(K, dK/dD_j, dK/dD_k, dK/dl) of the rows (gene j, taus) x columns (gene k, all tau')
+        in long double, the D-derivatives as partials (for j == k their sum is dK/dD_j); with
+        ``scale`` the sums of the absolute values of the product-rule terms instead."""
+        T = self.T
+        taus = np.arange(T) if taus is None else np.asarray(taus)
+        d = np.arange(T)[None, :] - taus[:, None]
+        eps = self.eps[taus]
+        ik, ij = d + (T - 1), -d + (T - 1)
+        col, row = (lambda v: v[None, :]), (lambda v: v[taus][:, None])
+        Wk, Xk, Wj, Xj = self.W[k][ik], self.X[k][ik], self.W[j][ij], self.X[j][ij]
+        WkD, Wkl, XkD, Xkl = self.dW[k][0][ik], self.dW[k][1][ik], self.dX[k][0][ik], self.dX[k][1][ik]
+        WjD, Wjl, XjD, Xjl = self.dW[j][0][ij], self.dW[j][1][ij], self.dX[j][0][ij], self.dX[j][1][ij]
+        Pk, PkD, Pkl = row(self.P[k]), row(self.dP[k][0]), row(self.dP[k][1])
+        Pj, PjD, Pjl = col(self.P[j]), col(self.dP[j][0]), col(self.dP[j][1])
+        Ek, EkD = col(self.E[k]), col(self.dE[k][0])
+        Ej, EjD = row(self.E[j]), row(self.dE[j][0])
+        Qk, QkD, Qkl = col(self.Q[k]), col(self.dQ[k][0]), col(self.dQ[k][1])
+        Qj, QjD, Qjl = row(self.Q[j]), row(self.dQ[j][0]), row(self.dQ[j][1])
+        EE, QQ = Ek * Ej, Qk + Qj
+        Cm, CmD, CmL = self.Cm[j, k], self.CmD[j, k], self.CmL[j, k]
+        if scale:
+            a = np.abs
+            MV = a(Wk) + a(Wj) + a(Xk * Pk) + a(Xj * Pj) + a(EE * QQ)
+            mk = a(WkD) + a(XkD * Pk) + a(Xk * PkD) + a(EkD * Ej * QQ) + a(EE * QkD)
+            mj = a(WjD) + a(XjD * Pj) + a(Xj * PjD) + a(Ek * EjD * QQ) + a(EE * QjD)
+            ml = (a(Wkl) + a(Xkl * Pk) + a(Xk * Pkl) + a(Wjl) + a(Xjl * Pj) + a(Xj * Pjl)
+                  + a(EE * Qkl) + a(EE * Qjl))
+            return (a(Cm) * MV, a(CmD) * MV + a(Cm) * mj, a(CmD) * MV + a(Cm) * mk,
+                    a(CmL) * MV + a(Cm) * ml)
+        Dk, Dj = self.D[k], self.D[j]
+        fk, fkD, fkl = Wk - Xk * Pk, WkD - XkD * Pk - Xk * PkD, Wkl - Xkl * Pk - Xk * Pkl
+        fj, fjD, fjl = Wj - Xj * Pj, WjD - XjD * Pj - Xj * PjD, Wjl - Xjl * Pj - Xj * Pjl
+        # gene k's term moves with +eps along delta, gene j's (argument -delta) with -eps
+        ck = fk + eps * (self.Gt[ik] - Dk * fk)
+        ckD = fkD - eps * (fk + Dk * fkD)
+        ckl = fkl + eps * (self.GtL[ik] - Dk * fkl)
+        cj = fj - eps * (self.Gt[ij] - Dj * fj)
+        cjD = fjD + eps * (fj + Dj * fjD)
+        cjl = fjl - eps * (self.GtL[ij] - Dj * fjl)
+        V = (ck + cj) - EE * QQ
+        Vk = ckD - EkD * Ej * QQ - EE * QkD
+        Vj = cjD - Ek * EjD * QQ - EE * QjD
+        Vl = (ckl + cjl) - EE * (Qkl + Qjl)
+        return Cm * V, CmD * V + Cm * Vj, CmD * V + Cm * Vk, CmL * V + Cm * Vl
 
 
 def sigma_exact(x, D, S, l, diag=0.0, dps=50, dtype=np.float64, tables=None):
@@ -286,6 +416,19 @@ def sigma_rows_exact(x, rows, D, S, l, tables=None, dps=50):
 
 
 # ------------------------------------------------------------------------ MLL
+def _chol_ld(A):
+    """Lower Cholesky factor of the long double matrix A by columns; None when not PD."""
+    n = A.shape[0]
+    Lm = np.zeros((n, n), dtype=LD)
+    for j in range(n):
+        col = A[j:, j] - Lm[j:, :j] @ Lm[j, :j]
+        if not col[0] > 0:
+            return None
+        piv = np.sqrt(col[0])
+        Lm[j:, j] = col / piv
+    return Lm
+
+
 def mll_exact(Sigma, r, perm=None):
     """(mll, logdet, quad) of N(r; 0, Sigma) from a long double column Cholesky (eps 1.1e-19).
     ``perm`` factors the symmetric permutation Sigma[perm][:, perm] instead: the same three
@@ -296,13 +439,9 @@ def mll_exact(Sigma, r, perm=None):
         A = A[np.ix_(perm, perm)]
         r = r[perm]
     n = A.shape[0]
-    Lm = np.zeros((n, n), dtype=LD)
-    for j in range(n):
-        col = A[j:, j] - Lm[j:, :j] @ Lm[j, :j]
-        if not col[0] > 0:
-            return float("nan"), float("nan"), float("nan")
-        piv = np.sqrt(col[0])
-        Lm[j:, j] = col / piv
+    Lm = _chol_ld(A)
+    if Lm is None:
+        return float("nan"), float("nan"), float("nan")
     z = np.empty(n, dtype=LD)
     for i in range(n):
         z[i] = (r[i] - Lm[i, :i] @ z[:i]) / Lm[i, i]
@@ -311,6 +450,289 @@ def mll_exact(Sigma, r, perm=None):
     mll = -(n * np.log(2 * LD(np.pi)) + logdet + quad) / 2
     # log(2 pi) from the fp64 pi: n * 1e-17 absolute, far below the tolerances in use
     return float(mll), float(logdet), float(quad)
+
+
+# ------------------------------------------------------------------- gradient
+DIFF_DPS = 100   # digits of every differenced evaluation
+DIFF_H = "1e-25"  # central-difference step (see the module docstring for the error budget)
+GRAD_KEYS = ("d", "s", "b", "l", "obs_stddev")
+
+
+def _gene_tables_m(mp, Dg, L, deltas, tm):
+    """One gene's W, X (per delta) and P, E, Q (per time) tables as mpf lists."""
+    gam = Dg * L / 2
+    X = [mp.exp(gam * gam - Dg * dl) for dl in deltas]
+    W = [X[i] * mp.erfc(gam - dl / L) for i, dl in enumerate(deltas)]
+    eg = mp.exp(gam * gam)
+    return dict(W=W, X=X, P=[mp.erfc(v / L + gam) for v in tm], E=[mp.exp(-Dg * v) for v in tm],
+                Q=[eg * (mp.erfc(gam - v / L) - mp.erfc(gam)) for v in tm])
+
+
+def _pair_grad_m(mp, xa, xb, Dm, Sm, L, h):
+    """(K, {g: dK/dD_g}, {g: dK/dS_g}, dK/dl) of one pair as mpf, by central differences."""
+    G = len(Dm)
+    f1, f2 = math.trunc(xa[2]), math.trunc(xb[2])
+    assert f1 in (0, 1) and f2 in (0, 1), "flags 0 / 1: exactly one branch is live"
+    K = _kernel_m(mp, xa, xb, Dm, Sm, L)
+    mult = {}
+    for f, row in ((f1, xa), (f2, xb)):
+        if f:
+            g = _gene(row[1], G)
+            mult[g] = mult.get(g, 0) + 1
+    dD, dS = {}, {}
+    for g, cnt in mult.items():
+        up, dn = list(Dm), list(Dm)
+        up[g], dn[g] = Dm[g] + h, Dm[g] - h
+        dD[g] = (_kernel_m(mp, xa, xb, up, Sm, L) - _kernel_m(mp, xa, xb, dn, Sm, L)) / (2 * h)
+        dS[g] = K * cnt / Sm[g]
+    dl = (_kernel_m(mp, xa, xb, Dm, Sm, L + h) - _kernel_m(mp, xa, xb, Dm, Sm, L - h)) / (2 * h)
+    return K, dD, dS, dl
+
+
+def pair_grad_exact(xa, xb, D, S, l):
+    """The direct route for one pair of rows (t, gene, flag): K, dK/dD [G], dK/dS [G] and
+    dK/dl, each rounded once to long double."""
+    mp = _mp()
+    G = len(D)
+    with mp.workdps(DIFF_DPS):
+        K, dD, dS, dl = _pair_grad_m(mp, xa, xb, [mp.mpf(float(v)) for v in D],
+                                     [mp.mpf(float(v)) for v in S], mp.mpf(float(l)),
+                                     mp.mpf(DIFF_H))
+        oD, oS = np.zeros(G, dtype=LD), np.zeros(G, dtype=LD)
+        for g in dD:
+            oD[g], oS[g] = _to_ld(dD[g]), _to_ld(dS[g])
+        return _to_ld(K), oD, oS, _to_ld(dl)
+
+
+def dk_direct(x, D, S, l):
+    """One block in ``mll_grad_exact``'s form holding the whole of K and its derivatives by
+    the direct route: the lower triangle pair by pair, mirrored."""
+    x = np.asarray(x, np.float64)
+    n, G = x.shape[0], len(D)
+    K, dl = np.zeros((n, n), dtype=LD), np.zeros((n, n), dtype=LD)
+    dD, dS = np.zeros((G, n, n), dtype=LD), np.zeros((G, n, n), dtype=LD)
+    for i in range(n):
+        for c in range(i + 1):
+            K[i, c], dD[:, i, c], dS[:, i, c], dl[i, c] = pair_grad_exact(x[i], x[c], D, S, l)
+            K[c, i], dD[:, c, i], dS[:, c, i], dl[c, i] = K[i, c], dD[:, i, c], dS[:, i, c], dl[i, c]
+    sl = slice(0, n)
+    return [(sl, sl, 1, K, {g: dD[g] for g in range(G)}, {g: dS[g] for g in range(G)}, dl)]
+
+
+def dk_grid(x, D, S, l, tables):
+    """K and its derivatives of a grid layout by the grid route, block by block (a generator
+    of ``mll_grad_exact`` blocks: the lower block triangle, the off-diagonal blocks counted
+    twice, the diagonal ones mirrored from their lower triangle as sigma_exact's are)."""
+    t, bg = grid_of(x)
+    G = len(D)
+    bg = [_gene(g, G) for g in bg]
+    T = t.size
+    for bi in range(len(bg)):
+        for bk in range(bi + 1):
+            j, k = bg[bi], bg[bk]
+            Kb, dj, dk, dl = tables.block_grad(j, k)
+            if bi == bk:
+                Kb, dj, dk, dl = (np.tril(v) + np.tril(v, -1).T for v in (Kb, dj, dk, dl))
+            dD = {j: dj + dk} if j == k else {j: dj, k: dk}
+            Sj, Sk = LD(float(S[j])), LD(float(S[k]))
+            dS = {j: 2 * Kb / Sj} if j == k else {j: Kb / Sj, k: Kb / Sk}
+            yield (slice(bi * T, (bi + 1) * T), slice(bk * T, (bk + 1) * T),
+                   1 if bi == bk else 2, Kb, dD, dS, dl)
+
+
+def w_exact(Sigma, r):
+    """(a = Sigma^{-1} r, W = a a^T - Sigma^{-1}, logdet, quad) in long double: the column
+    Cholesky of ``mll_exact``, the factor's inverse by forward substitution on the identity,
+    Sigma^{-1} = L^{-T} L^{-1}. None when Sigma is not PD."""
+    A = np.array(Sigma, dtype=LD)
+    r = np.asarray(r, dtype=LD).reshape(-1)
+    n = A.shape[0]
+    Lm = _chol_ld(A)
+    if Lm is None:
+        return None
+    Li = np.zeros((n, n), dtype=LD)
+    for i in range(n):
+        row = -(Lm[i, :i] @ Li[:i, :i + 1])
+        row[i] += 1
+        Li[i, :i + 1] = row / Lm[i, i]
+    Sinv = Li.T @ Li
+    z = Li @ r
+    a = Li.T @ z
+    return a, np.outer(a, a) - Sinv, 2 * np.sum(np.log(np.diagonal(Lm))), z @ z
+
+
+def contract_grad(blocks, W, a, x, D, B, obs_stddev, dtype=LD):
+    """The gradient dict (GRAD_KEYS and scale_* in oracle.mll_grad's layout, fp64 arrays) of
+    g = 1/2 sum W dSigma + a^T dm over ``blocks`` = (row slice, column slice, weight, K,
+    {g: dK/dD_g}, {g: dK/dS_g}, dK/dl), with every operand cast to ``dtype`` first (long
+    double: the truth; fp64: the restatement on correctly rounded inputs)."""
+    G, n = len(D), x.shape[0]
+    W, a = np.asarray(W, dtype=dtype), np.asarray(a, dtype=dtype)
+    g = {k: np.zeros(G, dtype=dtype) for k in ("d", "s")}
+    sc = {k: np.zeros(G, dtype=dtype) for k in ("d", "s")}
+    gl = sl = dtype(0)
+    for rs, cs, wgt, _, dD, dS, dl in blocks:
+        Wb = W[rs, cs]
+        aW = np.abs(Wb)
+        half = dtype(wgt) / 2
+        for key, parts in (("d", dD), ("s", dS)):
+            for q, m in parts.items():
+                m = np.asarray(m, dtype=dtype)
+                g[key][q] += half * np.sum(Wb * m)
+                sc[key][q] += half * np.sum(aW * np.abs(m))
+        m = np.asarray(dl, dtype=dtype)
+        gl += half * np.sum(Wb * m)
+        sl += half * np.sum(aW * np.abs(m))
+    # mean: m_i = (B / D)[i // (n / G)] flag_i (model.py:124-149: the block position)
+    bs = n // G
+    f = np.trunc(x[:, 2]).astype(dtype)
+    Dt, Bt = np.asarray(D, dtype=dtype), np.asarray(B, dtype=dtype)
+    af = np.array([np.sum((a * f)[q * bs:(q + 1) * bs]) for q in range(G)], dtype=dtype)
+    aabs = np.array([np.sum(np.abs(a * f)[q * bs:(q + 1) * bs]) for q in range(G)], dtype=dtype)
+    sd = dtype(float(obs_stddev))
+    dg = np.diagonal(W)
+    out = {"d": g["d"] - Bt / (Dt * Dt) * af, "s": g["s"], "b": af / Dt, "l": gl,
+           "obs_stddev": sd * np.sum(dg),
+           "scale_d": sc["d"] + np.abs(Bt / (Dt * Dt)) * aabs, "scale_s": sc["s"],
+           "scale_b": aabs / np.abs(Dt), "scale_l": sl,
+           "scale_obs_stddev": np.abs(sd) * np.sum(np.abs(dg))}
+    return {k: np.asarray(v, dtype=np.float64) for k, v in out.items()}
+
+
+def residual_ld(x, y, D, B):
+    """r = y - m in long double, m_i = (B / D)[i // (n / G)] flag_i."""
+    n, G = x.shape[0], len(D)
+    m = (np.asarray(B, dtype=LD) / np.asarray(D, dtype=LD))[np.arange(n) // (n // G)]
+    return np.asarray(y, dtype=LD).reshape(-1) - m * np.trunc(x[:, 2]).astype(LD)
+
+
+def mll_grad_exact(x, y, D, S, B, l, obs_stddev, jitter, tables=None, blocks=None):
+    """Exact value and gradient of log N(y; m, K + (jitter + obs_stddev^2) I): a dict with
+    value, logdet, quad, GRAD_KEYS and scale_* (oracle.mll_grad's layout), plus ``blocks``
+    (the long double K and derivative blocks), ``Sigma`` (long double) and ``r`` for a
+    restatement on rounded inputs. The grid route with ``tables`` (GridTables(grad=True)),
+    else the direct route. Where Sigma is not positive definite: {"not_pd": True, Sigma, r}."""
+    x = np.asarray(x, np.float64)
+    n = x.shape[0]
+    if blocks is None:
+        blocks = list(dk_grid(x, D, S, l, tables)) if tables is not None else dk_direct(x, D, S, l)
+    Sig = np.zeros((n, n), dtype=LD)
+    for rs, cs, _, Kb, _, _, _ in blocks:
+        Sig[rs, cs] = Kb
+        Sig[cs, rs] = Kb.T
+    idx = np.diag_indices(n)
+    Sig[idx] = Sig[idx] + (LD(float(jitter)) + LD(float(obs_stddev)) * LD(float(obs_stddev)))
+    r = residual_ld(x, y, D, B)
+    got = w_exact(Sig, r)
+    if got is None:  # not positive definite: no gradient; the caller gets Sigma to say by how much
+        return {"not_pd": True, "Sigma": Sig, "r": r}
+    a, W, logdet, quad = got
+    out = contract_grad(blocks, W, a, x, D, B, obs_stddev)
+    out.update(value=float(-(n * np.log(2 * LD(np.pi)) + logdet + quad) / 2),
+               logdet=float(logdet), quad=float(quad), blocks=blocks, Sigma=Sig, r=r)
+    return out
+
+
+def mll_grad_fp64(ex, x, D, B, obs_stddev):
+    """The fp64 restatement of ``mll_grad_exact``'s result ``ex``: scipy's Cholesky and inverse
+    on the correctly rounded Sigma and residual, the exact dSigma rounded to fp64."""
+    import scipy.linalg
+
+    Sig, r = ex["Sigma"].astype(np.float64), ex["r"].astype(np.float64)
+    c = scipy.linalg.cho_factor(Sig, lower=True, check_finite=False)
+    a = scipy.linalg.cho_solve(c, r, check_finite=False)
+    W = np.outer(a, a) - scipy.linalg.cho_solve(c, np.eye(Sig.shape[0]), check_finite=False)
+    return contract_grad(ex["blocks"], W, a, x, D, B, obs_stddev, dtype=np.float64)
+
+
+def grad_error(got, ex, sign=1.0):
+    """The largest |got - sign exact| / scale over the components of two gradient dicts."""
+    worst = 0.0
+    for k in GRAD_KEYS:
+        e = np.abs(np.atleast_1d(got[k]) - sign * np.atleast_1d(ex[k]))
+        worst = max(worst, float(np.max(e / np.atleast_1d(ex["scale_" + k]))))
+    return worst
+
+
+def grid_vs_direct(x, rows, cols, D, S, l, tables):
+    """The tie between the routes on the pairs (x[rows[i]], x[cols[i]]) of a grid layout: the
+    largest |grid - direct| / (sum of the absolute values of the product-rule terms) over K,
+    dK/dD_row, dK/dD_col and dK/dl."""
+    t, bg = grid_of(x)
+    G, T = len(D), t.size
+    worst = 0.0
+    for r, c in zip(rows, cols):
+        r, c = int(r), int(c)
+        j, k = _gene(bg[r // T], G), _gene(bg[c // T], G)
+        K, dD, _, dl = pair_grad_exact(x[r], x[c], D, S, l)
+        got = [v[0][c % T] for v in tables.block_grad(j, k, [r % T])]
+        mag = [v[0][c % T] for v in tables.block_grad(j, k, [r % T], scale=True)]
+        if j == k:
+            ref = (K, dD[j], dl)
+            got, mag = (got[0], got[1] + got[2], got[3]), (mag[0], mag[1] + mag[2], mag[3])
+        else:
+            ref = (K, dD[j], dD[k], dl)
+        worst = max(worst, max(float(abs(g - v) / m) for g, v, m in zip(got, ref, mag)))
+    return worst
+
+
+def grad_tables_exact(t, D, l):
+    """(exact, M), each a flat fp64 array in the layout of the device's 14 derivative tables
+    (grad_tables_doubles: six Toeplitz tables G x (2T - 1), eight time tables G x T) on the
+    uniform grid t: the derivative tables by central differences in mpmath, M from the
+    identities in the module docstring."""
+    mp = _mp()
+    t = np.asarray(t, np.float64)
+    T, G = t.size, len(D)
+    with mp.workdps(DIFF_DPS):
+        h = mp.mpf(DIFF_H)
+        L = mp.mpf(float(l))
+        tm = [mp.mpf(float(v)) for v in t]
+        dt = (tm[-1] - tm[0]) / (T - 1)
+        deltas = [d * dt for d in range(-(T - 1), T)]
+        c = 2 / mp.sqrt(mp.pi)
+        toe = [[] for _ in range(6)]
+        tim = [[] for _ in range(8)]
+        mtoe = [[] for _ in range(6)]
+        mtim = [[] for _ in range(8)]
+        for g in range(G):
+            Dg = mp.mpf(float(D[g]))
+            b = _gene_tables_m(mp, Dg, L, deltas, tm)
+            dp, dm = _gene_tables_m(mp, Dg + h, L, deltas, tm), _gene_tables_m(mp, Dg - h, L, deltas, tm)
+            lp, lm = _gene_tables_m(mp, Dg, L + h, deltas, tm), _gene_tables_m(mp, Dg, L - h, deltas, tm)
+
+            def dif(p, m, name):
+                return [(u - v) / (2 * h) for u, v in zip(p[name], m[name])]
+
+            for w, vals in enumerate((b["W"], b["X"], dif(dp, dm, "W"), dif(dp, dm, "X"),
+                                      dif(lp, lm, "W"), dif(lp, lm, "X"))):
+                toe[w] += [float(v) for v in vals]
+            for w, vals in enumerate((b["P"], dif(dp, dm, "P"), dif(lp, lm, "P"), b["E"],
+                                      dif(dp, dm, "E"), b["Q"], dif(dp, dm, "Q"),
+                                      dif(lp, lm, "Q"))):
+                tim[w] += [float(v) for v in vals]
+            gam = Dg * L / 2
+            for i, dl in enumerate(deltas):
+                Wv, Xv = abs(b["W"][i]), abs(b["X"][i])
+                ez = c * mp.exp(-(dl / L) ** 2)
+                lin = gam * L + abs(dl)
+                for w, v in enumerate((Wv, Xv, Wv * lin + ez * L / 2, Xv * lin,
+                                       Wv * gam * Dg + ez * (Dg / 2 + abs(dl) / (L * L)),
+                                       Xv * gam * Dg)):
+                    mtoe[w].append(float(v))
+            eg = mp.exp(gam * gam)
+            for i, tv in enumerate(tm):
+                ey = c * mp.exp(-(tv / L + gam) ** 2)
+                MQ = eg * (mp.erfc(gam - tv / L) + mp.erfc(gam))
+                eq = mp.exp(Dg * tv - tv * tv / (L * L))
+                Ev = b["E"][i]
+                for w, v in enumerate((b["P"][i], ey * L / 2, ey * (Dg / 2 + tv / (L * L)), Ev,
+                                       tv * Ev, MQ, gam * L * MQ + c * (L / 2) * (eq + 1),
+                                       gam * Dg * MQ + c * ((Dg / 2 + tv / (L * L)) * eq + Dg / 2))):
+                    mtim[w].append(float(v))
+    flat = [v for tab in toe + tim for v in tab]
+    mflat = [v for tab in mtoe + mtim for v in tab]
+    return np.array(flat), np.array(mflat)
 
 
 # ------------------------------------------------------------ reduced problems

@@ -196,6 +196,27 @@ def test_direct_path_vs_truth(red, sub):
     assert not bad, bad
 
 
+def test_direct_path_zero_time_rows_are_exactly_zero_past_the_switch(sub):
+    """Past gamma^2 = 4 the direct path leaves the reference's operation order for the erfc form
+    (kGamma2Switch, lfm_math.h). The identity the reference's order gives for free must survive:
+    a gene row at t = 0 has covariance exactly 0 with every gene row and every latent row, on
+    either side of the pair, at restarts 1, 5, 10, 29 (the largest-D gene is past the switch, the
+    others are not)."""
+    _, _, models = sub
+    xa = np.stack((np.zeros(4), np.arange(4.0), np.ones(4)), -1)
+    times = np.array([0.0, 0.7, 5.0, 12.0])
+    xb = np.concatenate([np.stack((np.tile(times, 4), np.repeat(np.arange(4.0), 4), np.ones(16)), -1),
+                         np.array([[0.3, 0.0, 0.0], [6.0, 2.0, 0.0]])])
+    for r in ILL:
+        m = models[r]
+        assert np.max((np.asarray(m.true_d) * m.l / 2) ** 2) > 4 > np.min((np.asarray(m.true_d) * m.l / 2) ** 2)
+        K = m.cross_covariance(m.kernel, xa, xb)
+        Kt = m.cross_covariance(m.kernel, xb, xa)
+        assert K.shape == (4, 18) and np.all(K == 0.0) and np.all(Kt == 0.0), r
+        # and the rows past t = 0 are not zero
+        assert np.all(m.cross_covariance(m.kernel, xb[1:4], xb[1:4]).diagonal() > 0)
+
+
 @pytest.fixture(scope="module")
 def c5():
     from dis_project_amd import configs
@@ -326,10 +347,12 @@ def test_fused_gram_is_bit_identical_at_ill_conditioned_restarts(red, sub, monke
 
 def test_gradient_value_matches_mll_path(red, sub):
     """lfm_mll_grad_f64's value (the bordered factor over the same gram) at restarts 5 and 29 of
-    the sub-model equals lfm_mll_f64's to 1e-12 relative."""
+    the sub-model equals lfm_mll_f64's to 1e-12 relative, and its gradient is within the project's
+    bound grad_rtol scale + 1e-10 |g| of the exact one (tests/golden/exact_grad.npz)."""
     from dis_project_amd import _lib
 
     x, y, models = sub
+    gx = load_golden("exact_grad")
     ctx = _lib.get_context(0)
     for r in (5, 29):
         hp = models[r].hyp()
@@ -339,7 +362,10 @@ def test_gradient_value_matches_mll_path(red, sub):
         ctx.check(ctx.lib.lfm_mll_grad_f64(ctx.handle, _lib.dptr(x), _lib.dptr(y), x.shape[0],
                                            hp.ref, 0, _lib.dptr(val), _lib.dptr(gv)))
         assert abs(val[0] - v[0]) <= 1e-12 * abs(v[0]), (r, val[0], v[0])
-        assert np.all(np.isfinite(gv))
+        assert r not in gx["sub_grad_dropped"]
+        ref = gx["sub_grad"][r]
+        bound = gx["sub_grad_rtol"][r] * gx["sub_scale"][r] + 1e-10 * np.abs(ref)
+        assert np.all(np.abs(gv - ref) <= bound), (r, (np.abs(gv - ref) / bound).round(3))
         assert abs(val[0] - red["sub_mll"][r]) <= red["sub_mll_rtol"][r] * abs(red["sub_mll"][r])
 
 
