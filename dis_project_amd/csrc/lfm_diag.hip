@@ -271,13 +271,11 @@ __global__ void kxx_tab_probe_kernel(const double* __restrict__ x, int n, const 
                                      double* __restrict__ out) {
   extern __shared__ double tb[];
   double* gam = tb;
-  double* egg = gam + G;
-  double* erg = egg + G;
-  double* e2 = erg + G;
-  double* e1 = e2 + n;
+  double* qr = gam + G;
+  double* pr = qr + n;
   const HypDev h{hyp, hyp + G, hyp + 2 * G, G, hyp[3 * G]};
-  const KxxTab t{gam, egg, erg, e1, e2, G};
-  small_tables(h, x, n, t, gam, egg, erg, e1, e2);
+  const KxxTab t{gam, pr, qr, G};
+  small_tables(h, x, n, G, gam, pr, qr);
   for (int q = threadIdx.x; q < n * n; q += 256) {
     const int i = q / n, c = q - i * n;
     const double* xa = x + 3 * i;
@@ -303,7 +301,7 @@ int probe_kxx_tab(lfm_ctx* ctx, const double* x, int64_t n, const lfm_hyp* hyp, 
   hh[3 * G] = hyp->l;
   hipMemcpyAsync(d, hh.data(), nh * 8, hipMemcpyHostToDevice, ctx->stream);
   hipMemcpyAsync(d + nh, x, nx * 8, hipMemcpyHostToDevice, ctx->stream);
-  const size_t lds = (3 * (size_t)G + n + (size_t)n * G) * sizeof(double);
+  const size_t lds = ((size_t)G + n + (size_t)n * G) * sizeof(double);
   hipLaunchKernelGGL(kxx_tab_probe_kernel, dim3(1), dim3(256), lds, ctx->stream, d + nh, (int)n,
                      d, G, d + nh + nx);
   hipMemcpyAsync(out, d + nh + nx, no * 8, hipMemcpyDeviceToHost, ctx->stream);

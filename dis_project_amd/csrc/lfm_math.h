@@ -2,8 +2,8 @@
 // Each function restates the reference expression it cites, in the same operation order,
 // with floating-point contraction off (no fused multiply-add): the reference's XLA-CPU
 // elementwise code rounds every product, and exact identities of the formula — e.g. the
-// t = 0 rows of h vanishing because erf is odd (SURVEY.md §4 KAT) — depend on it. Past
-// gamma^2 = kGamma2Switch, where that order cancels, h and kernel_xf take the erfc form.
+// t = 0 rows of h vanishing because erf is odd (SURVEY.md §4 KAT) — depend on it. h and
+// kernel_xf are the exception: the reference's order cancels there, and they take the erfc form.
 #pragma once
 #include "lfm_internal.h"
 
@@ -17,42 +17,52 @@ __device__ __forceinline__ double exp_erfc(double A, double z) {
   return z > 0.0 ? erfcx(z) * exp(A - z * z) : exp(A) * erfc(z);
 }
 
-// In the reference's order the sums erf(a - gamma) + erf(b + gamma) cancel to ~eps absolute and
-// are then multiplied by e^{gamma^2 - D delta}: the rounding of h grows with e^{gamma^2}. Up to
-// gamma^2 = kGamma2Switch (e^4 = 55; every benign point, the C5 rounds included, lies below)
-// the reference's order and bits are kept; beyond it h and kernel_xf take the erfc form of the
-// structured gram's tables (lfm_gram.hip), which does not cancel. At C3's ill-conditioned restarts
-// (gamma^2 up to 21) the reference order is off by up to 1e-2 absolute on entries of order 10.
-static constexpr double kGamma2Switch = 4.0;
+// In the reference's order (model.py:315-365) the sums erf(a - gamma) + erf(b + gamma) cancel to
+// ~eps absolute and are then multiplied by e^{gamma^2 - D delta}: its rounding is
+// eps e^{gamma^2 + D |delta|}, 1e-8 absolute at D = 1.95, l = 2 (gamma^2 = 3.8) and 1e-2 at C3's
+// worst restarts, on entries of order 1 to 10. A threshold on gamma^2 alone (the earlier
+// kGamma2Switch = 4) left the e^{D |delta|} part in: the posterior predictors missed their 1e-9
+// at five of C3's 32 restarts and at two of C5's problems (tests/test_gpu_exact_posterior.py).
+// h and kernel_xf therefore take the form that does not cancel at every hyperparameter:
+//   erf(a - g) + erf(b + g) = erfc(g - a) - erfc(b + g),  erf(t2/l - g) + erf(g) = erfc(g - t2/l) - erfc(g)
+// with every product e^{A} erfc(z), z > 0, as erfcx(z) e^{A - z^2} and A - z^2 written out, so
+// that it is not itself a difference of large numbers (2 g / l = D):
+//   Wt   = e^{g^2 - D d} erfc(g - d/l)        = erfcx(g - d/l) e^{-(d/l)^2}
+//   XtPt = e^{g^2 - D d} erfc(t1/l + g)       = erfcx(t1/l + g) e^{-(t1/l)^2} e^{-D t2}
+//   Qt   = e^{g^2} (erfc(g - t2/l) - erfc(g)) = erfcx(g - t2/l) e^{(t2/l)(2g - t2/l)} - erfcx(g)
+//   h    = (Wt - XtPt - e^{-D_k t2} e^{-D_j t1} Qt) / (D_j + D_k)
+// (the terms of the structured gram's tables, lfm_gram.hip). A row at t = 0 gives exactly 0, as
+// the reference's order does because erf is odd (SURVEY.md section 4 KAT).
 
-// h in the erfc form: erf(a - g) + erf(b + g) = erfc(g - a) - erfc(b + g) and
-// erf(t2/l - g) + erf(g) = erfc(g - t2/l) - erfc(g), each e^{A} erfc(z) through exp_erfc.
-// A row at t = 0 gives exactly 0, as the reference's order does (erf is odd).
-__device__ __forceinline__ double h_erfc(const HypDev& p, int j, int k, double t1, double t2) {
-  if (t1 == 0.0 || t2 == 0.0) return 0.0;
-  const double l = p.l;
-  const double g = p.D[k] * l / 2.0;
-  const double d = t2 - t1;
-  const double A = g * g - p.D[k] * d;
-  const double first = exp_erfc(A, g - d / l) - exp_erfc(A, t1 / l + g);
-  const double E = exp(-(p.D[k] * t2 + p.D[j] * t1));
-  const double Q = exp_erfc(g * g, g - t2 / l) - erfcx(g);
-  return (first - E * Q) / (p.D[j] + p.D[k]);
+// Wt: e^{g^2 - D d} erfc(g - d/l).
+__device__ __forceinline__ double wt_pair(double D, double g, double l, double d) {
+  #pragma clang fp contract(off)
+  const double v = d / l;
+  const double z = g - v;
+  return z > 0.0 ? erfcx(z) * exp(-(v * v)) : exp(g * g - D * d) * erfc(z);
+}
+// Xt Pt without its factor e^{-D t2}: depends on the row t1 (u1 = t1 / l) and the gene alone.
+__device__ __forceinline__ double xp_row(double g, double u1) {
+  #pragma clang fp contract(off)
+  const double z = u1 + g;
+  return z > 0.0 ? erfcx(z) * exp(-(u1 * u1)) : erfc(z) * exp(g * (g + 2.0 * u1));
+}
+// Qt: depends on the row t2 (u2 = t2 / l) and its own gene alone.
+__device__ __forceinline__ double qt_row(double g, double u2) {
+  #pragma clang fp contract(off)
+  const double z = g - u2;
+  return (z > 0.0 ? erfcx(z) * exp(u2 * (2.0 * g - u2)) : exp(g * g) * erfc(z)) - erfcx(g);
 }
 
 // h(j,k,t1,t2), model.py:315-365.
 __device__ __forceinline__ double h_ref(const HypDev& p, int j, int k, double t1, double t2) {
   #pragma clang fp contract(off)
+  if (t1 == 0.0 || t2 == 0.0) return 0.0;
   const double l = p.l;
   const double gk = p.D[k] * l / 2.0;                           // gamma(k), model.py:367-369
-  if (gk * gk > kGamma2Switch) return h_erfc(p, j, k, t1, t2);
-  const double tdist = t2 - t1;
-  const double multiplier = exp(gk * gk) / (p.D[j] + p.D[k]);
-  const double first_multiplier = exp(-p.D[k] * tdist);
-  const double first_erf = erf((tdist / l) - gk) + erf(t1 / l + gk);
-  const double second_multiplier = exp(-(p.D[k] * t2 + p.D[j] * t1));
-  const double second_erf = erf((t2 / l) - gk) + erf(gk);
-  return multiplier * (first_multiplier * first_erf - second_multiplier * second_erf);
+  const double ek = exp(-p.D[k] * t2), ej = exp(-p.D[j] * t1);
+  const double first = wt_pair(p.D[k], gk, l, t2 - t1) - xp_row(gk, t1 / l) * ek;
+  return (first - (ek * ej) * qt_row(gk, t2 / l)) / (p.D[j] + p.D[k]);
 }
 
 // kernel_xx, model.py:197-235.
@@ -62,7 +72,8 @@ __device__ __forceinline__ double kxx_ref(const HypDev& p, double ta, int j, dou
   return mult * (h_ref(p, k, j, tb, ta) + h_ref(p, j, k, ta, tb));
 }
 
-// kernel_xf, model.py:237-282 (the row whose flag is non-zero is the gene row).
+// kernel_xf, model.py:237-282 (the row whose flag is non-zero is the gene row): Wt - XtPt with
+// d = t_gene - t_latent and the latent time in Pt; a gene row at t = 0 gives 0.
 __device__ __forceinline__ double kxf_ref(const HypDev& p, double ta, double ga, double fa,
                                           double tb, double gb) {
   #pragma clang fp contract(off)
@@ -73,17 +84,9 @@ __device__ __forceinline__ double kxf_ref(const HypDev& p, double ta, double ga,
   const int j = gene_index(gg, p.G);
   const double l = p.l;
   const double gj = p.D[j] * l / 2.0;
-  const double t_dist = tg - tl;
   const double first_term = 0.5 * l * kSqrtPi * p.S[j];
-  if (gj * gj > kGamma2Switch) {  // the erfc form (see kGamma2Switch); a gene row at t = 0 gives 0
-    if (tg == 0.0) return 0.0;
-    const double A = gj * gj - p.D[j] * t_dist;
-    return first_term * (exp_erfc(A, gj - t_dist / l) - exp_erfc(A, tl / l + gj));
-  }
-  const double e1 = exp(gj * gj);
-  const double e2 = exp(-p.D[j] * t_dist);
-  const double erfs = erf((t_dist / l) - gj) + erf(tl / l + gj);
-  return first_term * e1 * e2 * erfs;
+  if (tg == 0.0) return 0.0;
+  return first_term * (wt_pair(p.D[j], gj, l, tg - tl) - xp_row(gj, tl / l) * exp(-p.D[j] * tg));
 }
 
 // kernel_ff, model.py:284-312 (divides by 2*l, not l^2: kept for parity).
@@ -110,62 +113,47 @@ __device__ __forceinline__ double kernel_ref(const HypDev& p, double ta, double 
 }
 
 // kernel_xx from per-problem tables (small_mll_kernel): the same operations on the same
-// operands as kxx_ref / h_ref, so the same bits, with every factor that depends on one row or
-// one gene only evaluated once per row / gene instead of once per pair:
-//   gam[g] = D_g l / 2, egg[g] = exp(gam^2), erg[g] = erf(gam)            (per gene)
-//   e2[i] = erf(t_i / l - gam[g_i]), e1[i G + g] = erf(t_i / l + gam[g])    (per row)
-// and exp(-(D_k t2 + D_j t1)), which both h terms of a pair share (the sum is the same two
-// products in the other order, and IEEE addition commutes). Left per pair: one erf and one exp
-// per h, the shared exp and the two divisions. a, b: row indices; j = g_a, k = g_b.
+// operands as kxx_ref / h_ref, so the same bits, with the factors that depend on one row only
+// evaluated once per row instead of once per pair:
+//   gam[g] = D_g l / 2                                                     (per gene)
+//   qr[i] = qt_row(gam[g_i], t_i / l), pr[i G + g] = xp_row(gam[g], t_i / l)  (per row)
+// Left per pair: e^{-D t} of either row, which both h terms share, one Wt (an erfcx or erfc and
+// an exp) per h and the two divisions. a, b: row indices; j = g_a, k = g_b.
 struct KxxTab {
   const double* gam;
-  const double* egg;
-  const double* erg;
-  const double* e1;
-  const double* e2;
+  const double* pr;
+  const double* qr;
   int G;
 };
 __device__ __forceinline__ double h_tab(const HypDev& p, const KxxTab& t, int j, int k,
-                                        double t1, double t2, int r1, int r2, double se) {
+                                        double t1, double t2, int r1, int r2, double ej,
+                                        double ek) {
   #pragma clang fp contract(off)
-  const double l = p.l;
-  const double tdist = t2 - t1;
-  const double multiplier = t.egg[k] / (p.D[j] + p.D[k]);
-  const double first_multiplier = exp(-p.D[k] * tdist);
-  const double first_erf = erf((tdist / l) - t.gam[k]) + t.e1[r1 * t.G + k];
-  const double second_erf = t.e2[r2] + t.erg[k];
-  return multiplier * (first_multiplier * first_erf - se * second_erf);
+  const double first = wt_pair(p.D[k], t.gam[k], p.l, t2 - t1) - t.pr[r1 * t.G + k] * ek;
+  return (first - (ek * ej) * t.qr[r2]) / (p.D[j] + p.D[k]);
 }
 __device__ __forceinline__ double kxx_tab(const HypDev& p, const KxxTab& t, double ta, int j,
                                           int a, double tb, int k, int b) {
   #pragma clang fp contract(off)
-  // past kGamma2Switch the tabulated erf values are not what h needs: the pair goes per pair
-  if (t.gam[j] * t.gam[j] > kGamma2Switch || t.gam[k] * t.gam[k] > kGamma2Switch)
-    return kxx_ref(p, ta, j, tb, k);
   const double mult = p.S[j] * p.S[k] * p.l * kSqrtPi * 0.5;
-  const double se = exp(-(p.D[k] * tb + p.D[j] * ta));
-  return mult * (h_tab(p, t, k, j, tb, ta, b, a, se) + h_tab(p, t, j, k, ta, tb, a, b, se));
+  if (ta == 0.0 || tb == 0.0) return mult * (0.0 + 0.0);
+  const double ea = exp(-p.D[j] * ta), eb = exp(-p.D[k] * tb);
+  return mult * (h_tab(p, t, k, j, tb, ta, b, a, eb, ea) + h_tab(p, t, j, k, ta, tb, a, b, ea, eb));
 }
 
 // KxxTab's per-gene and per-row factors of one problem, into the shared memory t points to
 // (one 256-thread workgroup; two workgroup barriers).
 __device__ __forceinline__ void small_tables(const HypDev& h, const double* __restrict__ x, int n,
-                                             const KxxTab& t, double* gam, double* egg,
-                                             double* erg, double* e1, double* e2) {
+                                             int G, double* gam, double* pr, double* qr) {
   #pragma clang fp contract(off)
-  const int tid = threadIdx.x, G = h.G;
+  const int tid = threadIdx.x;
   const double l = h.l;
-  for (int g = tid; g < G; g += 256) {
-    const double gk = h.D[g] * l / 2.0;  // gamma(k), model.py:367-369
-    gam[g] = gk;
-    egg[g] = exp(gk * gk);
-    erg[g] = erf(gk);
-  }
+  for (int g = tid; g < G; g += 256) gam[g] = h.D[g] * l / 2.0;  // gamma(k), model.py:367-369
   __syncthreads();
-  for (int i = tid; i < n; i += 256) e2[i] = erf((x[3 * i] / l) - gam[gene_index(x[3 * i + 1], G)]);
+  for (int i = tid; i < n; i += 256) qr[i] = qt_row(gam[gene_index(x[3 * i + 1], G)], x[3 * i] / l);
   for (int q = tid; q < n * G; q += 256) {
     const int i = q / G, g = q - i * G;
-    e1[q] = erf(x[3 * i] / l + gam[g]);
+    pr[q] = xp_row(gam[g], x[3 * i] / l);
   }
   __syncthreads();
 }

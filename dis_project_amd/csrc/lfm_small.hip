@@ -435,13 +435,11 @@ __device__ __forceinline__ void small_sigma(const SmallProb& P, const SmallMap& 
   } else if (tabs) {
     // n <= 63 (the launch's LDS holds the tables): gene-gene pairs from KxxTab, the same bits
     // as kernel_ref with a third of its transcendentals; pairs with a latent row direct
-    double* gam = m.ktab;
-    double* egg = gam + G;
-    double* erg = egg + G;
-    double* e2 = erg + G;
-    double* e1 = e2 + n;
-    const KxxTab t{gam, egg, erg, e1, e2, G};
-    small_tables(h, xs, n, t, gam, egg, erg, e1, e2);
+    double* gam = m.ktab;  // [G], 2 G unused
+    double* qr = gam + 3 * G;
+    double* pr = qr + n;
+    const KxxTab t{gam, pr, qr, G};
+    small_tables(h, xs, n, G, gam, pr, qr);
     const int np = n * (n + 1) / 2;  // the lower triangle, row by row
     for (int q = tid; q < np; q += 256) {
       int i = (int)((sqrt(8.0 * q + 1.0) - 1.0) * 0.5);

@@ -38,7 +38,8 @@ LFM_HD inline size_t tables_doubles(int G, int T) {
 //                           are then free of LDS bank conflicts)
 //   red    [16]             reductions
 //   hyp    [3G + 3]         D S B, l, obs_stddev, jitter (the constrained parameters)
-//   ktab   [3G + n + nG]    KxxTab's per-gene / per-row factors (tabs: n + 1 <= 64 in the launch)
+//   ktab   [3G + n + nG]    KxxTab's per-gene / per-row factors (tabs: n + 1 <= 64 in the launch):
+//                           gam [G], 2G unused since the erfc form, qr [n], pr [nG]
 //   colbuf [128 / 512]      the factor's column buffer(s): one wave 128; two waves (n + 1 > 64)
 //                           two of 256 (rows, a zero tail, the next pivot in slot 255)
 //   xs, ys [3n], [n]

@@ -48,8 +48,13 @@ value that is right to fp64 rounding at any hyperparameters:
     M is the sum of the absolute values of the products on the right, with g l - delta taken
     as g l + |delta|, D / 2 -+ x as D / 2 + |x| and Qt as e^{g^2} (erfc(u) + erfc(g)).
 
-mpmath is needed by the generators (tests/golden/make_golden_exact.py and
-make_golden_exact_grad.py) and by the CPU tests that regenerate a subsample; nothing here runs
+  * ``posterior_exact``: the posterior predictors' mean and covariance (model.py:420-514) from
+    entries of the reference formula in mpmath carried in long double (never rounded to fp64),
+    a long double Cholesky and forward solves; ``PairCache.scale`` gives the magnitude M of the
+    cancellation-free form's terms for any flag pairing (``mtab_scale``'s analogue for xf / ff).
+
+mpmath is needed by the generators (tests/golden/make_golden_exact.py, make_golden_exact_grad.py
+and make_golden_exact_posterior.py) and by the CPU tests that regenerate a subsample; nothing here runs
 on a GPU box at test time.
 """
 
@@ -733,6 +738,172 @@ def grad_tables_exact(t, D, l):
     flat = [v for tab in toe + tim for v in tab]
     mflat = [v for tab in mtoe + mtim for v in tab]
     return np.array(flat), np.array(mflat)
+
+
+# ------------------------------------------------------------------ posterior
+def _row_key(row, G):
+    """A row (t, gene, flag) as the kernel reads it: a latent row's gene index is not read."""
+    f = math.trunc(row[2])
+    return (float(row[0]), _gene(row[1], G) if f else 0, f)
+
+
+def _pair_scale_m(mp, xa, xb, Dm, Sm, L):
+    """The magnitude M of the terms of the cancellation-free form of ``_kernel_m`` for rows with
+    flags 0 / 1: gene / gene |Cm| sum |term| (``mtab_scale``); gene / latent
+    l sqrt(pi) / 2 S_j (|Wt_j| + |Xt_j Pt_j|) with delta = t_gene - t_latent and Pt at the latent
+    time; latent / latent the value itself."""
+    G = len(Dm)
+    f1, f2 = math.trunc(xa[2]), math.trunc(xb[2])
+    assert f1 in (0, 1) and f2 in (0, 1)
+    if f1 and f2:
+        j, k = _gene(xa[1], G), _gene(xb[1], G)
+        Ta, Tb = mp.mpf(float(xa[0])), mp.mpf(float(xb[0]))
+        gj, gk = Dm[j] * L / 2, Dm[k] * L / 2
+        delta = Tb - Ta
+        Cm = Sm[j] * Sm[k] * L * mp.sqrt(mp.pi) / 2 / (Dm[j] + Dm[k])
+        Xk, Xj = mp.exp(gk * gk - Dm[k] * delta), mp.exp(gj * gj + Dm[j] * delta)
+        Qk = mp.exp(gk * gk) * (mp.erfc(gk - Tb / L) - mp.erfc(gk))
+        Qj = mp.exp(gj * gj) * (mp.erfc(gj - Ta / L) - mp.erfc(gj))
+        terms = (Xk * mp.erfc(gk - delta / L), Xj * mp.erfc(gj + delta / L),
+                 Xk * mp.erfc(Ta / L + gk), Xj * mp.erfc(Tb / L + gj),
+                 mp.exp(-Dm[k] * Tb) * mp.exp(-Dm[j] * Ta) * (Qk + Qj))
+        return abs(Cm) * sum(abs(v) for v in terms)
+    if not f1 and not f2:
+        return abs(_kernel_m(mp, xa, xb, Dm, Sm, L))
+    gene, lat = (xa, xb) if f1 else (xb, xa)
+    j = _gene(gene[1], G)
+    tl = mp.mpf(float(lat[0]))
+    td = mp.mpf(float(gene[0])) - tl
+    gj = Dm[j] * L / 2
+    X = mp.exp(gj * gj - Dm[j] * td)
+    return abs(L * mp.sqrt(mp.pi) / 2 * Sm[j]) * (X * mp.erfc(gj - td / L) + X * mp.erfc(tl / L + gj))
+
+
+class PairCache:
+    """kernel(xa, xb) of rows (t, gene, flag) with flags 0 / 1 at ``dps`` digits, each distinct
+    pair evaluated once (the kernel is symmetric) and carried as a long double; ``scale`` gives
+    ``_pair_scale_m`` of the same pair as fp64. A pair whose terms are far below the cancelling
+    ones of the reference formula is evaluated at as many more digits as that takes."""
+
+    def __init__(self, D, S, l, dps=60):
+        self.mp = _mp()
+        self.dps = dps
+        with self.mp.workdps(dps):
+            self.Dm = [self.mp.mpf(float(v)) for v in D]
+            self.Sm = [self.mp.mpf(float(v)) for v in S]
+            self.L = self.mp.mpf(float(l))
+        self.G = len(D)
+        self.val, self.mag = {}, {}
+
+    def _key(self, xa, xb):
+        ka, kb = _row_key(xa, self.G), _row_key(xb, self.G)
+        return (ka, kb) if ka <= kb else (kb, ka)
+
+    def _digits(self, key, mag):
+        """Digits at which the reference formula, which loses e^{gamma^2 + D |dt|} to
+        cancellation, is still right to 1e-30 of ``mag`` (prefactors are below 1e3)."""
+        (ta, ja, fa), (tb, jb, fb) = key
+        if mag == 0 or not (fa or fb):
+            return self.dps
+        mp = self.mp
+        A = max((self.Dm[g] * self.L / 2) ** 2 + self.Dm[g] * abs(ta - tb)
+                for g, f in ((ja, fa), (jb, fb)) if f)
+        return max(self.dps, 33 + int(math.ceil(float(A / mp.log(10) - mp.log10(mag)))))
+
+    def _mag(self, key):
+        if key not in self.mag:
+            with self.mp.workdps(self.dps):
+                self.mag[key] = _pair_scale_m(self.mp, key[0], key[1], self.Dm, self.Sm, self.L)
+        return self.mag[key]
+
+    def value(self, xa, xb):
+        key = self._key(xa, xb)
+        if key not in self.val:
+            with self.mp.workdps(self._digits(key, self._mag(key))):
+                self.val[key] = _to_ld(_kernel_m(self.mp, key[0], key[1], self.Dm, self.Sm, self.L))
+        return self.val[key]
+
+    def scale(self, xa, xb):
+        return float(self._mag(self._key(xa, xb)))
+
+    def matrix(self, xa, xb=None, scale=False):
+        """kernel (or its scale) of every row of xa against every row of xb; with xb None the
+        lower triangle of xa against itself, mirrored."""
+        fn = self.scale if scale else self.value
+        dt = np.float64 if scale else LD
+        if xb is None:
+            n = len(xa)
+            out = np.zeros((n, n), dtype=dt)
+            for i in range(n):
+                for c in range(i + 1):
+                    out[i, c] = out[c, i] = fn(xa[i], xa[c])
+            return out
+        return np.array([[fn(a, b) for b in xb] for a in xa], dtype=dt).reshape(len(xa), len(xb))
+
+
+def posterior_entries(x, t, D, S, l, dps=60, diag_only=False, cache=None):
+    """(K(x,x), K(t,x), K(t,t)) in long double from ``_kernel_m`` at ``dps`` digits, never
+    rounded to fp64; with ``diag_only`` the third is the diagonal of K(t,t) alone."""
+    x, t = np.asarray(x, np.float64), np.asarray(t, np.float64)
+    pc = cache or PairCache(D, S, l, dps)
+    Ktt = (np.array([pc.value(r, r) for r in t], dtype=LD) if diag_only else pc.matrix(t))
+    return pc.matrix(x), pc.matrix(t, x), Ktt
+
+
+def posterior_from_entries(ent, x, y, diag_vec, diag_add, t, D, B, dtype=LD, perm=None):
+    """(mean, cov) of the posterior from the entries ``ent`` of ``posterior_entries`` (cov is the
+    variance vector when ent[2] is K(t,t)'s diagonal): S = K(x,x) + diag(diag_vec) + diag_add I,
+    V = L^{-1} K(x,t), z = L^{-1} (y - m(x)), mean = m(t) + V^T z, cov = K(t,t) - V^T V, in
+    ``dtype`` (long double: the truth, by ``_chol_ld``; fp64: scipy's Cholesky and triangular
+    solves on the entries rounded once). ``perm`` factors the symmetric permutation instead.
+    (None, None) when S is not positive definite."""
+    Kxx, Ktx, Ktt = ent
+    x, t = np.asarray(x, np.float64), np.asarray(t, np.float64)
+    n, m, G = x.shape[0], t.shape[0], len(D)
+    dv = np.zeros(n) if diag_vec is None else np.asarray(diag_vec, np.float64).reshape(-1)
+    Sig = np.array(Kxx, dtype=LD)
+    idx = np.diag_indices(n)
+    Sig[idx] = Sig[idx] + (dv.astype(LD) + LD(float(diag_add)))
+    r = residual_ld(x, y, D, B)
+    Kxt = np.array(Ktx, dtype=LD).T
+    if perm is not None:
+        Sig, r, Kxt = Sig[np.ix_(perm, perm)], r[perm], Kxt[perm]
+    mt = ((np.asarray(B, dtype=LD) / np.asarray(D, dtype=LD))[np.arange(m) // (m // G)]
+          * np.trunc(t[:, 2]).astype(LD))
+    if dtype == LD:
+        Lm = _chol_ld(Sig)
+        if Lm is None:
+            return None, None
+        W = np.concatenate([Kxt, r[:, None]], axis=1)
+        for i in range(n):
+            W[i] = (W[i] - Lm[i, :i] @ W[:i]) / Lm[i, i]
+    else:
+        import scipy.linalg
+
+        try:
+            Lm = scipy.linalg.cholesky(Sig.astype(dtype), lower=True, check_finite=False)
+        except (np.linalg.LinAlgError, scipy.linalg.LinAlgError):
+            return None, None
+        W = scipy.linalg.solve_triangular(
+            Lm, np.concatenate([Kxt, r[:, None]], axis=1).astype(dtype), lower=True,
+            check_finite=False)
+        mt, Ktt = mt.astype(dtype), np.asarray(Ktt).astype(dtype)
+    V, z = W[:, :m], W[:, m]
+    mean = mt + V.T @ z
+    cov = Ktt - np.sum(V * V, axis=0) if np.ndim(Ktt) == 1 else Ktt - V.T @ V
+    return mean.astype(np.float64), cov.astype(np.float64)
+
+
+def posterior_exact(x, y, diag_vec, diag_add, t, D, S, B, l, dps=60, perm=None, diag_only=False,
+                    entries=None):
+    """The exact posterior (mean [m], cov [m, m]) of model.py:420-514's predictors before their
+    jitter assembly, mean = m(t) + K(t,x) S^{-1} (y - m(x)), cov = K(t,t) - K(t,x) S^{-1} K(x,t),
+    S = K(x,x) + diag(diag_vec) + diag_add I: entries from the reference formula in mpmath at
+    ``dps`` digits carried in long double, a long double Cholesky and forward solves, rounded to
+    fp64 at the end. ``diag_only``: the variances instead of cov. (None, None) where S is not
+    positive definite in this arithmetic."""
+    ent = entries or posterior_entries(x, t, D, S, l, dps, diag_only)
+    return posterior_from_entries(ent, x, y, diag_vec, diag_add, t, D, B, perm=perm)
 
 
 # ------------------------------------------------------------ reduced problems

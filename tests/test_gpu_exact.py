@@ -10,8 +10,9 @@ make_golden_exact.py) and the bounds are the fixture's own:
   * structured gram entries: |dK| <= k_tab64 eps M_tab (fp32: k_tab32 eps32 M_tab), M_tab the
     magnitude of the five terms of the cancellation-free table form, k_tab 4 x what a numpy
     restatement of that form needs;
-  * direct / small-table paths, which keep the reference's operation order: 16 eps
-    gram_error_scale of the truth;
+  * direct / small-table paths: 16 eps gram_error_scale of the truth (they take the erfc form
+    too; tests/test_gpu_exact_posterior.py holds them to a bound that does not grow with the
+    reference order's cancellation);
   * MLL: the fixture's per-problem mll_rtol (1e-9 wherever LAPACK on correctly rounded inputs
     is that good, which is everywhere here).
 
@@ -179,8 +180,8 @@ def oracle_scale(x, rows, cols, D, S, l):
 
 def test_direct_path_vs_truth(red, sub):
     """gram_direct_kernel (cross_covariance of the sampled rows against the sampled columns: a
-    scattered copy of the same points, so no layout is detected) keeps the reference's
-    operation order: within 16 eps gram_error_scale of the truth, all 32 restarts."""
+    scattered copy of the same points, so no layout is detected): within 16 eps
+    gram_error_scale of the truth, all 32 restarts."""
     x, _, models = sub
     worst, bad = 0.0, []
     for r, m in enumerate(models):
@@ -197,11 +198,10 @@ def test_direct_path_vs_truth(red, sub):
 
 
 def test_direct_path_zero_time_rows_are_exactly_zero_past_the_switch(sub):
-    """Past gamma^2 = 4 the direct path leaves the reference's operation order for the erfc form
-    (kGamma2Switch, lfm_math.h). The identity the reference's order gives for free must survive:
+    """The direct path takes the erfc form (lfm_math.h), not the reference's operation order.
+    The identity the reference's order gives for free must survive:
     a gene row at t = 0 has covariance exactly 0 with every gene row and every latent row, on
-    either side of the pair, at restarts 1, 5, 10, 29 (the largest-D gene is past the switch, the
-    others are not)."""
+    either side of the pair, at restarts 1, 5, 10, 29 (genes on both sides of gamma^2 = 4)."""
     _, _, models = sub
     xa = np.stack((np.zeros(4), np.arange(4.0), np.ones(4)), -1)
     times = np.array([0.0, 0.7, 5.0, 12.0])
