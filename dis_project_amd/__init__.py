@@ -9,7 +9,7 @@ from .dataset import Dataset, SyntheticP53Data, dataset_3d  # noqa: F401
 from .distributions import GaussianDistribution  # noqa: F401
 from .model import ExactLFM  # noqa: F401
 from .objectives import CustomConjMLL  # noqa: F401
-from .predict import BatchPredictor  # noqa: F401
+from .predict import BatchPredictor, Posterior  # noqa: F401
 
 __all__ = [
     "BatchPredictor",
@@ -18,6 +18,7 @@ __all__ = [
     "ExactLFM",
     "GaussianDistribution",
     "LfmError",
+    "Posterior",
     "SyntheticP53Data",
     "dataset_3d",
     "device_count",

@@ -141,6 +141,11 @@ PRODUCT_SIGNATURES = [
       _dptr]),
     ("lfm_batch_posterior_f64", c_int,
      [_c_ctx, c_void_p, _dptr, _dptr, _dptr, _dptr, _dptr, _dptr, _dptr, _dptr, _dptr]),
+    ("lfm_post_create", c_int,
+     [_c_ctx, _dptr, _dptr, c_int64, _dptr, c_double, POINTER(LfmHyp), POINTER(c_void_p)]),
+    ("lfm_post_destroy", c_int, [c_void_p]),
+    ("lfm_post_set_chunk", c_int, [c_void_p, c_int64]),
+    ("lfm_post_predict_f64", c_int, [_c_ctx, c_void_p, _dptr, c_int64, _dptr, _dptr, _dptr]),
     ("lfm_log_prob_f64", c_int, [_c_ctx, _dptr, _dptr, c_int64, c_int64, _dptr, _dptr]),
     ("lfm_h_f64", c_int,
      [_c_ctx, POINTER(LfmHyp), POINTER(c_int64), POINTER(c_int64), _dptr, _dptr, c_int64, _dptr]),
@@ -192,7 +197,7 @@ DIAG_SIGNATURES = [
 # kernel classes in lfm_profile_read order (lfm_internal.h KClass)
 KCLASSES = ["tables", "gram_grid", "gram_direct", "augment", "potrf", "trsm", "syrk",
             "finalize", "small_mll", "mean", "grad", "panel", "syrk_side", "small_grad",
-            "small_post"]
+            "small_post", "post_panel", "post_update"]
 
 _lib = None
 _diag = None

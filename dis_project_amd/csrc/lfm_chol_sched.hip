@@ -186,7 +186,7 @@ int probe_update_launch(lfm_ctx* ctx, hipStream_t st, int T, int kd, int cio, in
 
 bool chol_fuses_gram(const lfm_ctx* ctx, int mode, const GridLayout& lay, int64_t n) {
   return ctx->knobs.gram_fuse && lay.ok && lay.T % 256 == 0 && n % 256 == 0 && n >= 1024 &&
-         s3_on(ctx) && mode != CHOL_SCHUR;
+         s3_on(ctx) && mode != CHOL_SCHUR && mode != CHOL_RESIDENT;
 }
 
 // Diagnostics: the next region of the unit trace (lfm_debug_trace) for a launch of `grid`
@@ -578,8 +578,8 @@ int chol_factor_solve(lfm_ctx* ctx, double* A, int64_t lda, int64_t n, int64_t M
   int r = ctx->parts.reserve(ctx, (size_t)nblk * sizeof(double));
   if (r) return r;
   // schedule 3 for the MLL and for the bordered inverse (gradient); the Schur-complement
-  // posterior keeps schedule 1
-  const bool s3 = s3_on(ctx) && mode != CHOL_SCHUR;
+  // posterior keeps schedule 1, and so does the resident posterior's fit, which needs L in A
+  const bool s3 = s3_on(ctx) && mode != CHOL_SCHUR && mode != CHOL_RESIDENT;
   ctx->last_sched = s3 ? 3 : 1;
   // the bordered matrix's bottom rows [I, 0]: in memory for schedule 1; schedule 3 never reads
   // them before its window reaches them (StepArgs zero_from / copy_from)
@@ -621,7 +621,7 @@ int chol_factor_solve(lfm_ctx* ctx, double* A, int64_t lda, int64_t n, int64_t M
     r = schedule3(ctx, A, lda, n, Mp, bordered, steps, fused ? gen : nullptr, &main, &zsplit);
   else
     r = schedule1(ctx, Launcher{ctx, A, lda, bordered ? 2 * Mp : Mp, bordered ? Mp : 0}, n, steps,
-                  mode != CHOL_MLL);
+                  mode == CHOL_INVERSE || mode == CHOL_SCHUR);
   if (r) return r;
   r = hip_fail(ctx, hipGetLastError(), "cholesky launch");
   if (r) return r;

@@ -172,7 +172,8 @@ const char* const kClassName[K_NCLASS] = {"tables",   "gram_grid", "gram_direct"
                                           "augment",  "potrf",     "trsm",
                                           "syrk",     "finalize",  "small_mll",
                                           "mean",     "grad",      "panel",
-                                          "syrk_side", "small_grad", "small_post"};
+                                          "syrk_side", "small_grad", "small_post",
+                                          "post_panel", "post_update"};
 
 int set_err(lfm_ctx* ctx, int code, const std::string& msg) {
   if (ctx) ctx->err = msg;

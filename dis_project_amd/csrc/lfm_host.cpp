@@ -512,4 +512,62 @@ TenancyLock::~TenancyLock() {
   if (turn_ >= 0) ::close(turn_);
 }
 
+// ------------------------------------------------- resident posterior (lfm_post.hip)
+int64_t post_default_chunk(int64_t Np) {
+  const int64_t fit = (int64_t)(POST_VT_BUDGET / ((size_t)Np * sizeof(double)));
+  return std::min(POST_CHUNK_MAX, std::max<int64_t>(fit / 128 * 128, 128));
+}
+
+ResidentPlan plan_post(int64_t n, int64_t G, int64_t m, int64_t chunk, bool want_cov) {
+  ResidentPlan P;
+  P.n = n;
+  P.Np = (n + 127) / 128 * 128;
+  P.m = m;
+  P.chunk = chunk ? chunk : post_default_chunk(P.Np);
+  auto rejected = [&](int code, const std::string& why) {
+    P.reject = code;
+    P.why = why;
+    return P;
+  };
+  if (m < 1 || G < 1 || m % G != 0)
+    return rejected(ResidentPlan::BAD_M,
+                    "m must be >= 1 and divisible by num_genes (mean_function, model.py:145-149)");
+  if (want_cov && m > P.chunk)
+    return rejected(ResidentPlan::COV_CHUNK,
+                    "the covariance needs m within one chunk: m = " + std::to_string(m) +
+                        " is above the limit of " + std::to_string(P.chunk) +
+                        " test rows (lfm_post_set_chunk; cov = NULL takes any m)");
+  if (P.chunk < 128 || P.chunk % 128 != 0)
+    return rejected(ResidentPlan::BAD_CHUNK, "the chunk must be a positive multiple of 128 rows");
+  for (int64_t q0 = 0; q0 < m; q0 += P.chunk) {
+    PostChunk c;
+    c.q0 = q0;
+    c.rows = std::min(P.chunk, m - q0);
+    c.pad_rows = (c.rows + 127) / 128 * 128;
+    c.panel_grid = (int)((c.rows + 63) / 64);
+    c.tiles = (int)(c.pad_rows / 128);
+    P.vt_rows = std::max(P.vt_rows, c.pad_rows);
+    P.chunks.push_back(c);
+  }
+  const int nblk = (int)(P.Np / 128);
+  for (int b = 0; b < nblk; b += POST_W) {
+    PostPanel s;
+    s.w = std::min(POST_W, nblk - b);
+    s.K0 = (int64_t)b * 128;
+    s.K1 = s.K0 + (int64_t)s.w * 128;
+    s.tj0 = b + s.w;
+    s.ntj = nblk - s.tj0;
+    P.panels.push_back(s);
+  }
+  P.vt_bytes = (size_t)P.vt_rows * P.Np * sizeof(double);
+  P.acc_bytes = 2 * (size_t)P.vt_rows * sizeof(double);
+  P.t_bytes = (size_t)m * 3 * sizeof(double);
+  P.out_bytes = 2 * (size_t)m * sizeof(double);
+  if (want_cov) {
+    P.cov_bytes = (size_t)m * m * sizeof(double);
+    P.cov_tiles = (int)((m + 127) / 128);
+  }
+  return P;
+}
+
 }  // namespace lfm

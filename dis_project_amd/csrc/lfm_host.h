@@ -3,7 +3,8 @@
 // schedule 3's whole launch plan (plan_s3: every unit count, grid, buffer and flag offset,
 // device-counter target and profiling figure of a call, which lfm_chol_sched.hip only reads);
 // with lfm_small_plan.h the small-problem path's LDS map, staging and buffer layouts and its
-// launch plans (plan_small_*, which lfm_small.hip and lfm_batch.hip only read).
+// launch plans (plan_small_*, which lfm_small.hip and lfm_batch.hip only read); and the resident
+// posterior's predict plan (plan_post, which lfm_post.hip only reads).
 // Plain C++ (no HIP types), so lfm_host.cpp also builds into the host sanitizer check
 // (tests/native, `make -C tests/native asan`) with g++ -fsanitize=address,undefined.
 #pragma once
@@ -186,6 +187,51 @@ S3Plan plan_s3(const std::vector<std::pair<int64_t, int>>& steps, const S3Params
 // from other inputs. Returns whether it was rebuilt.
 bool plan_s3_keep(S3Plan& kept, const std::vector<std::pair<int64_t, int>>& steps,
                   const S3Params& p);
+
+// ------------------------------------------------- resident posterior (lfm_post.hip)
+// A predict against a resident factor (lfm_post_predict_f64): the m test rows go through in
+// chunks of `chunk` rows; per chunk Vt (rows x Np, row-major) holds K(t, x) and is solved in
+// place by a right-looking sweep over super-panels of up to POST_W block columns: one panel
+// launch (64 test rows per workgroup) and, while block columns remain to the right, one update
+// launch (one workgroup per 128 x 128 tile). With the covariance the single chunk is followed by
+// one launch over the lower 128-tiles of the m x m output.
+constexpr int POST_W = 4;                                 // super-panel width, block columns
+constexpr size_t POST_VT_BUDGET = (size_t)1 << 30;        // bytes of Vt the default chunk keeps to
+constexpr int64_t POST_CHUNK_MAX = 16384;                 // rows; also the default's upper bound
+
+struct PostChunk {
+  int64_t q0 = 0, rows = 0;  // test rows [q0, q0 + rows)
+  int64_t pad_rows = 0;      // rows rounded up to 128: what the launches of this chunk touch in Vt
+  int panel_grid = 0;        // workgroups of each panel launch: 64-row slabs
+  int tiles = 0;             // 128-row tiles: the update launches' grid.x
+};
+struct PostPanel {
+  int64_t K0 = 0, K1 = 0;    // columns [K0, K1) of the factor
+  int w = 0;                 // (K1 - K0) / 128
+  int tj0 = 0, ntj = 0;      // the update: block columns [tj0, tj0 + ntj) (ntj = 0: no launch)
+};
+struct ResidentPlan {
+  enum Reject { OK = 0, BAD_M, COV_CHUNK, BAD_CHUNK };
+  int reject = OK;
+  std::string why;           // the message of a rejection
+  int64_t n = 0, Np = 0, m = 0, chunk = 0;
+  std::vector<PostChunk> chunks;
+  std::vector<PostPanel> panels;
+  int64_t vt_rows = 0;       // rows of Vt: the largest chunk's pad_rows
+  size_t vt_bytes = 0;       // vt_rows x Np doubles
+  size_t acc_bytes = 0;      // two per-row accumulators of vt_rows doubles each
+  size_t t_bytes = 0;        // the staged test inputs, m x 3
+  size_t out_bytes = 0;      // mean [m] then var [m]
+  size_t cov_bytes = 0;      // m x m (0 without the covariance)
+  int cov_tiles = 0;         // 128-tiles per side of the covariance: its grid is cov_tiles^2
+};
+// Default chunk for a factor of Np columns: the largest multiple of 128 rows, at most
+// POST_CHUNK_MAX, whose chunk x Np doubles fit POST_VT_BUDGET (at least 128)
+int64_t post_default_chunk(int64_t Np);
+// n training rows, G genes, m test rows, chunk rows per pass (0: the default). Rejections in
+// order: m < 1 or m % G != 0; the covariance with m above the chunk; a chunk that is no
+// positive multiple of 128.
+ResidentPlan plan_post(int64_t n, int64_t G, int64_t m, int64_t chunk, bool want_cov);
 
 // Readers-writer lock over one GPU's library work (lfm_ctx.hip DeviceTenancy: a schedule-3
 // factorisation exclusive, all other GPU work shared). In-process a std::shared_mutex; across

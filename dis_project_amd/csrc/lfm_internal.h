@@ -33,6 +33,8 @@ enum KClass {
   K_SIDE_SYRK,    // schedule 3: the tail of a step's trailing update on the side CUs (helper)
   K_SMALL_GRAD,   // one-workgroup-per-problem value + gradient (and the in-kernel fit)
   K_SMALL_POST,   // batched posterior predictors of the small problems (and their covariance)
+  K_POST_PANEL,   // resident posterior: multi-right-hand-side panel solve against the factor
+  K_POST_UPDATE,  // resident posterior: right-looking update of the test rows (fp64 MFMA)
   K_NCLASS
 };
 
@@ -299,7 +301,10 @@ int launch_gram_region(lfm_ctx* ctx, const GramGen& g, int64_t r0, int64_t r1, i
                        int64_t c1, double* out, int64_t ldo);
 
 // the factorisation (lfm_chol_sched.hip; its kernels: lfm_chol.hip, lfm_chol.h)
-enum CholMode { CHOL_MLL = 0, CHOL_INVERSE = 1, CHOL_SCHUR = 2 };
+// CHOL_RESIDENT: CHOL_MLL's matrix and plan, but always on schedule 1, which leaves L in A's
+// lower triangle and z in row n (schedule 3 keeps its panels in separate buffers); the
+// resident posterior's fit (lfm_post.hip)
+enum CholMode { CHOL_MLL = 0, CHOL_INVERSE = 1, CHOL_SCHUR = 2, CHOL_RESIDENT = 3 };
 // gen: the gram to fuse (lfm_api decides with chol_fuses_gram; the full gram is then NOT in A)
 int chol_factor_solve(lfm_ctx* ctx, double* A, int64_t lda, int64_t n, int64_t Mp, int negative,
                       double* d_out, int mode = CHOL_MLL, const GramGen* gen = nullptr);

@@ -242,6 +242,13 @@ class ExactLFM:
         var = cov + np.eye(mean.shape[0]) * self.jitter
         return GaussianDistribution(np.atleast_1d(mean.squeeze()), var, device=self.device)
 
+    def posterior(self, train_data, kind: str = "latent"):
+        """The predictor of ``kind`` conditioned once and kept resident for many sets of test
+        inputs (predict.Posterior): ``.predict(t)`` is latent_predict / multi_gene_predict."""
+        from .predict import Posterior
+
+        return Posterior(self, train_data, kind)
+
     def _check_kernel(self, kernel):
         # The reference passes ``model.kernel`` (objectives.py:70); any other kernel
         # object is not part of this hot path.

@@ -7,6 +7,9 @@ whole farm in one launch; this class does the same for the predictors: the train
 every problem is registered in HBM once (``lfm_batch_create``) and one
 ``lfm_batch_posterior_f64`` call evaluates every problem at its own test inputs. The assembly of
 the returned ``GaussianDistribution`` is ``ExactLFM.latent_predict`` / ``multi_gene_predict``'s.
+
+``Posterior`` is the large-N counterpart: one fitted model whose factor stays resident in HBM
+(``lfm_post_create``) and is evaluated at many sets of test inputs (``lfm_post_predict_f64``).
 """
 
 from __future__ import annotations
@@ -153,3 +156,112 @@ class BatchPredictor:
 
     def close(self):
         self._ev.close()
+
+
+# ------------------------------------------------------------------ the resident posterior
+def _destroy_post(lib, handle):
+    lib.lfm_post_destroy(handle)
+
+
+class Posterior:
+    """One large fitted model, conditioned once and evaluated at many sets of test inputs.
+
+    ``latent_predict`` / ``multi_gene_predict`` (src/model.py:420-514) condition on the training
+    data at every call; the notebooks then evaluate the fitted model at several sets of test
+    times. ``Posterior(model, train_data, kind)`` applies ``dataset_3d`` and that predictor's
+    diagonal (``kind="latent"``: ``jitter``; ``kind="gene"``: ``obs_stddev**2``), factors S once
+    (``lfm_post_create``: the factor stays in HBM) and every ``predict`` / ``marginals`` is one
+    ``lfm_post_predict_f64``: a multi-right-hand-side solve against the resident factor. The
+    model's hyperparameters are read at construction. ``status`` holds the fit's code
+    (LFM_E_NOT_PD: every output is NaN, as under JAX)."""
+
+    KINDS = ("latent", "gene")
+
+    def __init__(self, model, train_data, kind: str = "latent", ctx=None):
+        import ctypes
+        import weakref
+
+        from .dataset import dataset_3d
+
+        if kind not in self.KINDS:
+            raise ValueError('kind must be "latent" or "gene"')
+        x, y, variances = dataset_3d(train_data)
+        x = as_f64(x).reshape(-1, 3)
+        y = as_f64(y).reshape(-1)
+        v = as_f64(variances).reshape(-1)
+        self.num_genes = int(model.num_genes)
+        if x.shape[0] < 1 or x.shape[0] % self.num_genes != 0:
+            raise ValueError(f"n = {x.shape[0]} training rows is not a positive multiple of "
+                             f"num_genes = {self.num_genes} (mean_function, model.py:145-149)")
+        if y.shape[0] != x.shape[0] or v.shape[0] != x.shape[0]:
+            raise ValueError("x, y and the variances must have one row per observation")
+        self.kind = kind
+        self.jitter = float(model.jitter)
+        self.n = x.shape[0]
+        diag_add = self.jitter if kind == "latent" else float(model.obs_stddev) ** 2
+        self.ctx = ctx or model.ctx
+        hp = model.hyp()
+        handle = ctypes.c_void_p()
+        rc = self.ctx.lib.lfm_post_create(self.ctx.handle, dptr(x), dptr(y), self.n, dptr(v),
+                                          float(diag_add), hp.ref, ctypes.byref(handle))
+        self.status = self.ctx.check(rc, allow_not_pd=True)
+        self._handle = handle if rc == _lib.LFM_OK else None
+        # the fallback of close(): the context (kept alive by the finaliser) outlives the handle
+        self._final = (weakref.finalize(self, _destroy_post, self.ctx.lib, handle)
+                       if self._handle else None)
+        self._keep = self.ctx
+
+    def _test(self, test_inputs):
+        t = as_f64(test_inputs)
+        if t.ndim != 2 or t.shape[1] != 3:
+            raise ValueError("test inputs must be [m, 3]")
+        if t.shape[0] < 1 or t.shape[0] % self.num_genes != 0:
+            raise ValueError(f"m = {t.shape[0]} test rows is not a positive multiple of "
+                             f"num_genes = {self.num_genes} (mean_function, model.py:145-149)")
+        return t
+
+    def set_chunk(self, rows: int = 0):
+        """Test rows solved per pass (a multiple of 128; 0: the default)."""
+        if self._handle:
+            self.ctx.check(self.ctx.lib.lfm_post_set_chunk(self._handle, int(rows)))
+
+    def _predict(self, t, want_cov):
+        m = t.shape[0]
+        mean = np.full(m, np.nan)
+        var = np.full(m, np.nan)
+        cov = np.full((m, m), np.nan) if want_cov else None
+        if self._handle:  # a failed fit: NaN, as under JAX
+            self.ctx.check(self.ctx.lib.lfm_post_predict_f64(
+                self.ctx.handle, self._handle, dptr(t), m, dptr(mean), dptr(var),
+                dptr(cov) if want_cov else None))
+        return mean, var, cov
+
+    def marginals(self, test_inputs):
+        """(mean, var), var the diagonal of ``predict``'s scale, for any m: nothing of size m^2
+        is formed (what the plots of utils.py:144-172 read)."""
+        mean, var, _ = self._predict(self._test(test_inputs), False)
+        if self.kind == "latent":
+            return mean, (var + self.jitter) + self.jitter
+        return mean, var + self.jitter
+
+    def predict(self, test_inputs):
+        """The ``GaussianDistribution`` of ``ExactLFM.latent_predict`` (kind "latent": the scale
+        is diagonal, model.py:420-465, so only the variances are computed) or
+        ``multi_gene_predict`` (kind "gene": the dense covariance, model.py:467-514)."""
+        from .distributions import GaussianDistribution
+
+        t = self._test(test_inputs)
+        m = t.shape[0]
+        if self.kind == "latent":
+            mean, var, _ = self._predict(t, False)
+            scale = np.diag(var + self.jitter) + np.eye(m) * self.jitter
+        else:
+            mean, _, cov = self._predict(t, True)
+            scale = cov + np.eye(m) * self.jitter
+        return GaussianDistribution(mean, scale, device=self.ctx.device)
+
+    def close(self):
+        if self._final is not None:
+            self._final()  # runs lfm_post_destroy once
+            self._final = None
+        self._handle = None

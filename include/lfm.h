@@ -272,6 +272,46 @@ int lfm_batch_posterior_f64(lfm_ctx* ctx, lfm_batch* batch, const double* hyp,
                             const double* diag_vec, const double* diag_add, const int64_t* m,
                             const double* t, double* mean, double* var, double* cov, int* status);
 
+/* ------------- resident posterior: factor a large model once, predict many times */
+/* latent_predict / multi_gene_predict (model.py:420-514) condition on the training data once;
+ * the notebooks then evaluate the fitted model at several sets of test times. lfm_posterior_f64
+ * pays the whole N^3 / 3 factorisation on every call; a handle pays it once.
+ *
+ * lfm_post_create: S = K(x,x) + diag(diag_vec) + diag_add I factored once; L and
+ * z = L^{-1} (y - m(x)) stay in HBM, in memory the handle owns (not the ctx workspace). x [n x 3],
+ * y [n], diag_vec [n] (may be NULL) and hyp are host pointers, copied: the caller may free them.
+ * n and num_genes as lfm_posterior_f64. Not PD: LFM_E_NOT_PD, *out = NULL. The handle needs
+ * about 8 (n + 128)^2 bytes of device memory.
+ *
+ * lfm_post_predict_f64: mean [m] and cov [m x m] as lfm_posterior_f64 defines them, var [m] the
+ * diagonal of cov. var or cov may be NULL, not both; m >= 1 and m % num_genes == 0, any m (no
+ * n + m limit); t [m x 3] as lfm_batch_posterior_f64's.
+ *   Marginals only (cov == NULL): no off-diagonal K(t,t) entry is evaluated and nothing of size
+ *     m^2 is allocated. The test rows go through in chunks of the handle's chunk size; per chunk
+ *     the solve works in a chunk x round_up(n, 128) buffer of doubles. The default chunk is the
+ *     largest multiple of 128 rows, at most 16384, that keeps that buffer within 1 GiB.
+ *   Covariance (cov != NULL): m must fit in one chunk, else LFM_E_ARG with a message naming the
+ *     limit. cov is dense row-major and exactly symmetric. When both are given, var is
+ *     diag(cov) bit for bit.
+ *   Independence of the split: a test point's variance and its row of K(t,x) L^{-T} depend on
+ *     its own row of t alone, not on m or on the chunk size. The mean depends on the point's
+ *     index and on m as well (mean_function's block position), not on the chunk size. The same
+ *     inputs give the same bits: no atomics and no device-side waits. Synchronous; holds the
+ *     device's lock shared.
+ * lfm_post_set_chunk: test rows solved per pass (0 restores the default); a multiple of 128, else
+ *   LFM_E_ARG (the message goes to the ctx that created the handle).
+ * Handle rules: a handle belongs to the device of the ctx that created it, which must outlive it,
+ * and to one host thread at a time. A predict with a ctx of another device is LFM_E_ARG. Other
+ * calls on the ctx between predicts (an MLL of a larger n, a gradient, lfm_posterior_f64) do not
+ * disturb the handle. lfm_post_destroy(NULL) is LFM_E_ARG. */
+typedef struct lfm_post lfm_post;
+int lfm_post_create(lfm_ctx* ctx, const double* x, const double* y, int64_t n,
+                    const double* diag_vec, double diag_add, const lfm_hyp* hyp, lfm_post** out);
+int lfm_post_destroy(lfm_post* post);
+int lfm_post_set_chunk(lfm_post* post, int64_t rows);
+int lfm_post_predict_f64(lfm_ctx* ctx, lfm_post* post, const double* t, int64_t m, double* mean,
+                         double* var, double* cov);
+
 /* ------------------- GaussianDistribution(loc, scale).log_prob(y) (gpjax 0.8.2) */
 /* scale is a dense SPD n x n (row-major, leading dim lds; lower triangle read). */
 int lfm_log_prob_f64(lfm_ctx* ctx, const double* loc, const double* scale, int64_t n,
