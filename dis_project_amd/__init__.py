@@ -7,9 +7,11 @@ likelihood (src/objectives.py), on hand-written gfx950 HIP kernels behind a ctyp
 from ._lib import LfmError, device_count, get_context, load_library  # noqa: F401
 from .dataset import Dataset, SyntheticP53Data, dataset_3d  # noqa: F401
 from .distributions import GaussianDistribution  # noqa: F401
+from .farm import MidBatchEvaluator  # noqa: F401
 from .model import ExactLFM  # noqa: F401
 from .objectives import CustomConjMLL  # noqa: F401
 from .predict import BatchPredictor, Posterior  # noqa: F401
+from .trainer import MidBatchTrainer  # noqa: F401
 
 __all__ = [
     "BatchPredictor",
@@ -18,6 +20,8 @@ __all__ = [
     "ExactLFM",
     "GaussianDistribution",
     "LfmError",
+    "MidBatchEvaluator",
+    "MidBatchTrainer",
     "Posterior",
     "SyntheticP53Data",
     "dataset_3d",

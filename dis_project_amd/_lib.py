@@ -141,6 +141,11 @@ PRODUCT_SIGNATURES = [
       _dptr]),
     ("lfm_batch_posterior_f64", c_int,
      [_c_ctx, c_void_p, _dptr, _dptr, _dptr, _dptr, _dptr, _dptr, _dptr, _dptr, _dptr]),
+    ("lfm_mbatch_create", c_int, [_c_ctx, c_int64, POINTER(LfmProblem), POINTER(c_void_p)]),
+    ("lfm_mbatch_destroy", c_int, [c_void_p]),
+    ("lfm_mbatch_hyp_size", c_int, [c_void_p, POINTER(c_int64)]),
+    ("lfm_mbatch_mll_f64", c_int, [_c_ctx, c_void_p, _dptr, c_int, _dptr, _dptr]),
+    ("lfm_mbatch_mll_grad_f64", c_int, [_c_ctx, c_void_p, _dptr, c_int, _dptr, _dptr, _dptr]),
     ("lfm_post_create", c_int,
      [_c_ctx, _dptr, _dptr, c_int64, _dptr, c_double, POINTER(LfmHyp), POINTER(c_void_p)]),
     ("lfm_post_destroy", c_int, [c_void_p]),
@@ -197,7 +202,8 @@ DIAG_SIGNATURES = [
 # kernel classes in lfm_profile_read order (lfm_internal.h KClass)
 KCLASSES = ["tables", "gram_grid", "gram_direct", "augment", "potrf", "trsm", "syrk",
             "finalize", "small_mll", "mean", "grad", "panel", "syrk_side", "small_grad",
-            "small_post", "post_panel", "post_update"]
+            "small_post", "post_panel", "post_update", "mid_fill", "mid_column", "mid_inverse",
+            "mid_pairs", "mid_finish"]
 
 _lib = None
 _diag = None

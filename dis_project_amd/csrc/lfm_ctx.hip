@@ -173,7 +173,9 @@ const char* const kClassName[K_NCLASS] = {"tables",   "gram_grid", "gram_direct"
                                           "syrk",     "finalize",  "small_mll",
                                           "mean",     "grad",      "panel",
                                           "syrk_side", "small_grad", "small_post",
-                                          "post_panel", "post_update"};
+                                          "post_panel", "post_update", "mid_fill",
+                                          "mid_column", "mid_inverse", "mid_pairs",
+                                          "mid_finish"};
 
 int set_err(lfm_ctx* ctx, int code, const std::string& msg) {
   if (ctx) ctx->err = msg;

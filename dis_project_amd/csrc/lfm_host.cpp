@@ -570,4 +570,85 @@ ResidentPlan plan_post(int64_t n, int64_t G, int64_t m, int64_t chunk, bool want
   return P;
 }
 
+// ------------------------------------------------- mid-size resident batch (lfm_mid.hip)
+namespace {
+int64_t even(int64_t d) { return (d + 1) / 2 * 2; }
+}  // namespace
+
+int64_t mid_problem_doubles(int64_t n) {
+  const int64_t nb = mid_blocks((int)n), Mp = nb * MID_TILE;
+  return even(3 * n) + even(n) + 3 * Mp * Mp + nb * MID_TILE * MID_TILE +
+         even((int64_t)mid_tiles((int)nb) * MID_PART);
+}
+
+MidPlan plan_mid(const std::vector<MidShape>& shapes) {
+  MidPlan P;
+  auto rejected = [&](int code, const std::string& why) {
+    P.reject = code;
+    P.why = why;
+    return P;
+  };
+  if (shapes.empty()) return rejected(MidPlan::EMPTY, "lfm_mbatch: no problems");
+  if ((int64_t)shapes.size() > MID_MAX_PROBS)
+    return rejected(MidPlan::TOO_MANY, "lfm_mbatch: at most " + std::to_string(MID_MAX_PROBS) +
+                                           " problems per batch");
+  for (size_t q = 0; q < shapes.size(); ++q) {
+    const MidShape& s = shapes[q];
+    if (s.n < 1 || s.n > MID_MAX_N)
+      return rejected(MidPlan::BAD_N, "lfm_mbatch: problem " + std::to_string(q) + " has n = " +
+                                          std::to_string(s.n) + ", outside [1, " +
+                                          std::to_string(MID_MAX_N) + "] (LFM_MID_MAX_N)");
+    if (s.G < 1 || s.G > s.n || s.n % s.G != 0)
+      return rejected(MidPlan::BAD_G, "lfm_mbatch: problem " + std::to_string(q) +
+                                          " needs num_genes in [1, n] dividing n "
+                                          "(mean_function, model.py:145-149)");
+  }
+  P.nprob = (int64_t)shapes.size();
+  for (const MidShape& s : shapes) P.nhyp += 3 * s.G + 3;
+  P.hyp = 0;
+  P.out = even(P.nhyp);
+  P.grad = P.out + even(P.nprob);
+  int64_t at = P.grad + even(P.nhyp);
+  int64_t hv = 0, hs = P.nhyp - 3 * P.nprob;  // the vectors first, then the scalars
+  P.probs.reserve(shapes.size());
+  for (const MidShape& s : shapes) {
+    MidProb m{};
+    m.n = (int)s.n;
+    m.G = (int)s.G;
+    m.nb = mid_blocks(m.n);
+    m.Mp = m.nb * MID_TILE;
+    m.hv = hv;
+    m.hs = hs;
+    hv += 3 * s.G;
+    hs += 3;
+    const int64_t mat = (int64_t)m.Mp * m.Mp;
+    m.x = at;
+    m.y = m.x + even(3 * s.n);
+    m.S = m.y + even(s.n);
+    m.L = m.S + mat;
+    m.W = m.L + mat;
+    m.dinv = m.W + mat;
+    m.part = m.dinv + (int64_t)m.nb * MID_TILE * MID_TILE;
+    at = m.part + even((int64_t)mid_tiles(m.nb) * MID_PART);
+    P.maxnb = std::max(P.maxnb, m.nb);
+    P.probs.push_back(m);
+  }
+  P.maxtiles = mid_tiles(P.maxnb);
+  P.doubles = at;
+  P.status = (size_t)at * sizeof(double);
+  P.table = P.status + ((size_t)P.nprob * sizeof(int) + 15) / 16 * 16;
+  P.bytes = P.table + (size_t)P.nprob * sizeof(MidProb);
+  // the launches: their count depends on the largest problem alone
+  const unsigned gx = (unsigned)P.nprob;
+  P.value.push_back({MID_FILL, 0, gx, (unsigned)P.maxtiles});
+  for (int k = 0; k < P.maxnb; ++k) P.value.push_back({MID_COLUMN, k, gx, (unsigned)(P.maxnb - k)});
+  P.value.push_back({MID_VALUE, 0, gx, 1u});
+  P.value_grad = P.value;  // the same launches first: the same value bits
+  P.value_grad.push_back({MID_INVERT, 0, gx, (unsigned)P.maxnb});
+  P.value_grad.push_back({MID_SINV, 0, gx, (unsigned)P.maxtiles});
+  P.value_grad.push_back({MID_PAIRS, 0, gx, (unsigned)P.maxtiles});
+  P.value_grad.push_back({MID_GRAD, 0, gx, 1u});
+  return P;
+}
+
 }  // namespace lfm

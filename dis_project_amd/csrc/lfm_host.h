@@ -4,7 +4,8 @@
 // device-counter target and profiling figure of a call, which lfm_chol_sched.hip only reads);
 // with lfm_small_plan.h the small-problem path's LDS map, staging and buffer layouts and its
 // launch plans (plan_small_*, which lfm_small.hip and lfm_batch.hip only read); and the resident
-// posterior's predict plan (plan_post, which lfm_post.hip only reads).
+// posterior's predict plan (plan_post, which lfm_post.hip only reads); with lfm_mid_plan.h the
+// mid-size resident batch's arena and launch plan (plan_mid, which lfm_mid.hip only reads).
 // Plain C++ (no HIP types), so lfm_host.cpp also builds into the host sanitizer check
 // (tests/native, `make -C tests/native asan`) with g++ -fsanitize=address,undefined.
 #pragma once
@@ -19,6 +20,7 @@
 #include <utility>
 #include <vector>
 
+#include "lfm_mid_plan.h"    // the mid-size resident batch's layout and plan (plan_mid)
 #include "lfm_small_plan.h"  // LFM_HD; the small-problem path's layout and plans
 
 namespace lfm {

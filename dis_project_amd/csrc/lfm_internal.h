@@ -35,6 +35,11 @@ enum KClass {
   K_SMALL_POST,   // batched posterior predictors of the small problems (and their covariance)
   K_POST_PANEL,   // resident posterior: multi-right-hand-side panel solve against the factor
   K_POST_UPDATE,  // resident posterior: right-looking update of the test rows (fp64 MFMA)
+  K_MID_FILL,     // mid-size batch: every problem's augmented matrix from the hyperparameters
+  K_MID_COLUMN,   // mid-size batch: one block column of every problem's factor (fp64 MFMA)
+  K_MID_INVERSE,  // mid-size batch: X = L^{-1} and S^{-1} = X^T X (fp64 MFMA)
+  K_MID_PAIRS,    // mid-size batch: W-weighted kernel derivatives per lower tile
+  K_MID_FINISH,   // mid-size batch: the values / the gradients joined in a fixed order
   K_NCLASS
 };
 

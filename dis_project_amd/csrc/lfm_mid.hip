@@ -1,0 +1,677 @@
+// lfm_mid.hip — the resident batch of mid-size problems (lfm_mbatch_*, 1 <= n <= 1024): every
+// problem's MLL, and its MLL and gradient, in a number of launches that depends on the largest
+// problem alone. CustomConjMLL.step (src/objectives.py:21-78) and jax.value_and_grad of it
+// (src/trainer.py:126) for a set of independent (model, dataset) problems, as
+// src/notebook.py:33-75 trains them, above the one-workgroup limit of lfm_batch.
+//
+// Every problem has its own padded augmented matrix in the handle's arena (lfm_mid_plan.h: the
+// layout, the grids and the launch list all come from plan_mid), in 64 x 64 tiles. A launch's
+// grid is (problem, unit); a workgroup whose problem has no such unit exits at once.
+//   mid_fill_kernel    S's lower tiles from the packed hyperparameters (kernel_ref per pair),
+//                      the residual row n and the identity rows past it
+//   mid_column_kernel  left-looking factorisation, one launch per block column k, unit = row
+//                      block i >= k: the update from columns < k of block (i, k) and of the
+//                      diagonal block (fp64 MFMA), the diagonal block's factor and inverse in LDS
+//                      (every workgroup of the column redundantly: no workgroup waits for
+//                      another), then X = A_ik L_kk^{-T}. A non-positive pivot goes to the
+//                      problem's status word; later launches skip the problem.
+//   mid_value_kernel   logdet and z^T z in a fixed order -> the value
+//   mid_invert_kernel  X = L^{-1} by block columns (row n of it is -a, a = S^{-1} r)
+//   mid_sinv_kernel    S^{-1} = X^T X over the lower tiles, depth n
+//   mid_pairs_kernel   grad_pairs_kernel's work per lower tile with W = a a^T - S^{-1}: its
+//                      per-row / per-column partial sums go to the tile's own scratch slots
+//   mid_grad_kernel    joins the partials in a fixed order; tr(W), the mean terms, the sign
+// No atomics and no device-side waits: consecutive launches on one stream are the only ordering,
+// so a problem's bits depend on its own data and hyperparameters alone.
+#include <cstring>
+#include <memory>
+
+#include "lfm_api_internal.h"
+#include "lfm_chol_dev.h"
+#include "lfm_dual.h"
+
+using namespace lfm;
+
+// The handle: the plan, the device arena it lays out, and a pinned buffer for a call's packed
+// hyperparameters and results (hyp | out | grad | status words).
+struct lfm_mbatch {
+  int device = 0;
+  MidPlan plan;
+  char* dmem = nullptr;
+  double* hbuf = nullptr;
+  size_t h_out = 0, h_grad = 0, h_status = 0;  // doubles into hbuf
+};
+
+namespace lfm {
+
+namespace {
+
+constexpr int TS = MID_TILE, LD = TS + LDP;
+typedef double (*Tile)[LD];
+constexpr size_t MID_LDS = (3 * (size_t)TS * LD + 2 * TS) * sizeof(double);
+
+struct MidArgs {
+  const MidProb* probs;
+  double* base;  // the arena; the packed hyperparameters at its start
+  int* status;   // [nprob]: 0, or 1 + the first failing pivot
+  int64_t out, grad;
+  int negative, k;
+};
+
+// A 64 x 64 tile at g (row stride ld) into LDS, as it is or transposed; rows >= rows read as 0.
+__device__ __forceinline__ void stage(Tile s, const double* __restrict__ g, int64_t ld, bool tr,
+                                      int rows = TS) {
+  const int tid = threadIdx.x;
+#pragma unroll 4
+  for (int e = 0; e < 16; ++e) {
+    const int idx = tid + 256 * e, r = idx >> 6, c = idx & 63;
+    const double v = r < rows ? g[r * ld + c] : 0.0;
+    if (tr) s[c][r] = v;
+    else s[r][c] = v;
+  }
+}
+
+// acc[jr][q] (C[16 w + (lane >> 4) + 4 q][16 jr + (lane & 15)], wave w) += sum_k sA[i][k] sB[j][k]
+__device__ __forceinline__ void mma_nt(double4v (&acc)[4], Tile sA, Tile sB) {
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, li = lane & 15, lk = lane >> 4;
+#pragma unroll 4
+  for (int kk = 0; kk < TS; kk += 4) {
+    const double a = sA[16 * w + li][kk + lk];
+#pragma unroll
+    for (int jr = 0; jr < 4; ++jr) acc[jr] = mfma16(a, sB[16 * jr + li][kk + lk], acc[jr]);
+  }
+}
+
+__device__ __forceinline__ void acc_zero(double4v (&acc)[4]) {
+#pragma unroll
+  for (int jr = 0; jr < 4; ++jr) acc[jr] = double4v{0, 0, 0, 0};
+}
+
+// f(row, column, value&) over the thread's 16 accumulator elements
+template <typename F>
+__device__ __forceinline__ void acc_each(double4v (&acc)[4], F f) {
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, li = lane & 15, lk = lane >> 4;
+#pragma unroll
+  for (int jr = 0; jr < 4; ++jr)
+#pragma unroll
+    for (int q = 0; q < 4; ++q) f(16 * w + lk + 4 * q, 16 * jr + li, acc[jr][q]);
+}
+
+__device__ __forceinline__ HypDev mid_hyp(const MidProb& P, const double* hyp) {
+  const double* v = hyp + P.hv;
+  return HypDev{v, v + P.G, v + 2 * P.G, P.G, hyp[P.hs]};
+}
+
+// ------------------------------------------------------------------ fill
+__global__ __launch_bounds__(256) void mid_fill_kernel(MidArgs a) {
+  const int p = blockIdx.x, tid = threadIdx.x;
+  const MidProb P = a.probs[p];
+  if ((int)blockIdx.y >= mid_tiles(P.nb)) return;
+  int I, J;
+  mid_tile_of((int)blockIdx.y, &I, &J);
+  if (blockIdx.y == 0 && tid == 0) a.status[p] = 0;
+  const HypDev h = mid_hyp(P, a.base);
+  const double sd = a.base[P.hs + 1], jit = a.base[P.hs + 2], s2 = sd * sd;
+  const double* x = a.base + P.x;
+  const double* y = a.base + P.y;
+  double* S = a.base + P.S;
+  const int n = P.n, c = TS * J + (tid & 63);
+  const int64_t bs = n / P.G;
+  double tb = 0.0, gb = 0.0, fb = 0.0;
+  if (c < n) {
+    tb = x[c * 3];
+    gb = x[c * 3 + 1];
+    fb = x[c * 3 + 2];
+  }
+  for (int e = 0; e < 16; ++e) {
+    const int i = TS * I + (tid >> 6) + 4 * e;
+    double v;
+    if (i < n && c <= i) {
+      v = kernel_ref(h, x[i * 3], x[i * 3 + 1], x[i * 3 + 2], tb, gb, fb);
+      if (i == c) v = (v + jit) + s2;  // (K + jitter I) + sigma^2 I, objectives.py:71-72
+    } else if (i == n && c < n) {
+      v = y[c] - mean_at(h, x, c, bs);
+    } else {
+      v = (i == c) ? 1.0 : 0.0;
+    }
+    S[(int64_t)i * P.Mp + c] = v;
+  }
+}
+
+// ------------------------------------------------------------------ column k
+// The Cholesky factor of the block in sA (lower part read) and its inverse into sR, both in
+// place, over the block's first nlim columns (the columns past them are identity columns of
+// the augmented matrix: the residual row has a unit pivot). 256 threads: row tid >> 2, the
+// row's elements dealt round-robin to its four threads; per column two barriers and, between
+// them, one round of independent LDS loads (a step is LDS latency, not arithmetic). Row j of
+// the inverse stays unscaled until the end (the rows below take it times 1 / L_jj). sdiag:
+// 2 x 64 doubles. Returns the first column whose pivot is not positive, or -1.
+__device__ int factor_invert(Tile sA, Tile sR, double* sdiag, int nlim) {
+  const int tid = threadIdx.x, i = tid >> 2, q = tid & 3;
+  double* sinv = sdiag + TS;
+  for (int e = 0; e < 16; ++e) {
+    const int idx = tid + 256 * e, r = idx >> 6, c = idx & 63;
+    sR[r][c] = r == c ? 1.0 : 0.0;
+  }
+  if (tid < TS) {
+    sdiag[tid] = 1.0;
+    sinv[tid] = 1.0;
+  }
+  int fail = -1;
+  for (int j = 0; j < nlim; ++j) {
+    __syncthreads();
+    const double d = sA[j][j];
+    if (!(d > 0.0)) {
+      fail = j;
+      break;
+    }
+    const double inv = 1.0 / sqrt(d);
+    if (i > j && q == 0) sA[i][j] *= inv;
+    if (i == j && q == 0) {
+      sdiag[j] = d * inv;
+      sinv[j] = inv;
+    }
+    __syncthreads();
+    if (i > j) {
+      const double lij = sA[i][j], lr = lij * inv;
+      double m[16], t[16];
+#pragma unroll
+      for (int u = 0; u < 16; ++u) {
+        const int c = q + 4 * u;
+        const bool inA = c > j && c <= i && c < nlim, inR = c <= j;
+        m[u] = inA ? sA[c][j] : (inR ? sR[j][c] : 0.0);
+        t[u] = inA ? sA[i][c] : (inR ? sR[i][c] : 0.0);
+      }
+#pragma unroll
+      for (int u = 0; u < 16; ++u) {
+        const int c = q + 4 * u;
+        const bool inA = c > j && c <= i && c < nlim, inR = c <= j;
+        if (inA) sA[i][c] = t[u] - lij * m[u];
+        else if (inR) sR[i][c] = t[u] - lr * m[u];
+      }
+    }
+  }
+  __syncthreads();
+  if (fail < 0) {
+    for (int e = 0; e < 16; ++e) {
+      const int idx = tid + 256 * e, r = idx >> 6, c = idx & 63;
+      if (c > r) sA[r][c] = 0.0;
+      else if (c == r) sA[r][c] = sdiag[r];
+      if (c <= r) sR[r][c] *= sinv[r];
+    }
+    __syncthreads();
+  }
+  return fail;
+}
+
+__global__ __launch_bounds__(256) void mid_column_kernel(MidArgs a) {
+  extern __shared__ __attribute__((aligned(16))) double sm[];
+  Tile sA = reinterpret_cast<Tile>(sm), sB = sA + TS, sR = sB + TS;
+  double* sdiag = sm + 3 * TS * LD;
+  const int p = blockIdx.x, k = a.k, i = k + (int)blockIdx.y;
+  const MidProb P = a.probs[p];
+  if (i >= P.nb || a.status[p] != 0) return;
+  const int64_t ld = P.Mp;
+  const double* S = a.base + P.S;
+  double* L = a.base + P.L;
+  double4v accC[4], accD[4];
+  acc_zero(accC);
+  acc_zero(accD);
+  for (int j = 0; j < k; ++j) {
+    __syncthreads();
+    if (i > k) stage(sA, L + (int64_t)i * TS * ld + j * TS, ld, false);
+    stage(sB, L + (int64_t)k * TS * ld + j * TS, ld, false);
+    __syncthreads();
+    if (i > k) mma_nt(accC, sA, sB);
+    mma_nt(accD, sB, sB);
+  }
+  __syncthreads();
+  // the updated diagonal block; the columns from the residual row's on are identity columns
+  const int nloc = P.n - k * TS, nlim = nloc < TS ? (nloc > 0 ? nloc : 0) : TS;
+  const double* Skk = S + (int64_t)k * TS * ld + k * TS;
+  acc_each(accD, [&](int r, int c, double v) {
+    sA[r][c] = c < nlim ? Skk[r * ld + c] - v : (r == c ? 1.0 : 0.0);
+  });
+  __syncthreads();
+  const int fail = factor_invert(sA, sR, sdiag, nlim);
+  if (fail >= 0) {
+    if (i == k && threadIdx.x == 0) a.status[p] = 1 + k * TS + fail;
+    return;
+  }
+  if (i == k) {
+    double* Lkk = L + (int64_t)k * TS * ld + k * TS;
+    double* Dk = a.base + P.dinv + (int64_t)k * TS * TS;
+    for (int e = 0; e < 16; ++e) {
+      const int idx = threadIdx.x + 256 * e, r = idx >> 6, c = idx & 63;
+      Lkk[r * ld + c] = sA[r][c];
+      Dk[r * TS + c] = sR[r][c];
+    }
+    return;
+  }
+  // X = (A_ik - update) L_kk^{-T}
+  const double* Sik = S + (int64_t)i * TS * ld + k * TS;
+  acc_each(accC, [&](int r, int c, double v) { sB[r][c] = Sik[r * ld + c] - v; });
+  __syncthreads();
+  acc_zero(accC);
+  mma_nt(accC, sB, sR);
+  double* Lik = L + (int64_t)i * TS * ld + k * TS;
+  acc_each(accC, [&](int r, int c, double v) { Lik[r * ld + c] = v; });
+}
+
+// ------------------------------------------------------------------ value
+// sum over the workgroup (256 threads) in a fixed order; red: 4 doubles of LDS
+__device__ __forceinline__ double block_sum(double v, double* red) {
+  v = wave_sum(v);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return ((red[0] + red[1]) + red[2]) + red[3];
+}
+
+__global__ __launch_bounds__(256) void mid_value_kernel(MidArgs a) {
+  __shared__ double red[4];
+  const int p = blockIdx.x, tid = threadIdx.x;
+  const MidProb P = a.probs[p];
+  const double* L = a.base + P.L;
+  const int64_t ld = P.Mp;
+  const bool failed = a.status[p] != 0;
+  double q = 0.0, lg = 0.0;
+  if (!failed)
+    for (int c = tid; c < P.n; c += 256) {
+      const double z = L[(int64_t)P.n * ld + c];
+      q += z * z;
+      lg += log(L[(int64_t)c * ld + c]);
+    }
+  const double Q = block_sum(q, red), LG = block_sum(lg, red);
+  if (tid == 0) {
+    const double two_pi = 6.283185307179586476925;
+    double mll = -0.5 * ((double)P.n * log(two_pi) + 2.0 * LG + Q);
+    mll *= a.negative ? -1.0 : 1.0;
+    a.base[a.out + p] = failed ? __builtin_nan("") : mll;
+  }
+}
+
+// ------------------------------------------------------------------ X = L^{-1}
+// Block column c of X into S's tiles (i, c), i >= c, top down:
+//   X_cc = L_cc^{-1},   X_ic = -L_ii^{-1} sum_{c <= m < i} L_im X_mc.
+// The tiles this workgroup wrote above are the ones it reads back (workgroup barrier between).
+__global__ __launch_bounds__(256) void mid_invert_kernel(MidArgs a) {
+  extern __shared__ __attribute__((aligned(16))) double sm[];
+  Tile sA = reinterpret_cast<Tile>(sm), sB = sA + TS;
+  const int p = blockIdx.x, c = blockIdx.y;
+  const MidProb P = a.probs[p];
+  if (c >= P.nb || a.status[p] != 0) return;
+  const int64_t ld = P.Mp;
+  const double* L = a.base + P.L;
+  const double* Di = a.base + P.dinv;
+  double* X = a.base + P.S;
+  for (int e = 0; e < 16; ++e) {
+    const int idx = threadIdx.x + 256 * e, r = idx >> 6, cc = idx & 63;
+    X[((int64_t)c * TS + r) * ld + c * TS + cc] = Di[(int64_t)c * TS * TS + r * TS + cc];
+  }
+  for (int i = c + 1; i < P.nb; ++i) {
+    double4v acc[4];
+    acc_zero(acc);
+    for (int m = c; m < i; ++m) {
+      __syncthreads();  // also: the tile (m, c) written above is visible to the whole workgroup
+      stage(sA, L + (int64_t)i * TS * ld + m * TS, ld, false);
+      stage(sB, X + (int64_t)m * TS * ld + c * TS, ld, true);
+      __syncthreads();
+      mma_nt(acc, sA, sB);
+    }
+    __syncthreads();
+    acc_each(acc, [&](int r, int cc, double v) { sB[cc][r] = v; });
+    stage(sA, Di + (int64_t)i * TS * TS, TS, false);
+    __syncthreads();
+    acc_zero(acc);
+    mma_nt(acc, sA, sB);
+    double* Xic = X + (int64_t)i * TS * ld + c * TS;
+    acc_each(acc, [&](int r, int cc, double v) { Xic[r * ld + cc] = -v; });
+  }
+}
+
+// ------------------------------------------------------------------ S^{-1} = X^T X
+// Lower tile (I, J): sum over the block rows m >= I of X_mI^T X_mJ, the rows from n on left out
+// (row n of X is -a; the rows past it are identity rows).
+__global__ __launch_bounds__(256) void mid_sinv_kernel(MidArgs a) {
+  extern __shared__ __attribute__((aligned(16))) double sm[];
+  Tile sA = reinterpret_cast<Tile>(sm), sB = sA + TS;
+  const int p = blockIdx.x;
+  const MidProb P = a.probs[p];
+  if ((int)blockIdx.y >= mid_tiles(P.nb) || a.status[p] != 0) return;
+  int I, J;
+  mid_tile_of((int)blockIdx.y, &I, &J);
+  const int64_t ld = P.Mp;
+  const double* X = a.base + P.S;
+  double4v acc[4];
+  acc_zero(acc);
+  for (int m = I; m < P.nb; ++m) {
+    const int rows = P.n - m * TS;
+    if (rows <= 0) break;
+    __syncthreads();
+    stage(sA, X + (int64_t)m * TS * ld + I * TS, ld, true, rows);
+    stage(sB, X + (int64_t)m * TS * ld + J * TS, ld, true, rows);
+    __syncthreads();
+    mma_nt(acc, sA, sB);
+  }
+  double* W = a.base + P.W + (int64_t)I * TS * ld + J * TS;
+  acc_each(acc, [&](int r, int c, double v) { W[r * ld + c] = v; });
+}
+
+// ------------------------------------------------------------------ pairs
+// Tile (I, J) of 1/2 tr(W dS / d theta), W = a a^T - S^{-1}: one thread per column, 16 rows
+// each (wave w the rows w, w + 4, ...). Per pair the kernel's derivatives come from kernel_grad
+// (lfm_dual.h), weighted by W (x 1/2 on the diagonal). A row's sums over the tile's columns and
+// a column's over its rows go to the tile's MID_PART scratch slots, d l last.
+__global__ __launch_bounds__(256) void mid_pairs_kernel(MidArgs a) {
+  __shared__ double cred[2][4][TS];
+  __shared__ double red[4];
+  const int p = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const MidProb P = a.probs[p];
+  if ((int)blockIdx.y >= mid_tiles(P.nb) || a.status[p] != 0) return;
+  int I, J;
+  mid_tile_of((int)blockIdx.y, &I, &J);
+  const HypDev h = mid_hyp(P, a.base);
+  const int n = P.n;
+  const int64_t ld = P.Mp;
+  const double* x = a.base + P.x;
+  const double* Wm = a.base + P.W;
+  const double* xn = a.base + P.S + (int64_t)n * ld;  // row n of X: -a
+  double* part = a.base + P.part + (int64_t)blockIdx.y * MID_PART;
+  const int c = TS * J + lane;
+  const bool cv = c < n;
+  const int cc = cv ? c : n - 1;
+  const double tb = x[cc * 3], gb = x[cc * 3 + 1], fb = x[cc * 3 + 2];
+  const double ac = -xn[cc];
+  double cD = 0.0, cS = 0.0, sl = 0.0;
+  for (int e = 0; e < 16; ++e) {
+    const int r = w + 4 * e, i = TS * I + r;  // wave-uniform
+    PairGrad o{0.0, 0.0, 0.0, 0.0, 0.0};
+    if (i < n && cv && c <= i) {
+      double wgt = (-xn[i]) * ac - Wm[(int64_t)i * ld + c];
+      if (c == i) wgt *= 0.5;
+      kernel_grad(h, x[i * 3], x[i * 3 + 1], x[i * 3 + 2], tb, gb, fb, wgt, o);
+    }
+    const double rD = wave_sum(o.dDr), rS = wave_sum(o.dSr);
+    if (lane == 0) {
+      part[r] = rD;
+      part[TS + r] = rS;
+    }
+    cD += o.dDc;
+    cS += o.dSc;
+    sl += o.dl;
+  }
+  cred[0][w][lane] = cD;
+  cred[1][w][lane] = cS;
+  const double s_l = block_sum(sl, red);  // its barriers also cover cred
+  if (w == 0) {
+    part[2 * TS + lane] = ((cred[0][0][lane] + cred[0][1][lane]) + cred[0][2][lane]) + cred[0][3][lane];
+    part[3 * TS + lane] = ((cred[1][0][lane] + cred[1][1][lane]) + cred[1][2][lane]) + cred[1][3][lane];
+    if (lane == 0) part[4 * TS] = s_l;
+  }
+}
+
+// ------------------------------------------------------------------ gradient
+// One workgroup per problem: each row's share of dD / dS (its tiles' row sums left to right,
+// then its column sums top down), each gene's rows in index order, d l over the tiles in order,
+// tr(W), the mean terms of m_i = (B/D)[i // (n/G)] flag_i (model.py:124-149) and the sign, as
+// grad_finish_kernel. Packed as the hyperparameters; the jitter slot is 0.
+__global__ __launch_bounds__(256) void mid_grad_kernel(MidArgs a) {
+  __shared__ double vD[MID_MAX_N], vS[MID_MAX_N];
+  __shared__ int gi[MID_MAX_N];
+  __shared__ double red[4];
+  const int p = blockIdx.x, tid = threadIdx.x;
+  const MidProb P = a.probs[p];
+  const int n = P.n, G = P.G;
+  double* gv = a.base + a.grad + P.hv;
+  double* gs = a.base + a.grad + P.hs;
+  if (a.status[p] != 0) {
+    const double nan = __builtin_nan("");
+    for (int g = tid; g < 3 * G; g += 256) gv[g] = nan;
+    if (tid == 0) {
+      gs[0] = nan;
+      gs[1] = nan;
+      gs[2] = 0.0;
+    }
+    return;
+  }
+  const HypDev h = mid_hyp(P, a.base);
+  const int64_t ld = P.Mp;
+  const double* x = a.base + P.x;
+  const double* Wm = a.base + P.W;
+  const double* xn = a.base + P.S + (int64_t)n * ld;
+  const double* part = a.base + P.part;
+  const double sign = a.negative ? -1.0 : 1.0;
+  double tr = 0.0;
+  for (int i = tid; i < n; i += 256) {
+    const int I = i >> 6, r = i & 63;
+    double sD = 0.0, sS = 0.0;
+    for (int J = 0; J <= I; ++J) {
+      const double* t = part + (int64_t)mid_tile_index(I, J) * MID_PART;
+      sD += t[r];
+      sS += t[TS + r];
+    }
+    for (int I2 = I; I2 < P.nb; ++I2) {
+      const double* t = part + (int64_t)mid_tile_index(I2, I) * MID_PART;
+      sD += t[2 * TS + r];
+      sS += t[3 * TS + r];
+    }
+    vD[i] = sD;
+    vS[i] = sS;
+    gi[i] = gene_index(x[i * 3 + 1], G);
+    tr += xn[i] * xn[i] - Wm[(int64_t)i * ld + i];
+  }
+  const double T = block_sum(tr, red);  // its barriers also cover vD / vS / gi
+  const int bs = n / G;
+  for (int g = tid; g < G; g += 256) {
+    double aD = 0.0, aS = 0.0, af = 0.0;
+    for (int i = 0; i < n; ++i)
+      if (gi[i] == g) {
+        aD += vD[i];
+        aS += vS[i];
+      }
+    for (int i = g * bs; i < (g + 1) * bs; ++i) af += (-xn[i]) * (double)flag_int(x[i * 3 + 2]);
+    const double D = h.D[g], B = h.B[g];
+    gv[g] = sign * (aD - B / (D * D) * af);
+    gv[G + g] = sign * aS;
+    gv[2 * G + g] = sign * (af / D);
+  }
+  if (tid == 0) {
+    double dl = 0.0;
+    const int nt = mid_tiles(P.nb);
+    for (int t = 0; t < nt; ++t) dl += part[(int64_t)t * MID_PART + 4 * TS];
+    gs[0] = sign * dl;
+    gs[1] = sign * a.base[P.hs + 1] * T;
+    gs[2] = 0.0;
+  }
+}
+
+int launch_mid(lfm_ctx* ctx, const MidLaunch& l, MidArgs a) {
+  static const bool attrs = [] {
+    for (const void* f : {reinterpret_cast<const void*>(&mid_column_kernel),
+                          reinterpret_cast<const void*>(&mid_invert_kernel),
+                          reinterpret_cast<const void*>(&mid_sinv_kernel)})
+      hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)MID_LDS);
+    return true;
+  }();
+  (void)attrs;
+  a.k = l.k;
+  const dim3 grid(l.gx, l.gy), block(256);
+  hipEvent_t ev;
+  const char* what = "";
+  switch (l.kind) {
+    case MID_FILL:
+      prof_begin(ctx, K_MID_FILL, &ev);
+      hipLaunchKernelGGL(mid_fill_kernel, grid, block, 0, ctx->stream, a);
+      prof_end(ctx, K_MID_FILL, ev, 0, 0);
+      what = "mid_fill_kernel";
+      break;
+    case MID_COLUMN:
+      prof_begin(ctx, K_MID_COLUMN, &ev);
+      hipLaunchKernelGGL(mid_column_kernel, grid, block, MID_LDS, ctx->stream, a);
+      prof_end(ctx, K_MID_COLUMN, ev, 0, 0);
+      what = "mid_column_kernel";
+      break;
+    case MID_VALUE:
+      prof_begin(ctx, K_MID_FINISH, &ev);
+      hipLaunchKernelGGL(mid_value_kernel, grid, block, 0, ctx->stream, a);
+      prof_end(ctx, K_MID_FINISH, ev, 0, 0);
+      what = "mid_value_kernel";
+      break;
+    case MID_INVERT:
+      prof_begin(ctx, K_MID_INVERSE, &ev);
+      hipLaunchKernelGGL(mid_invert_kernel, grid, block, MID_LDS, ctx->stream, a);
+      prof_end(ctx, K_MID_INVERSE, ev, 0, 0);
+      what = "mid_invert_kernel";
+      break;
+    case MID_SINV:
+      prof_begin(ctx, K_MID_INVERSE, &ev);
+      hipLaunchKernelGGL(mid_sinv_kernel, grid, block, MID_LDS, ctx->stream, a);
+      prof_end(ctx, K_MID_INVERSE, ev, 0, 0);
+      what = "mid_sinv_kernel";
+      break;
+    case MID_PAIRS:
+      prof_begin(ctx, K_MID_PAIRS, &ev);
+      hipLaunchKernelGGL(mid_pairs_kernel, grid, block, 0, ctx->stream, a);
+      prof_end(ctx, K_MID_PAIRS, ev, 0, 0);
+      what = "mid_pairs_kernel";
+      break;
+    case MID_GRAD:
+      prof_begin(ctx, K_MID_FINISH, &ev);
+      hipLaunchKernelGGL(mid_grad_kernel, grid, block, 0, ctx->stream, a);
+      prof_end(ctx, K_MID_FINISH, ev, 0, 0);
+      what = "mid_grad_kernel";
+      break;
+    default:
+      return set_err(ctx, LFM_E_STATE, "plan_mid: unknown launch kind");
+  }
+  return hip_fail(ctx, hipGetLastError(), what);
+}
+
+// One call: the hyperparameters up, the plan's launches, the results and status words down.
+int mid_call(lfm_ctx* ctx, lfm_mbatch* b, const double* hyp, int negative, bool want_grad,
+             double* value, double* grad, int* status) {
+  DeviceGuard g(ctx->device);
+  DeviceTenancy tenancy(ctx, false);  // shared
+  const MidPlan& P = b->plan;
+  const int64_t np = P.nprob, nh = P.nhyp;
+  double* base = reinterpret_cast<double*>(b->dmem);
+  std::memcpy(b->hbuf, hyp, (size_t)nh * 8);
+  hipError_t e = hipMemcpyAsync(base + P.hyp, b->hbuf, (size_t)nh * 8, hipMemcpyHostToDevice,
+                                ctx->stream);
+  if (e != hipSuccess) return hip_fail(ctx, e, "lfm_mbatch: upload");
+  MidArgs a{};
+  a.probs = reinterpret_cast<const MidProb*>(b->dmem + P.table);
+  a.base = base;
+  a.status = reinterpret_cast<int*>(b->dmem + P.status);
+  a.out = P.out;
+  a.grad = P.grad;
+  a.negative = negative;
+  for (const MidLaunch& l : want_grad ? P.value_grad : P.value)
+    if (int r = launch_mid(ctx, l, a)) return r;
+  int* hst = reinterpret_cast<int*>(b->hbuf + b->h_status);
+  e = hipMemcpyAsync(b->hbuf + b->h_out, base + P.out, (size_t)np * 8, hipMemcpyDeviceToHost,
+                     ctx->stream);
+  if (e == hipSuccess && want_grad)
+    e = hipMemcpyAsync(b->hbuf + b->h_grad, base + P.grad, (size_t)nh * 8, hipMemcpyDeviceToHost,
+                       ctx->stream);
+  if (e == hipSuccess)
+    e = hipMemcpyAsync(hst, a.status, (size_t)np * sizeof(int), hipMemcpyDeviceToHost, ctx->stream);
+  if (e != hipSuccess) return hip_fail(ctx, e, "lfm_mbatch: download");
+  if (int r = finish(ctx)) return r;
+  std::memcpy(value, b->hbuf + b->h_out, (size_t)np * 8);
+  if (want_grad) std::memcpy(grad, b->hbuf + b->h_grad, (size_t)nh * 8);
+  return batch_status(ctx, hst, np, status);
+}
+
+}  // namespace
+
+}  // namespace lfm
+
+extern "C" {
+
+int lfm_mbatch_create(lfm_ctx* ctx, int64_t nprob, const lfm_problem* probs, lfm_mbatch** out) {
+  if (!ctx) return LFM_E_ARG;
+  if (!out || nprob < 1 || !probs) return set_err(ctx, LFM_E_ARG, "bad batch arguments");
+  *out = nullptr;
+  std::vector<MidShape> shapes((size_t)nprob);
+  for (int64_t q = 0; q < nprob; ++q) {
+    const lfm_problem& p = probs[q];
+    if (int r = validate_x(ctx, p.x, p.n)) return r;
+    if (!p.y) return set_err(ctx, LFM_E_ARG, "problem y is NULL");
+    shapes[q] = {p.n, p.hyp.num_genes};
+  }
+  std::unique_ptr<lfm_mbatch> b(new lfm_mbatch);
+  b->plan = plan_mid(shapes);
+  const MidPlan& P = b->plan;
+  if (P.reject) return set_err(ctx, LFM_E_ARG, P.why);
+  DeviceGuard g(ctx->device);
+  b->device = ctx->device;
+  auto even = [](int64_t d) { return (size_t)((d + 1) / 2 * 2); };
+  b->h_out = even(P.nhyp);
+  b->h_grad = b->h_out + even(P.nprob);
+  b->h_status = b->h_grad + even(P.nhyp);
+  const size_t hbytes = b->h_status * 8 + (size_t)P.nprob * sizeof(int);
+  hipError_t e = hipMalloc((void**)&b->dmem, P.bytes);
+  if (e != hipSuccess)
+    return set_err(ctx, LFM_E_OOM, "lfm_mbatch_create: " + std::to_string(P.bytes) +
+                                       " bytes of device memory: " + hipGetErrorString(e));
+  e = hipHostMalloc((void**)&b->hbuf, hbytes, hipHostMallocDefault);
+  if (e == hipSuccess) e = hipMemsetAsync(b->dmem, 0, P.bytes, ctx->stream);
+  // x / y of every problem (adjacent in the arena), then the table; the staging outlives the copies
+  std::vector<std::vector<double>> stagings((size_t)nprob);
+  for (int64_t q = 0; q < nprob && e == hipSuccess; ++q) {
+    const MidProb& m = P.probs[q];
+    std::vector<double>& s = stagings[q];
+    s.assign((size_t)(m.S - m.x), 0.0);
+    std::memcpy(s.data(), probs[q].x, (size_t)m.n * 3 * 8);
+    std::memcpy(s.data() + (m.y - m.x), probs[q].y, (size_t)m.n * 8);
+    e = hipMemcpyAsync(reinterpret_cast<double*>(b->dmem) + m.x, s.data(), s.size() * 8,
+                       hipMemcpyHostToDevice, ctx->stream);
+  }
+  if (e == hipSuccess)
+    e = hipMemcpyAsync(b->dmem + P.table, P.probs.data(), (size_t)nprob * sizeof(MidProb),
+                       hipMemcpyHostToDevice, ctx->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+  if (e != hipSuccess) {
+    hipFree(b->dmem);
+    if (b->hbuf) hipHostFree(b->hbuf);
+    return hip_fail(ctx, e, "lfm_mbatch_create: upload");
+  }
+  *out = b.release();
+  return LFM_OK;
+}
+
+int lfm_mbatch_destroy(lfm_mbatch* batch) {
+  if (!batch) return LFM_E_ARG;
+  hipSetDevice(batch->device);
+  hipFree(batch->dmem);  // every call on the handle is synchronous: nothing of it is in flight
+  hipHostFree(batch->hbuf);
+  delete batch;
+  return LFM_OK;
+}
+
+int lfm_mbatch_hyp_size(const lfm_mbatch* batch, int64_t* out) {
+  if (!batch || !out) return LFM_E_ARG;
+  *out = batch->plan.nhyp;
+  return LFM_OK;
+}
+
+int lfm_mbatch_mll_f64(lfm_ctx* ctx, lfm_mbatch* batch, const double* hyp, int negative,
+                       double* out, int* status) {
+  if (!ctx) return LFM_E_ARG;
+  if (!batch || !hyp || !out) return set_err(ctx, LFM_E_ARG, "batch / hyp / out is NULL");
+  if (batch->device != ctx->device) return set_err(ctx, LFM_E_ARG, "batch of another device");
+  return mid_call(ctx, batch, hyp, negative, false, out, nullptr, status);
+}
+
+int lfm_mbatch_mll_grad_f64(lfm_ctx* ctx, lfm_mbatch* batch, const double* hyp, int negative,
+                            double* value, double* grad, int* status) {
+  if (!ctx) return LFM_E_ARG;
+  if (!batch || !hyp || !value || !grad)
+    return set_err(ctx, LFM_E_ARG, "batch / hyp / value / grad is NULL");
+  if (batch->device != ctx->device) return set_err(ctx, LFM_E_ARG, "batch of another device");
+  return mid_call(ctx, batch, hyp, negative, true, value, grad, status);
+}
+
+}  // extern "C"

@@ -1,0 +1,97 @@
+// lfm_mid_plan.h — layout and launch plan of the resident batch of mid-size problems
+// (lfm_mbatch_*, 1 <= n <= MID_MAX_N): every problem's regions in the handle's device arena, the
+// grids and the launch list of a value call and of a value-and-gradient call. Plain C++ (part of
+// lfm_host.h): lfm_mid.hip only reads it, and tests/native/mid_plan_check.cpp checks it by
+// enumeration under the sanitizers.
+//
+// Per problem the arena holds x [n x 3], y [n] and, with Mp = 64 ceil((n + 1) / 64) and
+// nb = Mp / 64 block rows, three Mp x Mp row-major matrices:
+//   S   the augmented matrix (row n: the residual y - m(x); rows past n: identity), filled per
+//       call from the packed hyperparameters; the gradient call overwrites it with X = L^{-1}
+//   L   the factor (row n: z = L^{-1} (y - m(x)), unit pivot)
+//   W   S^{-1} over the lower tiles (gradient call)
+// then the nb inverses of the factor's 64 x 64 diagonal blocks and the pairs launch's partial
+// sums, MID_PART doubles per lower tile. Ordering between launches is the stream's alone: no
+// launch reads what another workgroup of the same launch writes.
+#pragma once
+
+#include <cstddef>
+#include <cstdint>
+#include <string>
+#include <vector>
+
+#include "lfm_small_plan.h"  // LFM_HD
+
+namespace lfm {
+
+constexpr int MID_TILE = 64;
+constexpr int MID_MAX_N = 1024;                 // LFM_MID_MAX_N
+constexpr int64_t MID_MAX_PROBS = 1 << 20;      // grid.x = problems
+// one tile's partial sums of 1/2 tr(W dS / d theta): by row dD [64] dS [64], by column dD [64]
+// dS [64], then d l
+constexpr int MID_PART = 4 * MID_TILE + 1;
+
+LFM_HD inline int mid_blocks(int n) { return (n + 1 + MID_TILE - 1) / MID_TILE; }
+LFM_HD inline int mid_tiles(int nb) { return nb * (nb + 1) / 2; }
+// lower tile t -> (block row I, block column J <= I), row by row
+LFM_HD inline void mid_tile_of(int t, int* I, int* J) {
+  int i = 0;
+  while ((i + 1) * (i + 2) / 2 <= t) ++i;
+  *I = i;
+  *J = t - i * (i + 1) / 2;
+}
+LFM_HD inline int mid_tile_index(int I, int J) { return I * (I + 1) / 2 + J; }
+
+struct MidShape {
+  int64_t n, G;
+};
+
+// One problem's table entry, as the kernels read it. Offsets in doubles from the arena's base;
+// hv / hs: its vectors (D S B, 3 G) and scalars (l, obs_stddev, jitter) in the packed
+// hyperparameters, and of its gradient in the packed gradient.
+struct MidProb {
+  int n, G, nb, Mp;
+  int64_t hv, hs;
+  int64_t x, y;
+  int64_t S, L, W;
+  int64_t dinv;  // [nb][64 x 64]
+  int64_t part;  // [nb (nb + 1) / 2][MID_PART]
+};
+
+// What each launch's workgroup (blockIdx.x = problem p, blockIdx.y = u) owns; a workgroup whose
+// problem has no such unit exits at once:
+//   MID_FILL    lower tile u of S (and the status word)
+//   MID_COLUMN  block (k + u, k) of L (u = 0 also the diagonal block's inverse and the status)
+//   MID_VALUE   the problem's value (u = 0)
+//   MID_INVERT  block column u of X = L^{-1}: tiles (i, u), i >= u, written into S
+//   MID_SINV    lower tile u of W = S^{-1} = X^T X
+//   MID_PAIRS   lower tile u's partial sums
+//   MID_GRAD    the problem's gradient (u = 0)
+enum MidKind { MID_FILL = 0, MID_COLUMN, MID_VALUE, MID_INVERT, MID_SINV, MID_PAIRS, MID_GRAD };
+struct MidLaunch {
+  int kind, k;
+  unsigned gx, gy;
+};
+
+struct MidPlan {
+  enum Reject { OK = 0, EMPTY, BAD_N, BAD_G, TOO_MANY };
+  int reject = OK;
+  std::string why;
+  int64_t nprob = 0, nhyp = 0;
+  int maxnb = 0, maxtiles = 0;
+  std::vector<MidProb> probs;
+  // the arena, in doubles: the call's packed hyperparameters, values and gradient first
+  int64_t hyp = 0, out = 0, grad = 0, doubles = 0;
+  // then, in bytes from the arena's base: the status words [nprob] and the problem table
+  size_t status = 0, table = 0, bytes = 0;
+  std::vector<MidLaunch> value, value_grad;  // the two calls' launches, in stream order
+};
+
+// doubles of one problem's regions (x, y, the three matrices, the block inverses, the partials),
+// each region rounded up to 2 doubles (16-byte alignment)
+int64_t mid_problem_doubles(int64_t n);
+// Rejections in order: no problems; too many; an n outside [1, MID_MAX_N]; a G outside [1, n] or
+// that does not divide n (the first offending problem, named in `why`)
+MidPlan plan_mid(const std::vector<MidShape>& shapes);
+
+}  // namespace lfm

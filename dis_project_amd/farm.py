@@ -295,6 +295,104 @@ class BatchEvaluator:
             self._genes = None
 
 
+class MidBatchEvaluator:
+    """``BatchEvaluator`` for problems of any size 1 <= n <= 1024 (``lfm_mbatch_*``): pooled
+    replicates, larger time grids — the same independent (model, dataset) problems once they
+    outgrow one workgroup each. Every problem's x / y go to HBM once; a call packs the models'
+    hyperparameters (``lfm_batch_mll_f64``'s layout) and evaluates every problem's MLL, or MLL
+    and gradient, in a number of launches that depends on the largest n alone. Sizes may be
+    mixed. Not PD -> NaN, with ``status``. A problem's bits depend on its own data and
+    hyperparameters alone. ``ctx`` may be None: the calling thread's context is then asked for
+    at the first evaluation, after the shapes and ``num_genes`` have been checked."""
+
+    MAX_N = 1024  # LFM_MID_MAX_N
+
+    def __init__(self, ctx, datasets, negative: bool = False):
+        self.ctx, self.negative = ctx, bool(negative)
+        self.datasets = list(datasets)
+        self.batch = None
+        if not self.datasets:
+            raise ValueError("at least one dataset")
+        probs = (_lib.LfmProblem * len(self.datasets))()
+        keep = []
+        for i, d in enumerate(self.datasets):
+            x = np.ascontiguousarray(d.X, dtype=np.float64)
+            y = np.ascontiguousarray(d.y, dtype=np.float64).reshape(-1)
+            if x.ndim != 2 or x.shape[1] != 3:
+                raise ValueError(f"dataset {i}: x must be [n, 3]")
+            if y.size != x.shape[0]:
+                raise ValueError(f"dataset {i}: x has {x.shape[0]} rows, y {y.size}")
+            if not 1 <= x.shape[0] <= self.MAX_N:
+                raise ValueError(f"dataset {i}: n = {x.shape[0]} outside [1, {self.MAX_N}]")
+            keep.append((x, y))
+            probs[i].x, probs[i].y, probs[i].n = x.ctypes.data, y.ctypes.data, x.shape[0]
+        self._probs, self._keep = probs, keep
+        self._genes = None
+        self.status = np.zeros(len(self.datasets), dtype=np.int32)
+        self._out = np.empty(len(self.datasets))
+
+    def registered(self, genes):
+        """The handle registered for this gene layout (re-registered if it changed)."""
+        genes = tuple(int(g) for g in genes)
+        if genes == self._genes:
+            return self.batch
+        if len(genes) != len(self.datasets):
+            raise ValueError("one model per registered dataset")
+        for i, (g, (x, _)) in enumerate(zip(genes, self._keep)):
+            if g < 1 or x.shape[0] % g != 0:
+                raise ValueError(f"dataset {i}: n = {x.shape[0]} is not a multiple of "
+                                 f"num_genes = {g}")
+        if self.ctx is None:
+            self.ctx = _lib.get_context()
+        self.close()
+        for i, g in enumerate(genes):
+            self._probs[i].hyp.num_genes = g
+        h = _lib.c_void_p()
+        self.ctx.check(self.ctx.lib.lfm_mbatch_create(self.ctx.handle, len(genes), self._probs,
+                                                      _lib.ctypes.byref(h)))
+        self.batch, self._genes = h, genes
+        nvec = 3 * sum(genes)
+        self._buf = np.empty(nvec + 3 * len(genes))
+        self._vec, self._sc = self._buf[:nvec], self._buf[nvec:]
+        return self.batch
+
+    def _pack(self, models):
+        models = list(models)
+        if len(models) != len(self.datasets):
+            raise ValueError("one model per registered dataset")
+        self.registered(map(_NUM_GENES, models))
+        np.concatenate([np.asarray(v, np.float64).reshape(-1)
+                        for v in _chain(map(_VECS, models))], out=self._vec)
+        self._sc[:] = list(_chain(map(_SCALARS, models)))
+        return models
+
+    def __call__(self, models) -> np.ndarray:
+        self._pack(models)
+        rc = self.ctx.lib.lfm_mbatch_mll_f64(self.ctx.handle, self.batch, _lib.dptr(self._buf),
+                                             int(self.negative), _lib.dptr(self._out),
+                                             _lib.dptr(self.status))
+        self.ctx.check(rc, allow_not_pd=True)
+        return self._out.copy()
+
+    def value_and_grad(self, models):
+        """(values [P], [grad dict per problem]) as ``BatchEvaluator.value_and_grad``
+        (``lfm_mbatch_mll_grad_f64``); NaN where not PD."""
+        self._pack(models)
+        grad = np.empty(self._buf.size)
+        rc = self.ctx.lib.lfm_mbatch_mll_grad_f64(self.ctx.handle, self.batch,
+                                                  _lib.dptr(self._buf), int(self.negative),
+                                                  _lib.dptr(self._out), _lib.dptr(grad),
+                                                  _lib.dptr(self.status))
+        self.ctx.check(rc, allow_not_pd=True)
+        return self._out.copy(), unpack_grads(grad, self._genes)
+
+    def close(self):
+        if self.batch is not None:
+            self.ctx.lib.lfm_mbatch_destroy(self.batch)
+            self.batch = None
+            self._genes = None
+
+
 def workload(kind: str, genes: int = 64, timepoints: int = 256, restarts: int = 32,
              rounds: int = 1):
     """Problems of a farm workload as (models, datasets):

@@ -292,6 +292,82 @@ class BatchTrainer:
         self._ev.close()
 
 
+class _StepValues:
+    """The objective of one problem's JaxTrainer inside MidBatchTrainer: hands back the value and
+    gradient the batched call has already computed for this step."""
+
+    value, grad = None, None
+
+    def value_and_grad(self, model, data):
+        return self.value, self.grad
+
+
+@dataclass
+class MidBatchTrainer:
+    """``JaxTrainer`` (trainer.py:36-228) over P independent (model, dataset) problems of any
+    size up to 1024 rows each, stepped on the host: every step makes ONE batched value-and-
+    gradient call for all problems (``farm.MidBatchEvaluator``: ``lfm_mbatch_mll_grad_f64``) at
+    the constrained models, then each problem takes ``JaxTrainer.step`` — the bijectors' chain
+    rule, ``optim.update`` / ``apply_updates`` — and ``after_epoch`` exactly as ``JaxTrainer.fit``
+    orders them. ``objective`` is a ``CustomConjMLL`` (its ``negative``). ``evaluator`` replaces
+    the GPU evaluator (anything with ``value_and_grad(models) -> (values, [grad dicts])``): the
+    host loop then needs no device."""
+
+    models: Sequence[ExactLFM]
+    objective: Any
+    training_data: Sequence[Dataset]
+    optim: adam
+    key: Any = None
+    num_iters: int = 150
+    ctx: Any = None
+    evaluator: Any = None
+    history: Any = None
+
+    def __post_init__(self):
+        self.models = list(self.models)
+        self.training_data = list(self.training_data)
+        if len(self.models) != len(self.training_data):
+            raise ValueError("one model per dataset")
+        self._like = list(self.models)
+        self._steps = [_StepValues() for _ in self.models]
+        self._trainers = [JaxTrainer(m, s, d, self.optim, num_iters=self.num_iters)
+                          for m, s, d in zip(self.models, self._steps, self.training_data)]
+        self.raws = [t.raw for t in self._trainers]  # trainer.py:75
+        if self.evaluator is None:
+            from .farm import MidBatchEvaluator
+
+            self.evaluator = MidBatchEvaluator(self.ctx, self.training_data,
+                                               bool(self.objective.negative))
+
+    def fit(self, fix_params: bool = True, num_steps_per_epoch: int = 1000):
+        """trainer.py:162-228 for every problem; returns (models, histories [P, num_iters])."""
+        raws = list(self.raws)
+        states = [self.optim.init(r) for r in raws]
+        hist = np.empty((len(raws), self.num_iters))
+        for step_count in range(self.num_iters):
+            vals, grads = self.evaluator.value_and_grad(
+                [constrain(r, like) for r, like in zip(raws, self._like)])
+            for p, t in enumerate(self._trainers):
+                self._steps[p].value, self._steps[p].grad = float(vals[p]), grads[p]
+                (raws[p], states[p]), hist[p, step_count] = t.step((raws[p], states[p]), None,
+                                                                   step_count)
+                if step_count % num_steps_per_epoch == 0:
+                    raws[p] = JaxTrainer.after_epoch(raws[p], fix_params)
+        out = []
+        for r, like in zip(raws, self._like):
+            m = constrain(r, like)
+            if fix_params:  # trainer.py:218-222, on the constrained model
+                c = JaxTrainer.after_epoch({"true_s": m.true_s, "true_d": m.true_d}, True)
+                m = m.replace(true_s=c["true_s"], true_d=c["true_d"])
+            out.append(m)
+        self.raws, self.models, self.history = raws, out, hist
+        return self.models, self.history
+
+    def close(self):
+        if hasattr(self.evaluator, "close"):
+            self.evaluator.close()
+
+
 def fit_records(raws: Sequence[dict], hist: np.ndarray, gmax: int) -> np.ndarray:
     """Each problem's fit result as one fixed-length fp64 record (FarmTrainer's exchange):
     raw true_d / true_s / true_b (G each, NaN-padded to gmax), raw l, raw obs_stddev, then the

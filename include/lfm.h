@@ -195,6 +195,52 @@ int lfm_batch_mll_f64(lfm_ctx* ctx, lfm_batch* batch, const double* hyp, int neg
 int lfm_batch_mll_grad_f64(lfm_ctx* ctx, lfm_batch* batch, const double* hyp, int negative,
                            double* value, double* grad, int* status);
 
+/* A resident batch of problems of any size 1 <= n <= LFM_MID_MAX_N — the same set of independent
+ * (model, dataset) problems (src/notebook.py:33-75, each trained on CustomConjMLL(negative=True),
+ * src/trainer.py:105-132) once they outgrow lfm_batch's one workgroup per problem: pooled
+ * replicates (3 x 10 genes x 7 times, n = 210) or a 5-gene x 64-time grid (n = 320). Every
+ * problem's MLL, or MLL and gradient, in a number of launches that depends on the largest n alone
+ * (ceil((n + 1) / 64) + 2 for the value, four more with the gradient), not on the problem count.
+ *   lfm_mbatch_create   x / y of every problem (probs[p].x, .y, .n) go to HBM once; of
+ *     probs[p].hyp only num_genes is read. 1 <= n_p <= LFM_MID_MAX_N and n_p % G_p == 0, else
+ *     LFM_E_ARG with a message naming the limit; sizes may be mixed freely, small ones included.
+ *     The handle owns its device memory (the factors, S^{-1}, the partial sums; nothing in the
+ *     ctx workspace, which other calls regrow): per problem, with Mp = 64 ceil((n + 1) / 64) and
+ *     nb = Mp / 64,   8 (3 Mp^2 + 64 Mp + 257 nb (nb + 1) / 2 + 4 n + 3) bytes at most
+ *     (29.3 MB at n = 1024, 1.0 MB at n = 128), plus 8 (6 G + 9) + 100 bytes of call buffers.
+ *   lfm_mbatch_mll_f64 / lfm_mbatch_mll_grad_f64   hyp, out, value, grad and status in exactly
+ *     the packed layouts of lfm_batch_mll_f64 / lfm_batch_mll_grad_f64 (the gradient's jitter
+ *     slot is 0). The value is lfm_mll_f64's and the gradient lfm_mll_grad_f64's: the same
+ *     constrained parameters in the same order. Not positive definite (a pivot <= 0 or NaN in
+ *     whichever block column it happens): that problem's value and gradient are NaN, status[p] =
+ *     LFM_E_NOT_PD and the call returns LFM_E_NOT_PD; every other problem's outputs are valid and
+ *     the same bits as without it.
+ *   Determinism and independence: no atomics and no device-side waits (ordering comes only from
+ *     consecutive launches on the ctx's stream). The same inputs give the same bits; a problem's
+ *     bits depend on its own data and hyperparameters alone, not on which other problems share
+ *     the batch, on their sizes or on its position; value from the gradient call is the MLL
+ *     call's out, bit for bit.
+ *   Synchronous; holds the device's lock shared. A handle belongs to the device of the ctx that
+ *     created it (a ctx of another device: LFM_E_ARG) and to one host thread at a time.
+ *     lfm_mbatch_destroy(NULL) is LFM_E_ARG.
+ * LFM_MID_MAX_N bounds the handle's memory, not its speed. A call's time is set by the largest n
+ * and hardly by the problem count, so the per-problem loop of lfm_mll_f64 / lfm_mll_grad_f64
+ * catches up below the cap when few problems share the call. Measured on an MI355X (DESIGN.md
+ * section 4.9, scripts/mid_batch_rate.py): with 15 problems the batch is faster at every size
+ * (value and gradient 7.8x at n = 160, 4.3x at 320, 2.4x at 640, 1.7x at 1020); with 4 problems
+ * the loop is the faster one from n = 320 up for the value (0.99x at 320, 0.57x at 1020) and from
+ * n = 640 up with the gradient (1.3x at 320, 0.80x at 640, 0.61x at 1020). */
+#define LFM_MID_MAX_N 1024
+typedef struct lfm_mbatch lfm_mbatch;
+int lfm_mbatch_create(lfm_ctx* ctx, int64_t nprob, const lfm_problem* probs, lfm_mbatch** out);
+int lfm_mbatch_destroy(lfm_mbatch* batch);
+/* Doubles in the packed hyperparameter array: sum_p (3 G_p + 3). */
+int lfm_mbatch_hyp_size(const lfm_mbatch* batch, int64_t* out);
+int lfm_mbatch_mll_f64(lfm_ctx* ctx, lfm_mbatch* batch, const double* hyp, int negative,
+                       double* out, int* status);
+int lfm_mbatch_mll_grad_f64(lfm_ctx* ctx, lfm_mbatch* batch, const double* hyp, int negative,
+                            double* value, double* grad, int* status);
+
 /* optax.adam(learning_rate, b1, b2, eps, eps_root) and JaxTrainer.fit's epoch handling
  * (src/trainer.py:162-228; src/main.py:45 and notebook.py:55 use adam(0.01)). */
 typedef struct {
