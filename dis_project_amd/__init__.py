@@ -10,7 +10,7 @@ from .distributions import GaussianDistribution  # noqa: F401
 from .farm import MidBatchEvaluator  # noqa: F401
 from .model import ExactLFM  # noqa: F401
 from .objectives import CustomConjMLL  # noqa: F401
-from .predict import BatchPredictor, Posterior  # noqa: F401
+from .predict import BatchPredictor, MidBatchPredictor, Posterior  # noqa: F401
 from .trainer import MidBatchTrainer  # noqa: F401
 
 __all__ = [
@@ -21,6 +21,7 @@ __all__ = [
     "GaussianDistribution",
     "LfmError",
     "MidBatchEvaluator",
+    "MidBatchPredictor",
     "MidBatchTrainer",
     "Posterior",
     "SyntheticP53Data",

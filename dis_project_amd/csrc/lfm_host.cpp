@@ -651,4 +651,88 @@ MidPlan plan_mid(const std::vector<MidShape>& shapes) {
   return P;
 }
 
+MidPostPlan plan_mid_post(const std::vector<MidShape>& shapes, const int64_t* m, bool has_dv,
+                          bool want_cov) {
+  MidPostPlan P;
+  auto rejected = [&](int code, size_t q, const std::string& why) {
+    P.reject = code;
+    P.why = "lfm_mbatch_posterior_f64: problem " + std::to_string(q) + " has m = " +
+            std::to_string(m[q]) + why;
+    return P;
+  };
+  for (size_t q = 0; q < shapes.size(); ++q) {
+    if (m[q] < 1) return rejected(MidPostPlan::NO_ROWS, q, ", needs m >= 1");
+    if (m[q] % shapes[q].G != 0)
+      return rejected(MidPostPlan::BAD_M, q, ", no multiple of num_genes = " +
+                                                 std::to_string(shapes[q].G) +
+                                                 " (mean_function, model.py:145-149)");
+    if (m[q] > MID_MAX_M)
+      return rejected(MidPostPlan::TOO_MANY_ROWS, q, ", past " + std::to_string(MID_MAX_M) +
+                                                         " (LFM_MID_MAX_M); use lfm_post_* for "
+                                                         "more test rows on one model");
+  }
+  P.nprob = (int64_t)shapes.size();
+  for (size_t q = 0; q < shapes.size(); ++q) {
+    P.sn += shapes[q].n;
+    P.sm += m[q];
+    P.sc += m[q] * m[q];
+  }
+  int64_t at = 0;
+  P.dadd = at;
+  at += even(P.nprob);
+  if (has_dv) {
+    P.dv = at;
+    at += even(P.sn);
+  }
+  P.t = at;
+  at += even(3 * P.sm);
+  P.pp.reserve(shapes.size());
+  int64_t on = 0, om = 0, oc = 0;
+  for (size_t q = 0; q < shapes.size(); ++q) {
+    const int nb = mid_blocks((int)shapes[q].n);
+    MidPostProb e{};
+    e.m = (int)m[q];
+    e.mb = (e.m + MID_TILE - 1) / MID_TILE;
+    e.dv = has_dv ? P.dv + on : -1;
+    e.t = P.t + 3 * om;
+    e.V = at;
+    at += (int64_t)e.mb * MID_TILE * nb * MID_TILE;
+    e.mean = om;  // within the packed outputs: their bases are added below
+    e.var = om;
+    e.cov = want_cov ? oc : -1;
+    on += shapes[q].n;
+    om += m[q];
+    oc += m[q] * m[q];
+    P.maxnb = std::max(P.maxnb, nb);
+    P.maxmb = std::max(P.maxmb, e.mb);
+    P.maxunits = std::max(P.maxunits, e.mb * nb);
+    P.pp.push_back(e);
+  }
+  P.mean = at;
+  at += even(P.sm);
+  P.var = at;
+  at += even(P.sm);
+  if (want_cov) {
+    P.cov = at;
+    at += even(P.sc);
+  }
+  for (MidPostProb& e : P.pp) {
+    e.mean += P.mean;
+    e.var += P.var;
+    if (want_cov) e.cov += P.cov;
+  }
+  P.maxtiles = mid_tiles(P.maxnb);
+  P.maxcov = mid_tiles(P.maxmb);
+  P.doubles = at;
+  P.table = (size_t)at * sizeof(double);
+  P.bytes = P.table + (size_t)P.nprob * sizeof(MidPostProb);
+  const unsigned gx = (unsigned)P.nprob;
+  P.launches.push_back({MID_POST_FILL, 0, gx, (unsigned)(P.maxtiles + P.maxunits)});
+  for (int k = 0; k < P.maxnb; ++k)
+    P.launches.push_back({MID_COLUMN, k, gx, (unsigned)(P.maxnb - k)});
+  P.launches.push_back({MID_SOLVE, 0, gx, (unsigned)P.maxmb});
+  if (want_cov) P.launches.push_back({MID_COV, 0, gx, (unsigned)P.maxcov});
+  return P;
+}
+
 }  // namespace lfm

@@ -21,10 +21,22 @@
 //   mid_pairs_kernel   grad_pairs_kernel's work per lower tile with W = a a^T - S^{-1}: its
 //                      per-row / per-column partial sums go to the tile's own scratch slots
 //   mid_grad_kernel    joins the partials in a fixed order; tr(W), the mean terms, the sign
+// and latent_predict / multi_gene_predict (src/model.py:420-514) of every problem at its own test
+// inputs (lfm_mbatch_posterior_f64; the layout of its arena and its launches: plan_mid_post):
+//   mid_fill_kernel<true>  S with the posterior's diagonal, (K + diag_vec) + diag_add, and in the
+//                      same launch T = K(t, x), one unit per (test block, column block), into V
+//   mid_column_kernel  as above
+//   mid_solve_kernel   unit = a block of 64 test rows: V_uk = (T_uk - sum_{j<k} V_uj L_kj^T)
+//                      D_k^T for k = 0 .. nb - 1 (fp64 MFMA), in place; column n of V is then
+//                      -V z (the augmented row of L is z, with a unit pivot), so
+//                      mean = m(t) - V[:, n], and var = k(t, t) - sum_{c<n} V_c^2 in column order
+//   mid_cov_kernel     lower tile (a, b) of K(t, t) - V V^T over depth n, and its mirror image;
+//                      the diagonal entries are var's
 // No atomics and no device-side waits: consecutive launches on one stream are the only ordering,
 // so a problem's bits depend on its own data and hyperparameters alone.
 #include <cstring>
 #include <memory>
+#include <type_traits>
 
 #include "lfm_api_internal.h"
 #include "lfm_chol_dev.h"
@@ -37,7 +49,10 @@ using namespace lfm;
 struct lfm_mbatch {
   int device = 0;
   MidPlan plan;
+  std::vector<lfm::MidShape> shapes;
   char* dmem = nullptr;
+  char* pmem = nullptr;  // the posterior calls' arena (plan_mid_post), grown on demand
+  size_t pbytes = 0;
   double* hbuf = nullptr;
   size_t h_out = 0, h_grad = 0, h_status = 0;  // doubles into hbuf
 };
@@ -97,15 +112,56 @@ __device__ __forceinline__ void acc_each(double4v (&acc)[4], F f) {
     for (int q = 0; q < 4; ++q) f(16 * w + lk + 4 * q, 16 * jr + li, acc[jr][q]);
 }
 
+// The posterior call's second arena and table; `none` for the MLL's fill.
+struct MidPostArgs {
+  const MidPostProb* pp;
+  double* base;
+  int64_t dadd;  // diag_add [nprob], doubles from base
+  int maxtiles;  // units of the fill launch before the first T unit
+};
+struct MidNoPost {};
+
 __device__ __forceinline__ HypDev mid_hyp(const MidProb& P, const double* hyp) {
   const double* v = hyp + P.hv;
   return HypDev{v, v + P.G, v + 2 * P.G, P.G, hyp[P.hs]};
 }
 
 // ------------------------------------------------------------------ fill
-__global__ __launch_bounds__(256) void mid_fill_kernel(MidArgs a) {
+// POST: the posterior's fill. The diagonal is (K + diag_vec) + diag_add instead of the MLL's
+// (K + jitter) + sigma^2, and the units from q.maxtiles on fill T = K(t, x): unit tb * nb + k the
+// 64 x 64 tile of test block tb and column block k of the problem's V buffer (rows past m and the
+// columns from n on are 0).
+template <bool POST>
+__global__ __launch_bounds__(256) void mid_fill_kernel(
+    MidArgs a, typename std::conditional<POST, MidPostArgs, MidNoPost>::type q) {
   const int p = blockIdx.x, tid = threadIdx.x;
   const MidProb P = a.probs[p];
+  if constexpr (POST) {
+    if ((int)blockIdx.y >= q.maxtiles) {
+      const MidPostProb Q = q.pp[p];
+      const int unit = (int)blockIdx.y - q.maxtiles;
+      if (unit >= Q.mb * P.nb) return;
+      const int tb = unit / P.nb, k = unit - tb * P.nb;
+      const HypDev h = mid_hyp(P, a.base);
+      const double* x = a.base + P.x;
+      const double* t = q.base + Q.t;
+      double* T = q.base + Q.V;
+      const int c = TS * k + (tid & 63);
+      double tx = 0.0, gx = 0.0, fx = 0.0;
+      if (c < P.n) {
+        tx = x[c * 3];
+        gx = x[c * 3 + 1];
+        fx = x[c * 3 + 2];
+      }
+      for (int e = 0; e < 16; ++e) {
+        const int r = TS * tb + (tid >> 6) + 4 * e;
+        double v = 0.0;
+        if (r < Q.m && c < P.n) v = kernel_ref(h, t[r * 3], t[r * 3 + 1], t[r * 3 + 2], tx, gx, fx);
+        T[(int64_t)r * P.Mp + c] = v;
+      }
+      return;
+    }
+  }
   if ((int)blockIdx.y >= mid_tiles(P.nb)) return;
   int I, J;
   mid_tile_of((int)blockIdx.y, &I, &J);
@@ -128,7 +184,15 @@ __global__ __launch_bounds__(256) void mid_fill_kernel(MidArgs a) {
     double v;
     if (i < n && c <= i) {
       v = kernel_ref(h, x[i * 3], x[i * 3 + 1], x[i * 3 + 2], tb, gb, fb);
-      if (i == c) v = (v + jit) + s2;  // (K + jitter I) + sigma^2 I, objectives.py:71-72
+      if (i == c) {
+        if constexpr (POST) {
+          const MidPostProb Q = q.pp[p];
+          const double dv = Q.dv >= 0 ? q.base[Q.dv + i] : 0.0;
+          v = (v + dv) + q.base[q.dadd + p];  // (K + diag(diag_vec)) + diag_add I
+        } else {
+          v = (v + jit) + s2;  // (K + jitter I) + sigma^2 I, objectives.py:71-72
+        }
+      }
     } else if (i == n && c < n) {
       v = y[c] - mean_at(h, x, c, bs);
     } else {
@@ -486,11 +550,139 @@ __global__ __launch_bounds__(256) void mid_grad_kernel(MidArgs a) {
   }
 }
 
-int launch_mid(lfm_ctx* ctx, const MidLaunch& l, MidArgs a) {
+// ------------------------------------------------------------------ V = T L^{-T}
+// Block row u of V, left to right: V_uk = (T_uk - sum_{j<k} V_uj L_kj^T) D_k^T, D_k the inverse
+// of the factor's diagonal block. The tiles this workgroup wrote to its own rows of V are the
+// ones it reads back (workgroup barrier between), as mid_invert_kernel. A row of V depends on its
+// own row of T alone. Thread r < 64 then owns test row 64 u + r: the sum of its squares over the
+// columns < n in column order, and column n, which is -(V z)_r.
+__global__ __launch_bounds__(256) void mid_solve_kernel(MidArgs a, MidPostArgs q) {
+  extern __shared__ __attribute__((aligned(16))) double sm[];
+  Tile sA = reinterpret_cast<Tile>(sm), sB = sA + TS;
+  const int p = blockIdx.x, u = blockIdx.y, tid = threadIdx.x;
+  const MidProb P = a.probs[p];
+  const MidPostProb Q = q.pp[p];
+  if (u >= Q.mb) return;
+  const int row = TS * u + tid;
+  double* mean = q.base + Q.mean;
+  double* var = q.base + Q.var;
+  if (a.status[p] != 0) {
+    if (tid < TS && row < Q.m) {
+      mean[row] = __builtin_nan("");
+      var[row] = __builtin_nan("");
+    }
+    return;
+  }
+  const int64_t ld = P.Mp;
+  const int n = P.n;
+  const double* L = a.base + P.L;
+  const double* Di = a.base + P.dinv;
+  double* V = q.base + Q.V + (int64_t)u * TS * ld;
+  double vacc = 0.0, vn = 0.0;
+  for (int k = 0; k < P.nb; ++k) {
+    double4v acc[4];
+    acc_zero(acc);
+    for (int j = 0; j < k; ++j) {
+      __syncthreads();  // also: the tile (u, j) written below is visible to the whole workgroup
+      stage(sA, V + j * TS, ld, false);
+      stage(sB, L + (int64_t)k * TS * ld + j * TS, ld, false);
+      __syncthreads();
+      mma_nt(acc, sA, sB);
+    }
+    __syncthreads();
+    const double* Tuk = V + k * TS;
+    acc_each(acc, [&](int r, int c, double v) { sA[r][c] = Tuk[r * ld + c] - v; });
+    stage(sB, Di + (int64_t)k * TS * TS, TS, false);
+    __syncthreads();
+    acc_zero(acc);
+    mma_nt(acc, sA, sB);
+    __syncthreads();
+    double* Vuk = V + k * TS;
+    acc_each(acc, [&](int r, int c, double v) {
+      Vuk[r * ld + c] = v;
+      sA[r][c] = v;
+    });
+    __syncthreads();
+    if (tid < TS) {
+      const int lim = n - k * TS;  // the columns of this block below n
+      for (int c = 0; c < TS && c < lim; ++c) vacc = fma(sA[tid][c], sA[tid][c], vacc);
+      if (lim >= 0 && lim < TS) vn = sA[tid][lim];
+    }
+  }
+  if (tid < TS && row < Q.m) {
+    const HypDev h = mid_hyp(P, a.base);
+    const double* t = q.base + Q.t;
+    const double* tr = t + 3 * row;
+    mean[row] = mean_at(h, t, row, Q.m / P.G) - vn;
+    var[row] = kernel_ref(h, tr[0], tr[1], tr[2], tr[0], tr[1], tr[2]) - vacc;
+  }
+}
+
+// A 64 x 64 tile at g into LDS with the columns >= cols read as 0
+__device__ __forceinline__ void stage_cols(Tile s, const double* __restrict__ g, int64_t ld,
+                                           int cols) {
+  const int tid = threadIdx.x;
+#pragma unroll 4
+  for (int e = 0; e < 16; ++e) {
+    const int idx = tid + 256 * e, r = idx >> 6, c = idx & 63;
+    s[r][c] = c < cols ? g[r * ld + c] : 0.0;
+  }
+}
+
+// ------------------------------------------------------------------ covariance
+// Lower tile (A, B) of the test blocks: k(t_i, t_j) - sum_{c<n} V_ic V_jc for j <= i, written to
+// (i, j) and to (j, i); the columns of V from n on are left out, as mid_sinv_kernel leaves out
+// X's rows. The diagonal entries are var's (the solve's sums in column order).
+__global__ __launch_bounds__(256) void mid_cov_kernel(MidArgs a, MidPostArgs q) {
+  extern __shared__ __attribute__((aligned(16))) double sm[];
+  Tile sA = reinterpret_cast<Tile>(sm), sB = sA + TS;
+  const int p = blockIdx.x;
+  const MidProb P = a.probs[p];
+  const MidPostProb Q = q.pp[p];
+  if ((int)blockIdx.y >= mid_tiles(Q.mb)) return;
+  int A, B;
+  mid_tile_of((int)blockIdx.y, &A, &B);
+  const int64_t ld = P.Mp, m = Q.m;
+  double* cov = q.base + Q.cov;
+  const bool failed = a.status[p] != 0;
+  double4v acc[4];
+  acc_zero(acc);
+  if (!failed) {
+    const double* V = q.base + Q.V;
+    for (int k = 0; k < P.nb; ++k) {
+      const int cols = P.n - k * TS;
+      if (cols <= 0) break;
+      __syncthreads();
+      stage_cols(sA, V + (int64_t)A * TS * ld + k * TS, ld, cols);
+      stage_cols(sB, V + (int64_t)B * TS * ld + k * TS, ld, cols);
+      __syncthreads();
+      mma_nt(acc, sA, sB);
+    }
+  }
+  const HypDev h = mid_hyp(P, a.base);
+  const double* t = q.base + Q.t;
+  const double* var = q.base + Q.var;
+  acc_each(acc, [&](int r, int c, double s) {
+    const int64_t i = TS * A + r, j = TS * B + c;
+    if (i >= m || j > i) return;
+    double v = __builtin_nan("");
+    if (!failed) {
+      const double* ti = t + 3 * i;
+      const double* tj = t + 3 * j;
+      v = i == j ? var[i] : kernel_ref(h, ti[0], ti[1], ti[2], tj[0], tj[1], tj[2]) - s;
+    }
+    cov[i * m + j] = v;
+    cov[j * m + i] = v;
+  });
+}
+
+int launch_mid(lfm_ctx* ctx, const MidLaunch& l, MidArgs a, const MidPostArgs* q = nullptr) {
   static const bool attrs = [] {
     for (const void* f : {reinterpret_cast<const void*>(&mid_column_kernel),
                           reinterpret_cast<const void*>(&mid_invert_kernel),
-                          reinterpret_cast<const void*>(&mid_sinv_kernel)})
+                          reinterpret_cast<const void*>(&mid_sinv_kernel),
+                          reinterpret_cast<const void*>(&mid_solve_kernel),
+                          reinterpret_cast<const void*>(&mid_cov_kernel)})
       hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)MID_LDS);
     return true;
   }();
@@ -502,7 +694,7 @@ int launch_mid(lfm_ctx* ctx, const MidLaunch& l, MidArgs a) {
   switch (l.kind) {
     case MID_FILL:
       prof_begin(ctx, K_MID_FILL, &ev);
-      hipLaunchKernelGGL(mid_fill_kernel, grid, block, 0, ctx->stream, a);
+      hipLaunchKernelGGL(mid_fill_kernel<false>, grid, block, 0, ctx->stream, a, MidNoPost{});
       prof_end(ctx, K_MID_FILL, ev, 0, 0);
       what = "mid_fill_kernel";
       break;
@@ -541,6 +733,24 @@ int launch_mid(lfm_ctx* ctx, const MidLaunch& l, MidArgs a) {
       hipLaunchKernelGGL(mid_grad_kernel, grid, block, 0, ctx->stream, a);
       prof_end(ctx, K_MID_FINISH, ev, 0, 0);
       what = "mid_grad_kernel";
+      break;
+    case MID_POST_FILL:
+      prof_begin(ctx, K_MID_FILL, &ev);
+      hipLaunchKernelGGL(mid_fill_kernel<true>, grid, block, 0, ctx->stream, a, *q);
+      prof_end(ctx, K_MID_FILL, ev, 0, 0);
+      what = "mid_fill_kernel (posterior)";
+      break;
+    case MID_SOLVE:
+      prof_begin(ctx, K_MID_INVERSE, &ev);
+      hipLaunchKernelGGL(mid_solve_kernel, grid, block, MID_LDS, ctx->stream, a, *q);
+      prof_end(ctx, K_MID_INVERSE, ev, 0, 0);
+      what = "mid_solve_kernel";
+      break;
+    case MID_COV:
+      prof_begin(ctx, K_MID_FINISH, &ev);
+      hipLaunchKernelGGL(mid_cov_kernel, grid, block, MID_LDS, ctx->stream, a, *q);
+      prof_end(ctx, K_MID_FINISH, ev, 0, 0);
+      what = "mid_cov_kernel";
       break;
     default:
       return set_err(ctx, LFM_E_STATE, "plan_mid: unknown launch kind");
@@ -584,6 +794,68 @@ int mid_call(lfm_ctx* ctx, lfm_mbatch* b, const double* hyp, int negative, bool 
   return batch_status(ctx, hst, np, status);
 }
 
+// One posterior call: the hyperparameters into the first arena, the diagonal and the test inputs
+// into the second (grown here when this call needs more), the plan's launches, the outputs down.
+int mid_post_call(lfm_ctx* ctx, lfm_mbatch* b, const MidPostPlan& Q, const double* hyp,
+                  const double* diag_vec, const double* diag_add, const double* t, double* mean,
+                  double* var, double* cov, int* status) {
+  DeviceGuard g(ctx->device);
+  DeviceTenancy tenancy(ctx, false);  // shared
+  const MidPlan& P = b->plan;
+  const int64_t np = P.nprob, nh = P.nhyp;
+  if (b->pbytes < Q.bytes) {
+    // every call on the handle is synchronous: nothing of the old arena is in flight
+    if (b->pmem) hipFree(b->pmem);
+    b->pmem = nullptr;
+    b->pbytes = 0;
+    const hipError_t e = hipMalloc((void**)&b->pmem, Q.bytes);
+    if (e != hipSuccess) {
+      b->pmem = nullptr;
+      (void)hipGetLastError();
+      return set_err(ctx, LFM_E_OOM, "lfm_mbatch_posterior_f64: " + std::to_string(Q.bytes) +
+                                         " bytes of device memory: " + hipGetErrorString(e));
+    }
+    b->pbytes = Q.bytes;
+  }
+  double* base = reinterpret_cast<double*>(b->dmem);
+  double* pbase = reinterpret_cast<double*>(b->pmem);
+  std::memcpy(b->hbuf, hyp, (size_t)nh * 8);
+  hipError_t e = hipMemcpyAsync(base + P.hyp, b->hbuf, (size_t)nh * 8, hipMemcpyHostToDevice,
+                                ctx->stream);
+  if (e == hipSuccess)
+    e = hipMemcpyAsync(pbase + Q.dadd, diag_add, (size_t)np * 8, hipMemcpyHostToDevice, ctx->stream);
+  if (e == hipSuccess && diag_vec)
+    e = hipMemcpyAsync(pbase + Q.dv, diag_vec, (size_t)Q.sn * 8, hipMemcpyHostToDevice, ctx->stream);
+  if (e == hipSuccess)
+    e = hipMemcpyAsync(pbase + Q.t, t, (size_t)Q.sm * 24, hipMemcpyHostToDevice, ctx->stream);
+  if (e == hipSuccess)
+    e = hipMemcpyAsync(b->pmem + Q.table, Q.pp.data(), (size_t)np * sizeof(MidPostProb),
+                       hipMemcpyHostToDevice, ctx->stream);
+  if (e != hipSuccess) return hip_fail(ctx, e, "lfm_mbatch_posterior_f64: upload");
+  MidArgs a{};
+  a.probs = reinterpret_cast<const MidProb*>(b->dmem + P.table);
+  a.base = base;
+  a.status = reinterpret_cast<int*>(b->dmem + P.status);
+  MidPostArgs q{};
+  q.pp = reinterpret_cast<const MidPostProb*>(b->pmem + Q.table);
+  q.base = pbase;
+  q.dadd = Q.dadd;
+  q.maxtiles = Q.maxtiles;
+  for (const MidLaunch& l : Q.launches)
+    if (int r = launch_mid(ctx, l, a, &q)) return r;
+  int* hst = reinterpret_cast<int*>(b->hbuf + b->h_status);
+  e = hipMemcpyAsync(mean, pbase + Q.mean, (size_t)Q.sm * 8, hipMemcpyDeviceToHost, ctx->stream);
+  if (e == hipSuccess && var)
+    e = hipMemcpyAsync(var, pbase + Q.var, (size_t)Q.sm * 8, hipMemcpyDeviceToHost, ctx->stream);
+  if (e == hipSuccess && cov)
+    e = hipMemcpyAsync(cov, pbase + Q.cov, (size_t)Q.sc * 8, hipMemcpyDeviceToHost, ctx->stream);
+  if (e == hipSuccess)
+    e = hipMemcpyAsync(hst, a.status, (size_t)np * sizeof(int), hipMemcpyDeviceToHost, ctx->stream);
+  if (e != hipSuccess) return hip_fail(ctx, e, "lfm_mbatch_posterior_f64: download");
+  if (int r = finish(ctx)) return r;
+  return batch_status(ctx, hst, np, status);
+}
+
 }  // namespace
 
 }  // namespace lfm
@@ -603,6 +875,7 @@ int lfm_mbatch_create(lfm_ctx* ctx, int64_t nprob, const lfm_problem* probs, lfm
   }
   std::unique_ptr<lfm_mbatch> b(new lfm_mbatch);
   b->plan = plan_mid(shapes);
+  b->shapes = shapes;
   const MidPlan& P = b->plan;
   if (P.reject) return set_err(ctx, LFM_E_ARG, P.why);
   DeviceGuard g(ctx->device);
@@ -646,6 +919,7 @@ int lfm_mbatch_destroy(lfm_mbatch* batch) {
   if (!batch) return LFM_E_ARG;
   hipSetDevice(batch->device);
   hipFree(batch->dmem);  // every call on the handle is synchronous: nothing of it is in flight
+  if (batch->pmem) hipFree(batch->pmem);
   hipHostFree(batch->hbuf);
   delete batch;
   return LFM_OK;
@@ -672,6 +946,20 @@ int lfm_mbatch_mll_grad_f64(lfm_ctx* ctx, lfm_mbatch* batch, const double* hyp, 
     return set_err(ctx, LFM_E_ARG, "batch / hyp / value / grad is NULL");
   if (batch->device != ctx->device) return set_err(ctx, LFM_E_ARG, "batch of another device");
   return mid_call(ctx, batch, hyp, negative, true, value, grad, status);
+}
+
+int lfm_mbatch_posterior_f64(lfm_ctx* ctx, lfm_mbatch* batch, const double* hyp,
+                             const double* diag_vec, const double* diag_add, const int64_t* m,
+                             const double* t, double* mean, double* var, double* cov,
+                             int* status) {
+  if (!ctx) return LFM_E_ARG;
+  if (!batch || !hyp || !diag_add || !m || !t || !mean)
+    return set_err(ctx, LFM_E_ARG, "batch / hyp / diag_add / m / t / mean is NULL");
+  if (!var && !cov) return set_err(ctx, LFM_E_ARG, "one of var / cov must be given");
+  if (batch->device != ctx->device) return set_err(ctx, LFM_E_ARG, "batch of another device");
+  const MidPostPlan Q = plan_mid_post(batch->shapes, m, diag_vec != nullptr, cov != nullptr);
+  if (Q.reject) return set_err(ctx, LFM_E_ARG, Q.why);
+  return mid_post_call(ctx, batch, Q, hyp, diag_vec, diag_add, t, mean, var, cov, status);
 }
 
 }  // extern "C"

@@ -67,7 +67,15 @@ struct MidProb {
 //   MID_SINV    lower tile u of W = S^{-1} = X^T X
 //   MID_PAIRS   lower tile u's partial sums
 //   MID_GRAD    the problem's gradient (u = 0)
-enum MidKind { MID_FILL = 0, MID_COLUMN, MID_VALUE, MID_INVERT, MID_SINV, MID_PAIRS, MID_GRAD };
+// and of a posterior call (plan_mid_post), with mb = ceil(m / 64) blocks of test rows:
+//   MID_POST_FILL  u < maxtiles: lower tile u of S, with the posterior's diagonal;
+//                  u - maxtiles = tb * nb + k: tile (tb, k) of T = K(t, x) in the problem's V
+//   MID_SOLVE      block row u of V = T L^{-T}, and the mean and variance of its 64 test rows
+//   MID_COV        lower tile u of the covariance (and its mirror image)
+enum MidKind {
+  MID_FILL = 0, MID_COLUMN, MID_VALUE, MID_INVERT, MID_SINV, MID_PAIRS, MID_GRAD,
+  MID_POST_FILL, MID_SOLVE, MID_COV
+};
 struct MidLaunch {
   int kind, k;
   unsigned gx, gy;
@@ -93,5 +101,40 @@ int64_t mid_problem_doubles(int64_t n);
 // Rejections in order: no problems; too many; an n outside [1, MID_MAX_N]; a G outside [1, n] or
 // that does not divide n (the first offending problem, named in `why`)
 MidPlan plan_mid(const std::vector<MidShape>& shapes);
+
+// ---------------------------------------------------------------- the posterior call
+// lfm_mbatch_posterior_f64 works in a second device arena that the handle owns (allocated at the
+// first posterior call, regrown when a call needs more). In doubles from its base: diag_add
+// [nprob], diag_vec [sum n] (when given), t [sum m x 3], each problem's V buffer — 64 mb rows of
+// Mp doubles, row-major: T = K(t, x) after the fill, V = T L^{-T} after the solve, column n of it
+// -V z — then mean [sum m], var [sum m] and, when asked, cov [sum m^2], packed as the caller
+// gets them; the per-problem table follows. Bytes per problem: 8 (64 mb Mp + 5 m + n + 1), plus
+// 8 m^2 with the covariance. tests/native/mid_post_plan_check.cpp checks the plan by enumeration
+// under the sanitizers.
+constexpr int MID_MAX_M = 4096;  // LFM_MID_MAX_M
+
+// One problem's entry of the posterior table. Offsets in doubles from the second arena's base;
+// dv / cov are -1 when the call has none.
+struct MidPostProb {
+  int m, mb;
+  int64_t dv, t, V, mean, var, cov;
+};
+
+struct MidPostPlan {
+  enum Reject { OK = 0, NO_ROWS, BAD_M, TOO_MANY_ROWS };
+  int reject = OK;
+  std::string why;
+  int64_t nprob = 0, sn = 0, sm = 0, sc = 0;  // sums of n, m and m^2
+  int maxnb = 0, maxtiles = 0, maxmb = 0, maxunits = 0, maxcov = 0;
+  std::vector<MidPostProb> pp;
+  int64_t dadd = 0, dv = -1, t = 0, mean = 0, var = 0, cov = -1, doubles = 0;
+  size_t table = 0, bytes = 0;
+  std::vector<MidLaunch> launches;  // in stream order: maxnb + 2, one more with the covariance
+};
+
+// Rejections, per problem in order and within a problem in this order: m < 1; m no multiple of
+// G; m > MID_MAX_M (the first offending problem and the limit are named in `why`)
+MidPostPlan plan_mid_post(const std::vector<MidShape>& shapes, const int64_t* m, bool has_dv,
+                          bool want_cov);
 
 }  // namespace lfm

@@ -8,6 +8,9 @@ every problem is registered in HBM once (``lfm_batch_create``) and one
 ``lfm_batch_posterior_f64`` call evaluates every problem at its own test inputs. The assembly of
 the returned ``GaussianDistribution`` is ``ExactLFM.latent_predict`` / ``multi_gene_predict``'s.
 
+``MidBatchPredictor`` is the same for problems of up to 1024 rows each
+(``lfm_mbatch_posterior_f64`` on ``farm.MidBatchEvaluator``'s handle).
+
 ``Posterior`` is the large-N counterpart: one fitted model whose factor stays resident in HBM
 (``lfm_post_create``) and is evaluated at many sets of test inputs (``lfm_post_predict_f64``).
 """
@@ -68,51 +71,11 @@ def unpack_outputs(m, mean, var=None, cov=None):
     return out
 
 
-# ------------------------------------------------------------------ the predictor
-class BatchPredictor:
-    """``latent_predict`` / ``multi_gene_predict`` of P (model, training data) problems in one
-    call each. ``train_datas``: the P53-style data objects ``ExactLFM.latent_predict`` takes
-    (``dataset_3d`` is applied to each; n <= 127 per problem). ``models`` (one ExactLFM per
-    problem, e.g. ``BatchTrainer.fit``'s) are read at every call. ``status`` holds the last
-    call's per-problem codes (LFM_E_NOT_PD: that problem's outputs are NaN, as under JAX)."""
-
-    def __init__(self, train_datas, ctx=None):
-        from .dataset import Dataset, dataset_3d
-        from .farm import BatchEvaluator
-
-        self.ctx = ctx or _lib.get_context()
-        datasets, var = [], []
-        for d in train_datas:
-            x, y, v = dataset_3d(d)
-            datasets.append(Dataset(as_f64(x).reshape(-1, 3), as_f64(y).reshape(-1, 1)))
-            var.append(as_f64(v).reshape(-1))
-        if not datasets:
-            raise ValueError("no training data")
-        self.variances = np.ascontiguousarray(np.concatenate(var))
-        self._ev = BatchEvaluator(self.ctx, datasets)
-        self.status = np.zeros(len(datasets), np.int32)
-
-    def __len__(self):
-        return len(self._ev.datasets)
-
-    def _posterior(self, models, test_inputs, diag_add, want_cov):
-        models = list(models)
-        if len(models) != len(self):
-            raise ValueError("one model per registered problem")
-        genes = [int(mm.num_genes) for mm in models]
-        t, m = pack_test_inputs(test_inputs, genes)
-        hyp = self._ev.pack(models)  # lfm_batch_mll_f64's layout; registers this gene layout
-        batch = self._ev.batch
-        dadd = as_f64(diag_add).reshape(-1)
-        mean = np.empty(int(m.sum()))
-        var = np.empty_like(mean)
-        cov = np.empty(int((m * m).sum())) if want_cov else None
-        self.status = np.zeros(len(models), np.int32)
-        rc = self.ctx.lib.lfm_batch_posterior_f64(
-            self.ctx.handle, batch, dptr(hyp), dptr(self.variances), dptr(dadd), dptr(m), dptr(t),
-            dptr(mean), dptr(var), dptr(cov) if want_cov else None, dptr(self.status))
-        self.ctx.check(rc, allow_not_pd=True)
-        return unpack_outputs(m, mean, var, cov)
+# ------------------------------------------------------------------ the predictors
+class _Assembly:
+    """The ``GaussianDistribution``s and marginals of ``ExactLFM.latent_predict`` /
+    ``multi_gene_predict`` from a batched posterior: ``_posterior(models, test_inputs, diag_add,
+    want_cov)`` returns per problem (mean, var, cov or None)."""
 
     def latent_predict(self, models, test_inputs):
         """model.py:420-465 per problem: S = K(x,x) + diag(variances) + jitter I;
@@ -154,8 +117,122 @@ class BatchPredictor:
             return [(mean, var + mm.jitter) for (mean, var, _), mm in zip(res, models)]
         raise ValueError('kind must be "latent" or "gene"')
 
+
+def _training_sets(train_datas):
+    """``dataset_3d`` of every data object: ([Dataset], the variances packed in problem order)."""
+    from .dataset import Dataset, dataset_3d
+
+    datasets, var = [], []
+    for d in train_datas:
+        x, y, v = dataset_3d(d)
+        datasets.append(Dataset(as_f64(x).reshape(-1, 3), as_f64(y).reshape(-1, 1)))
+        var.append(as_f64(v).reshape(-1))
+    if not datasets:
+        raise ValueError("no training data")
+    return datasets, np.ascontiguousarray(np.concatenate(var))
+
+
+class BatchPredictor(_Assembly):
+    """``latent_predict`` / ``multi_gene_predict`` of P (model, training data) problems in one
+    call each. ``train_datas``: the P53-style data objects ``ExactLFM.latent_predict`` takes
+    (``dataset_3d`` is applied to each; n <= 127 per problem). ``models`` (one ExactLFM per
+    problem, e.g. ``BatchTrainer.fit``'s) are read at every call. ``status`` holds the last
+    call's per-problem codes (LFM_E_NOT_PD: that problem's outputs are NaN, as under JAX)."""
+
+    def __init__(self, train_datas, ctx=None):
+        from .farm import BatchEvaluator
+
+        self.ctx = ctx or _lib.get_context()
+        datasets, self.variances = _training_sets(train_datas)
+        self._ev = BatchEvaluator(self.ctx, datasets)
+        self.status = np.zeros(len(datasets), np.int32)
+
+    def __len__(self):
+        return len(self._ev.datasets)
+
+    def _posterior(self, models, test_inputs, diag_add, want_cov):
+        models = list(models)
+        if len(models) != len(self):
+            raise ValueError("one model per registered problem")
+        genes = [int(mm.num_genes) for mm in models]
+        t, m = pack_test_inputs(test_inputs, genes)
+        hyp = self._ev.pack(models)  # lfm_batch_mll_f64's layout; registers this gene layout
+        batch = self._ev.batch
+        dadd = as_f64(diag_add).reshape(-1)
+        mean = np.empty(int(m.sum()))
+        var = np.empty_like(mean)
+        cov = np.empty(int((m * m).sum())) if want_cov else None
+        self.status = np.zeros(len(models), np.int32)
+        rc = self.ctx.lib.lfm_batch_posterior_f64(
+            self.ctx.handle, batch, dptr(hyp), dptr(self.variances), dptr(dadd), dptr(m), dptr(t),
+            dptr(mean), dptr(var), dptr(cov) if want_cov else None, dptr(self.status))
+        self.ctx.check(rc, allow_not_pd=True)
+        return unpack_outputs(m, mean, var, cov)
+
     def close(self):
         self._ev.close()
+
+
+class MidBatchPredictor(_Assembly):
+    """``BatchPredictor`` for problems of any size 1 <= n <= 1024 — the predict half of
+    ``trainer.MidBatchTrainer``'s workflow: one ``lfm_mbatch_posterior_f64`` call evaluates every
+    problem at its own test inputs (at most 4096 rows each), in a number of launches that depends
+    on the largest n alone. ``train_datas`` as ``BatchPredictor``'s; the problems are registered
+    through ``farm.MidBatchEvaluator``. With ``evaluator=`` (``MidBatchTrainer.evaluator``) that
+    handle is used and the data is not uploaded a second time; its x / y must be the data's,
+    else ValueError. The context may be asked for as late as the first call."""
+
+    MAX_M = 4096  # LFM_MID_MAX_M
+
+    def __init__(self, train_datas, ctx=None, evaluator=None):
+        from .farm import MidBatchEvaluator
+
+        datasets, self.variances = _training_sets(train_datas)
+        self._own = evaluator is None
+        if evaluator is None:
+            evaluator = MidBatchEvaluator(ctx, datasets)
+        else:
+            if len(evaluator.datasets) != len(datasets):
+                raise ValueError("the evaluator holds another number of problems")
+            for i, (d, e) in enumerate(zip(datasets, evaluator.datasets)):
+                ex = np.asarray(e.X, np.float64)
+                ey = np.asarray(e.y, np.float64).reshape(-1)
+                if ex.shape != d.X.shape or not np.array_equal(ex, d.X) or \
+                        not np.array_equal(ey, np.asarray(d.y).reshape(-1)):
+                    raise ValueError(f"problem {i}: the evaluator's x / y differ from the data's")
+        self._ev = evaluator
+        self.ctx = ctx or evaluator.ctx
+        self.status = np.zeros(len(datasets), np.int32)
+
+    def __len__(self):
+        return len(self._ev.datasets)
+
+    def _posterior(self, models, test_inputs, diag_add, want_cov):
+        models = list(models)
+        if len(models) != len(self):
+            raise ValueError("one model per registered problem")
+        genes = [int(mm.num_genes) for mm in models]
+        t, m = pack_test_inputs(test_inputs, genes)
+        if np.any(m > self.MAX_M):
+            raise ValueError(f"at most {self.MAX_M} test rows per problem (LFM_MID_MAX_M); use "
+                             "Posterior for more on one model")
+        self._ev._pack(models)  # the packed hyperparameters; registers this gene layout
+        self.ctx = self.ctx or self._ev.ctx
+        dadd = as_f64(diag_add).reshape(-1)
+        mean = np.empty(int(m.sum()))
+        var = np.empty_like(mean)
+        cov = np.empty(int((m * m).sum())) if want_cov else None
+        self.status = np.zeros(len(models), np.int32)
+        rc = self.ctx.lib.lfm_mbatch_posterior_f64(
+            self.ctx.handle, self._ev.batch, dptr(self._ev._buf), dptr(self.variances),
+            dptr(dadd), dptr(m), dptr(t), dptr(mean), dptr(var),
+            dptr(cov) if want_cov else None, dptr(self.status))
+        self.ctx.check(rc, allow_not_pd=True)
+        return unpack_outputs(m, mean, var, cov)
+
+    def close(self):
+        if self._own:
+            self._ev.close()
 
 
 # ------------------------------------------------------------------ the resident posterior

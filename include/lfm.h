@@ -240,6 +240,59 @@ int lfm_mbatch_mll_f64(lfm_ctx* ctx, lfm_mbatch* batch, const double* hyp, int n
                        double* out, int* status);
 int lfm_mbatch_mll_grad_f64(lfm_ctx* ctx, lfm_mbatch* batch, const double* hyp, int negative,
                             double* value, double* grad, int* status);
+/* latent_predict / multi_gene_predict (model.py:420-514) of every problem of an lfm_mbatch at its
+ * own test inputs: lfm_batch_posterior_f64 for problems of any mix of sizes 1 <= n <= 1024, the
+ * predict half of the workflow whose fits lfm_mbatch_mll_grad_f64 serves. Per problem p:
+ *   S_p = (K(x_p,x_p) + diag(diag_vec_p)) + diag_add[p] I   (the terms are added in this order:
+ *         the kernel's diagonal entry, then diag_vec's, then diag_add; a NULL diag_vec adds 0.0),
+ *   mean = m(t_p) + K(t_p,x_p) S_p^{-1} (y_p - m(x_p)),  cov = K(t_p,t_p) - K(t_p,x_p) S_p^{-1} K(x_p,t_p),
+ *   var = diag(cov).
+ * Arguments, packed layouts and semantics are lfm_batch_posterior_f64's: hyp in the packed layout
+ * of lfm_mbatch_mll_f64, of which only D, S, B and l are read (the obs_stddev / jitter slots are
+ * ignored: the callers' diagonal is applied by the shim, dis_project_amd.predict.
+ * MidBatchPredictor); diag_vec packed [sum n_p] or NULL; diag_add [nprob]; m [nprob]; t packed
+ * [sum m_p x 3], gene indices truncating, wrapping and clamping as those of x, any mix of flags;
+ * mean / var packed [sum m_p]; cov packed [sum m_p^2], each problem's dense row-major m_p x m_p;
+ * status [nprob] optional. var or cov may be NULL, not both: with cov == NULL no off-diagonal
+ * K(t,t) entry is evaluated and nothing of size m^2 is allocated. A NULL required pointer, a
+ * handle of another device, or an m_p outside 1 <= m_p <= LFM_MID_MAX_M or with m_p % G_p != 0 is
+ * LFM_E_ARG (the message names the limit).
+ *
+ * LFM_MID_MAX_M bounds the handle's memory, as LFM_MID_MAX_N does: the call works in a second
+ * device arena that the handle owns (allocated at the first posterior call, regrown when a call
+ * needs more, freed by lfm_mbatch_destroy; never the ctx workspace), per problem
+ * 8 (64 ceil(m_p / 64) Mp_p + 5 m_p + n_p + 1) bytes, Mp_p = 64 ceil((n_p + 1) / 64), plus
+ * 8 m_p^2 with the covariance (at the caps: 36 MB and 134 MB). A failed allocation is LFM_E_OOM
+ * and the handle stays usable. For more test rows on one model use lfm_post_*.
+ *
+ * Launches: ceil((n_max + 1) / 64) + 2 without cov and one more with it, whatever the problem
+ * count and the m's: the fill (S, and T = K(t,x) spread over the grid), the factorisation's
+ * column launches, one solve launch over every 64-row block of test points of every problem
+ * (V = T L^{-T} on the fp64 MFMA, the mean and the variance), and the covariance's tiles.
+ *
+ * A problem that is not positive definite gets NaN outputs and its status, and the call returns
+ * LFM_E_NOT_PD; every other problem's outputs are valid and the same bits as without it. No
+ * atomics, no device-side waits and no cooperative launch: the same inputs give the same bits, and
+ * a problem's bits depend on its own data, hyperparameters and test inputs alone, not on the
+ * other problems, their sizes or its position. A test point's variance and its row of
+ * K(t,x) L^{-T} depend on its own row of t alone, not on m_p (the mean also on the point's index
+ * and m_p, through mean_function's block position). cov is exactly symmetric; when both are given
+ * var is diag(cov) bit for bit; mean and var are the same bits whether or not cov is requested.
+ * Synchronous; holds the device's lock shared. A posterior call and an MLL / gradient call on the
+ * same handle share S, L and the block inverses; each call refills what it reads, so interleaving
+ * them changes no bits of either.
+ *
+ * Measured (scripts/mid_predict_rate.py, profiles/mid_predict.json, mid_predict_p4.json; m = 100):
+ * with 15 problems the batch is ahead of the per-problem lfm_posterior_f64 loop at every size
+ * (latent marginals 11.2x at n = 160, 6.5x at 320, 4.6x at 640, 2.9x at 1020; with the covariance
+ * 8.5x, 5.7x, 3.7x, 2.9x). A call's time is set by the largest n, hardly by the problem count:
+ * with 4 problems the batch still leads up to n = 640 (marginals 3.6x at 160, 2.1x at 320, 1.25x
+ * at 640; with the covariance 2.4x, 1.6x, 1.08x) and the loop is the faster one at n = 1020
+ * (0.90x and 0.88x). */
+#define LFM_MID_MAX_M 4096
+int lfm_mbatch_posterior_f64(lfm_ctx* ctx, lfm_mbatch* batch, const double* hyp,
+                             const double* diag_vec, const double* diag_add, const int64_t* m,
+                             const double* t, double* mean, double* var, double* cov, int* status);
 
 /* optax.adam(learning_rate, b1, b2, eps, eps_root) and JaxTrainer.fit's epoch handling
  * (src/trainer.py:162-228; src/main.py:45 and notebook.py:55 use adam(0.01)). */
