@@ -735,4 +735,41 @@ MidPostPlan plan_mid_post(const std::vector<MidShape>& shapes, const int64_t* m,
   return P;
 }
 
+MidFitPlan plan_mid_fit(const std::vector<MidShape>& shapes, int64_t nsteps) {
+  MidFitPlan F;
+  auto rejected = [&](int code, const std::string& why) {
+    F.reject = code;
+    F.why = why;
+    return F;
+  };
+  const MidPlan P = plan_mid(shapes);
+  if (P.reject) return rejected(MidFitPlan::BAD_BATCH, P.why);
+  if (nsteps < 1) return rejected(MidFitPlan::NO_STEPS, "lfm_mbatch_fit_f64: nsteps = " +
+                                                            std::to_string(nsteps) + ", needs >= 1");
+  if (nsteps > MID_FIT_MAX_STEPS)
+    return rejected(MidFitPlan::TOO_MANY_STEPS,
+                    "lfm_mbatch_fit_f64: nsteps = " + std::to_string(nsteps) + ", past " +
+                        std::to_string(MID_FIT_MAX_STEPS) + " a call; resume with step0");
+  F.nprob = P.nprob;
+  F.nhyp = P.nhyp;
+  F.nsteps = nsteps;
+  F.raw = 0;
+  F.mu = F.raw + even(F.nhyp);
+  F.nu = F.mu + even(F.nhyp);
+  F.bias = F.nu + even(F.nhyp);
+  F.hist = F.bias + 2 * nsteps;
+  F.doubles = F.hist + even(nsteps * F.nprob);
+  F.first_bad = (size_t)F.doubles * sizeof(double);
+  F.bytes = F.first_bad + ((size_t)F.nprob * sizeof(int) + 15) / 16 * 16;
+  const unsigned gx = (unsigned)F.nprob;
+  F.per_step = P.value_grad.size() + 1;
+  F.launches.reserve(1 + (size_t)nsteps * F.per_step);
+  F.launches.push_back({MID_CONSTRAIN, 0, gx, 1u});
+  for (int64_t s = 0; s < nsteps; ++s) {
+    F.launches.insert(F.launches.end(), P.value_grad.begin(), P.value_grad.end());
+    F.launches.push_back({MID_ADAM, (int)s, gx, 1u});
+  }
+  return F;
+}
+
 }  // namespace lfm

@@ -72,9 +72,14 @@ struct MidProb {
 //                  u - maxtiles = tb * nb + k: tile (tb, k) of T = K(t, x) in the problem's V
 //   MID_SOLVE      block row u of V = T L^{-T}, and the mean and variance of its 64 test rows
 //   MID_COV        lower tile u of the covariance (and its mirror image)
+// and of a fit call (plan_mid_fit), u = 0 alone:
+//   MID_CONSTRAIN  the problem's constrained hyperparameters from its unconstrained ones, before
+//                  step 0 (and its first-bad-step word cleared)
+//   MID_ADAM       step k's loss and first-bad-step word, the problem's Adam update and the next
+//                  step's constrained hyperparameters
 enum MidKind {
   MID_FILL = 0, MID_COLUMN, MID_VALUE, MID_INVERT, MID_SINV, MID_PAIRS, MID_GRAD,
-  MID_POST_FILL, MID_SOLVE, MID_COV
+  MID_POST_FILL, MID_SOLVE, MID_COV, MID_CONSTRAIN, MID_ADAM
 };
 struct MidLaunch {
   int kind, k;
@@ -136,5 +141,32 @@ struct MidPostPlan {
 // G; m > MID_MAX_M (the first offending problem and the limit are named in `why`)
 MidPostPlan plan_mid_post(const std::vector<MidShape>& shapes, const int64_t* m, bool has_dv,
                           bool want_cov);
+
+// ---------------------------------------------------------------- the fit call
+// lfm_mbatch_fit_f64 works in a third device arena that the handle owns (allocated at the first
+// fit call, regrown when a call needs more). In doubles from its base, each region rounded up to
+// 2 doubles (16-byte alignment): raw, mu, nu [nhyp] each in the packed hyperparameters' layout,
+// the bias corrections [2 nsteps] (c1, c2 of each step), history [nsteps x nprob]; then, in bytes,
+// the first-bad-step words [nprob]. With e(d) = 2 ceil(d / 2):
+//   bytes = 8 (3 e(nhyp) + 2 nsteps + e(nsteps nprob)) + 16 ceil(nprob / 4).
+// The launch list: MID_CONSTRAIN, then per step s the value-and-gradient launches of plan_mid
+// (MidPlan::value_grad, unchanged) followed by MID_ADAM with k = s: 1 + nsteps (maxnb + 7) launches.
+// tests/native/mid_fit_plan_check.cpp checks the plan by enumeration under the sanitizers.
+constexpr int64_t MID_FIT_MAX_STEPS = 1 << 16;  // one call's steps (a longer fit resumes: step0)
+
+struct MidFitPlan {
+  enum Reject { OK = 0, BAD_BATCH, NO_STEPS, TOO_MANY_STEPS };
+  int reject = OK;
+  std::string why;
+  int64_t nprob = 0, nhyp = 0, nsteps = 0;
+  int64_t raw = 0, mu = 0, nu = 0, bias = 0, hist = 0, doubles = 0;
+  size_t first_bad = 0, bytes = 0;
+  size_t per_step = 0;              // launches of one step: the value-and-gradient call's + 1
+  std::vector<MidLaunch> launches;  // in stream order
+};
+
+// Rejections in order: shapes that plan_mid rejects (its message); nsteps < 1; nsteps >
+// MID_FIT_MAX_STEPS (the limit is named in `why`)
+MidFitPlan plan_mid_fit(const std::vector<MidShape>& shapes, int64_t nsteps);
 
 }  // namespace lfm

@@ -11,6 +11,7 @@
 //   small_post_kernel, small_post_cov_kernel
 //                             latent_predict / multi_gene_predict (src/model.py:420-514) of every
 //                             problem at its own test inputs (lfm_batch_posterior_f64).
+#include "lfm_bijectors.h"
 #include "lfm_dual.h"
 #include <mutex>
 
@@ -1286,16 +1287,8 @@ __global__ __launch_bounds__(256) void small_grad_kernel_args(SmallArgs a) {
 //   after_epoch (trainer.py:133-160, 205-210): every num_steps_per_epoch steps (step 0
 //     included), if fix_params, raw true_s[3] = 1.0 and raw true_d[3] = 0.8 (the unconstrained
 //     leaves: the reference's quirk; no-op for G <= 3, as JAX drops out-of-bounds updates)
-// The jitter slot holds the static jitter (constrained) and is never updated.
-__device__ __forceinline__ double softplus_d(double x) {
-  // np.logaddexp(0, x): x + log1p(exp(-x)) for x >= 0, log1p(exp(x)) below
-  return x >= 0.0 ? x + log1p(exp(-x)) : log1p(exp(x));
-}
-__device__ __forceinline__ double sigmoid_d(double x) {
-  const double e = exp(-fabs(x));
-  return x >= 0.0 ? 1.0 / (1.0 + e) : e / (1.0 + e);
-}
-
+// The jitter slot holds the static jitter (constrained) and is never updated. softplus_d and
+// sigmoid_d: lfm_bijectors.h.
 __global__ __launch_bounds__(256) void small_fit_kernel(SmallFitLaunch a) {
   #pragma clang fp contract(off)
   extern __shared__ __attribute__((aligned(16))) double sm[];

@@ -302,7 +302,8 @@ class MidBatchEvaluator:
     hyperparameters (``lfm_batch_mll_f64``'s layout) and evaluates every problem's MLL, or MLL
     and gradient, in a number of launches that depends on the largest n alone. Sizes may be
     mixed. Not PD -> NaN, with ``status``. A problem's bits depend on its own data and
-    hyperparameters alone. ``ctx`` may be None: the calling thread's context is then asked for
+    hyperparameters alone. ``fit_packed`` runs a whole Adam loop of every problem on the device
+    (``lfm_mbatch_fit_f64``). ``ctx`` may be None: the calling thread's context is then asked for
     at the first evaluation, after the shapes and ``num_genes`` have been checked."""
 
     MAX_N = 1024  # LFM_MID_MAX_N
@@ -385,6 +386,31 @@ class MidBatchEvaluator:
                                                   _lib.dptr(self.status))
         self.ctx.check(rc, allow_not_pd=True)
         return self._out.copy(), unpack_grads(grad, self._genes)
+
+    def fit_packed(self, raw, mu, nu, optim, fix_params, num_steps_per_epoch, step0, nsteps):
+        """``nsteps`` training steps of every problem on the device in one call
+        (``lfm_mbatch_fit_f64``), no host round trip between steps. ``raw`` (the unconstrained
+        parameters, ``trainer.pack_raw``), ``mu`` and ``nu`` (Adam's moments) are float64 arrays
+        of the registered layout (``registered(genes)``) and are updated in place; ``step0`` is
+        the number of steps already taken. Returns (history [nsteps, P], status [P]: 0, or
+        1 + the first step of this call whose factorisation failed — NaN from there on)."""
+        if self.batch is None:
+            raise ValueError("no registered batch: call registered(genes) first")
+        for a in (raw, mu, nu):
+            if not isinstance(a, np.ndarray) or a.dtype != np.float64 or \
+                    a.size != self._buf.size or not a.flags.c_contiguous:
+                raise ValueError("raw / mu / nu: packed float64 arrays of this batch's layout")
+        nsteps = int(nsteps)
+        hist = np.empty((max(nsteps, 0), len(self.datasets)))
+        st = np.zeros(len(self.datasets), np.int32)
+        opt = _lib.LfmAdam(optim.learning_rate, optim.b1, optim.b2, optim.eps, optim.eps_root,
+                           int(num_steps_per_epoch), int(bool(fix_params)))
+        rc = self.ctx.lib.lfm_mbatch_fit_f64(self.ctx.handle, self.batch, _lib.ctypes.byref(opt),
+                                             int(self.negative), int(step0), nsteps,
+                                             _lib.dptr(raw), _lib.dptr(mu), _lib.dptr(nu),
+                                             _lib.dptr(hist), _lib.dptr(st))
+        self.ctx.check(rc, allow_not_pd=True)
+        return hist, st
 
     def close(self):
         if self.batch is not None:

@@ -20,7 +20,10 @@ learning rate 0.01).
 ablation / replicate training runs (notebook.py:33-75, one JaxTrainer per problem; main.py:59)
 — with every step on the GPU: ``lfm_batch_fit_f64`` steps each problem's Adam loop inside one
 kernel launch (one workgroup per problem), with the same constrain / chain rule / adam /
-after_epoch arithmetic as this module's host loop.
+after_epoch arithmetic as this module's host loop. ``MidBatchTrainer`` does the same for problems
+of up to 1024 rows: on the host loop around one batched value-and-gradient call per step, or,
+with ``on_device=True``, in one ``lfm_mbatch_fit_f64`` call with no host round trip between
+steps.
 """
 
 from __future__ import annotations
@@ -311,7 +314,15 @@ class MidBatchTrainer:
     rule, ``optim.update`` / ``apply_updates`` — and ``after_epoch`` exactly as ``JaxTrainer.fit``
     orders them. ``objective`` is a ``CustomConjMLL`` (its ``negative``). ``evaluator`` replaces
     the GPU evaluator (anything with ``value_and_grad(models) -> (values, [grad dicts])``): the
-    host loop then needs no device."""
+    host loop then needs no device.
+
+    ``on_device=True`` runs the whole loop on the GPU instead, as ``BatchTrainer`` does for
+    small problems: ``fit`` packs the unconstrained parameters, makes ONE
+    ``evaluator.fit_packed`` call (``lfm_mbatch_fit_f64``: per step the batched value-and-
+    gradient launches and one update launch, no host round trip between steps) and unpacks.
+    ``status[p]`` is then 0, or 1 + the first step whose factorisation failed. A caller-supplied
+    ``evaluator`` must offer ``fit_packed`` and ``registered``
+    (``farm.MidBatchEvaluator``)."""
 
     models: Sequence[ExactLFM]
     objective: Any
@@ -322,8 +333,14 @@ class MidBatchTrainer:
     ctx: Any = None
     evaluator: Any = None
     history: Any = None
+    on_device: bool = False
 
     def __post_init__(self):
+        if self.on_device and self.evaluator is not None and \
+                not hasattr(self.evaluator, "fit_packed"):
+            raise ValueError("on_device=True needs an evaluator with fit_packed "
+                             "(farm.MidBatchEvaluator)")
+        self.status = None
         self.models = list(self.models)
         self.training_data = list(self.training_data)
         if len(self.models) != len(self.training_data):
@@ -341,6 +358,8 @@ class MidBatchTrainer:
 
     def fit(self, fix_params: bool = True, num_steps_per_epoch: int = 1000):
         """trainer.py:162-228 for every problem; returns (models, histories [P, num_iters])."""
+        if self.on_device:
+            return self._fit_on_device(fix_params, num_steps_per_epoch)
         raws = list(self.raws)
         states = [self.optim.init(r) for r in raws]
         hist = np.empty((len(raws), self.num_iters))
@@ -361,6 +380,26 @@ class MidBatchTrainer:
                 m = m.replace(true_s=c["true_s"], true_d=c["true_d"])
             out.append(m)
         self.raws, self.models, self.history = raws, out, hist
+        return self.models, self.history
+
+    def _fit_on_device(self, fix_params, num_steps_per_epoch):
+        """``fit`` in one ``fit_packed`` call; the tail is ``BatchTrainer.fit``'s."""
+        genes = [int(m.num_genes) for m in self._like]
+        self.evaluator.registered(genes)
+        raw = pack_raw(self.raws, [m.jitter for m in self._like])
+        mu, nu = np.zeros_like(raw), np.zeros_like(raw)
+        hist, self.status = self.evaluator.fit_packed(raw, mu, nu, self.optim, fix_params,
+                                                      num_steps_per_epoch, 0, self.num_iters)
+        self.raws = unpack_raw(raw, genes)
+        out = []
+        for r, like in zip(self.raws, self._like):
+            m = constrain(r, like)
+            if fix_params:  # trainer.py:218-222, on the constrained model
+                c = JaxTrainer.after_epoch({"true_s": m.true_s, "true_d": m.true_d}, True)
+                m = m.replace(true_s=c["true_s"], true_d=c["true_d"])
+            out.append(m)
+        self.models = out
+        self.history = hist.T.copy()
         return self.models, self.history
 
     def close(self):

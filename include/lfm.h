@@ -320,6 +320,58 @@ typedef struct {
 int lfm_batch_fit_f64(lfm_ctx* ctx, lfm_batch* batch, const lfm_adam* opt, int negative,
                       int64_t step0, int64_t nsteps, double* raw, double* mu, double* nu,
                       double* history, int* status);
+/* lfm_batch_fit_f64 for an lfm_mbatch: JaxTrainer.fit of every problem of any mix of sizes
+ * 1 <= n <= LFM_MID_MAX_N on the device, with no host round trip between steps. The arguments,
+ * packed layouts (lfm_mbatch_hyp_size's) and per-step semantics are lfm_batch_fit_f64's: raw, mu,
+ * nu [nhyp] in/out (the jitter slots hold the static jitter and are never changed); history
+ * [nsteps x nprob], step-major, each step's loss before its update; status[p] optional, 0 or
+ * 1 + the first step of this call whose factorisation failed (that step's loss, every later loss
+ * and the parameters are NaN from there on, as under JAX; the call then returns LFM_E_NOT_PD);
+ * Adam's count is step0 + s + 1 and its bias corrections 1 - b^count come from the host's pow,
+ * one pair per step; after_epoch on the unconstrained leaves when (step0 + s) %
+ * num_steps_per_epoch == 0 and fix_params (nothing for G <= 3). The final constrain and the last
+ * after_epoch are the caller's (dis_project_amd.trainer.MidBatchTrainer(on_device=True)).
+ *
+ * One call enqueues a constrain launch and then, per step, the launches of
+ * lfm_mbatch_mll_grad_f64 (ceil((n_max + 1) / 64) + 6, unchanged) and one update launch
+ * (one workgroup per problem: the loss, the chain rule, Adam, after_epoch and the next step's
+ * constrained hyperparameters), synchronises once and downloads raw, mu, nu, history and the
+ * status words. Plain stream-ordered launches: no graph capture, no device-side waits, no atomics,
+ * no cooperative launch. The same inputs give the same bits; a problem's trajectory depends on
+ * its own data and parameters alone, not on the other problems, their sizes or its position; a
+ * fit resumed across calls (mu, nu and step0 carried over) equals the one-call fit bit for bit.
+ * A fit leaves the handle usable: a later lfm_mbatch_mll_f64, lfm_mbatch_mll_grad_f64 or
+ * lfm_mbatch_posterior_f64 call on it returns the bits it returns on a fresh handle, because
+ * each call refills what it reads.
+ *
+ * A NULL batch, opt, raw, mu, nu (or history with nsteps > 0), a handle of another device,
+ * step0 < 0, nsteps < 0, num_steps_per_epoch < 1 or nsteps > 65536 (resume with step0 instead)
+ * is LFM_E_ARG with a message naming what was wrong; nsteps == 0 returns LFM_OK and touches
+ * nothing. The call works in a third device arena that the handle owns (allocated at the first
+ * fit call, regrown when a call needs more, freed by lfm_mbatch_destroy; never the ctx
+ * workspace): with e(d) = 2 ceil(d / 2),
+ *   8 (3 e(nhyp) + 2 nsteps + e(nsteps nprob)) + 16 ceil(nprob / 4) bytes
+ * (27 KB for 15 problems of G = 5 and 150 steps). A failed allocation is LFM_E_OOM and the
+ * handle stays usable.
+ *
+ * Synchronous; holds the device's lock shared for the WHOLE call, which at n = 1020 and 150 steps
+ * is on the order of a second: schedule-3 work of other threads on the device waits that long. A
+ * caller who shares the device with such work can split the fit into shorter calls with step0, at
+ * no cost in bits.
+ *
+ * Measured on an MI355X (scripts/mid_fit_rate.py, profiles/mid_fit.json,
+ * mid_fit_p4.json; 5-gene grids, 150 steps of adam(0.01) on -MLL, per step):
+ * the call's time per step is the kernel time of lfm_mbatch_mll_grad_f64 (0.70 ms at n = 160,
+ * 1.52 at 320, 3.77 at 640, 7.62 at 1020 with 15 problems; 0.71, 1.39, 3.08, 5.65 with 4), where
+ * the host loop of MidBatchTrainer around lfm_mbatch_mll_grad_f64 takes 1.67, 2.49, 4.73, 8.58 ms
+ * (15 problems: 2.37x, 1.64x, 1.26x, 1.13x) and 1.00, 1.68, 3.38, 5.96 ms (4 problems: 1.41x,
+ * 1.21x, 1.10x, 1.05x): the device fit is the faster one at every size and count measured, by
+ * the 0.96 ms (15 problems) or 0.30 ms (4) of host work a step that it removes. It does not
+ * replace lfm_batch_fit_f64 where that applies: on 15 problems of n = 35 the one-launch small
+ * fit takes 34 us a step and this call 226 us (8 launches a step), 6.6x as long. */
+int lfm_mbatch_fit_f64(lfm_ctx* ctx, lfm_mbatch* batch, const lfm_adam* opt, int negative,
+                       int64_t step0, int64_t nsteps, double* raw, double* mu, double* nu,
+                       double* history, int* status);
 
 /* Value and gradient of CustomConjMLL(negative).step — what jax.value_and_grad(loss)
  * differentiates at trainer.py:126, before the bijectors' chain rule (trainer.py:103) —
