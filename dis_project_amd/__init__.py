@@ -6,7 +6,7 @@ likelihood (src/objectives.py), on hand-written gfx950 HIP kernels behind a ctyp
 
 from ._lib import LfmError, device_count, get_context, load_library  # noqa: F401
 from .dataset import Dataset, SyntheticP53Data, dataset_3d  # noqa: F401
-from .distributions import GaussianDistribution  # noqa: F401
+from .distributions import GaussianDistribution, randn, seed_to_u64  # noqa: F401
 from .farm import MidBatchEvaluator  # noqa: F401
 from .model import ExactLFM  # noqa: F401
 from .objectives import CustomConjMLL  # noqa: F401
@@ -29,4 +29,6 @@ __all__ = [
     "device_count",
     "get_context",
     "load_library",
+    "randn",
+    "seed_to_u64",
 ]

@@ -15,7 +15,8 @@ from __future__ import annotations
 import ctypes
 import os
 import threading
-from ctypes import POINTER, c_char, c_char_p, c_double, c_int, c_int64, c_size_t, c_void_p
+from ctypes import (POINTER, c_char, c_char_p, c_double, c_int, c_int64, c_size_t, c_uint64,
+                    c_void_p)
 
 import numpy as np
 
@@ -157,6 +158,11 @@ PRODUCT_SIGNATURES = [
     ("lfm_post_set_chunk", c_int, [c_void_p, c_int64]),
     ("lfm_post_predict_f64", c_int, [_c_ctx, c_void_p, _dptr, c_int64, _dptr, _dptr, _dptr]),
     ("lfm_log_prob_f64", c_int, [_c_ctx, _dptr, _dptr, c_int64, c_int64, _dptr, _dptr]),
+    ("lfm_randn_f64", c_int, [_c_ctx, c_uint64, c_int64, c_int64, c_int64, _dptr]),
+    ("lfm_mvn_sample_f64", c_int,
+     [_c_ctx, _dptr, _dptr, c_int64, c_int64, c_uint64, c_int64, c_int64, _dptr]),
+    ("lfm_post_sample_f64", c_int,
+     [_c_ctx, c_void_p, _dptr, c_int64, c_double, c_uint64, c_int64, c_int64, _dptr, _dptr]),
     ("lfm_h_f64", c_int,
      [_c_ctx, POINTER(LfmHyp), POINTER(c_int64), POINTER(c_int64), _dptr, _dptr, c_int64, _dptr]),
     ("lfm_dev_alloc", c_int, [_c_ctx, c_size_t, POINTER(c_void_p)]),
@@ -209,6 +215,8 @@ KCLASSES = ["tables", "gram_grid", "gram_direct", "augment", "potrf", "trsm", "s
             "finalize", "small_mll", "mean", "grad", "panel", "syrk_side", "small_grad",
             "small_post", "post_panel", "post_update", "mid_fill", "mid_column", "mid_inverse",
             "mid_pairs", "mid_finish"]
+# ... and the joint samples' two (lfm_sample.hip), entries 22 and 23 of that order
+SAMPLE_KCLASSES = ["sample_randn", "sample_trmm"]
 
 _lib = None
 _diag = None
@@ -360,7 +368,7 @@ class Context:
         if classes is not None:
             mask = 0
             for c in classes:
-                mask |= 1 << KCLASSES.index(c)
+                mask |= 1 << (KCLASSES + SAMPLE_KCLASSES).index(c)
             self.check(self.lib.lfm_profile_classes(self.handle, mask))
         else:
             self.check(self.lib.lfm_profile_classes(self.handle, 0xFFFFFFFF))

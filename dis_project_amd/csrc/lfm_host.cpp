@@ -570,6 +570,42 @@ ResidentPlan plan_post(int64_t n, int64_t G, int64_t m, int64_t chunk, bool want
   return P;
 }
 
+// ------------------------------------------------- joint samples (lfm_sample.hip)
+SamplePlan plan_sample(int64_t n, int64_t nsamp, int64_t sample0) {
+  SamplePlan P;
+  P.n = n;
+  P.nsamp = nsamp;
+  P.sample0 = sample0;
+  auto rejected = [&](int code, const std::string& why) {
+    P.reject = code;
+    P.why = why;
+    return P;
+  };
+  if (n < 1 || n > (int64_t)1 << 30)
+    return rejected(SamplePlan::BAD_N, "n must be in [1, 2^30]");
+  if (nsamp < 1) return rejected(SamplePlan::BAD_NSAMP, "nsamp must be >= 1");
+  if (sample0 < 0) return rejected(SamplePlan::BAD_SAMPLE0, "sample0 must be >= 0");
+  if (sample0 > INT64_MAX - nsamp)
+    return rejected(SamplePlan::RANGE, "sample0 + nsamp overflows 2^63");
+  if (nsamp > SAMPLE_MAX_NSAMP)
+    return rejected(SamplePlan::TOO_MANY,
+                    "nsamp = " + std::to_string(nsamp) + " is above the limit of " +
+                        std::to_string(SAMPLE_MAX_NSAMP) +
+                        " samples a call (continue the draw with sample0)");
+  P.Np = (n + 127) / 128 * 128;
+  P.Mp = (n + 1 + 127) / 128 * 128;
+  P.ldz = P.Np;
+  P.zrows = (nsamp + 127) / 128 * 128;
+  P.mat_bytes = (size_t)P.Mp * P.Mp * sizeof(double);
+  P.z_bytes = (size_t)P.zrows * P.ldz * sizeof(double);
+  P.x_bytes = (size_t)nsamp * n * sizeof(double);
+  P.tiles_i = (int)(P.zrows / 128);
+  P.tiles_j = (int)(P.Np / 128);
+  P.pairs = P.zrows * (P.ldz / 2);
+  P.randn_grid = (int)std::min<int64_t>((P.pairs + 255) / 256, SAMPLE_RANDN_GRID);
+  return P;
+}
+
 // ------------------------------------------------- mid-size resident batch (lfm_mid.hip)
 namespace {
 int64_t even(int64_t d) { return (d + 1) / 2 * 2; }

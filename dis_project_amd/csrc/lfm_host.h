@@ -5,7 +5,8 @@
 // with lfm_small_plan.h the small-problem path's LDS map, staging and buffer layouts and its
 // launch plans (plan_small_*, which lfm_small.hip and lfm_batch.hip only read); and the resident
 // posterior's predict plan (plan_post, which lfm_post.hip only reads); with lfm_mid_plan.h the
-// mid-size resident batch's arena and launch plan (plan_mid, which lfm_mid.hip only reads).
+// mid-size resident batch's arena and launch plan (plan_mid, which lfm_mid.hip only reads); and
+// the joint samples' generator and launch plan (plan_sample, which lfm_sample.hip only reads).
 // Plain C++ (no HIP types), so lfm_host.cpp also builds into the host sanitizer check
 // (tests/native, `make -C tests/native asan`) with g++ -fsanitize=address,undefined.
 #pragma once
@@ -234,6 +235,60 @@ int64_t post_default_chunk(int64_t Np);
 // order: m < 1 or m % G != 0; the covariance with m above the chunk; a chunk that is no
 // positive multiple of 128.
 ResidentPlan plan_post(int64_t n, int64_t G, int64_t m, int64_t chunk, bool want_cov);
+
+// ------------------------------------------------- joint samples (lfm_sample.hip)
+// The generator include/lfm.h defines: Philox4x32-10 on counter c and key k, in place.
+LFM_HD inline void philox4x32_10(uint32_t c[4], uint32_t k0, uint32_t k1) {
+  constexpr uint32_t M0 = 0xD2511F53u, M1 = 0xCD9E8D57u, W0 = 0x9E3779B9u, W1 = 0xBB67AE85u;
+  for (int r = 0; r < 10; ++r) {
+    const uint64_t p0 = (uint64_t)M0 * c[0], p1 = (uint64_t)M1 * c[2];
+    const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c[1] ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c[3] ^ k1;
+    c[0] = n0;
+    c[1] = (uint32_t)p1;
+    c[2] = n2;
+    c[3] = (uint32_t)p0;
+    k0 += W0;
+    k1 += W1;
+  }
+}
+// The two uniforms in (0, 1] of pair p of sample s: u1 then u2, both exact
+LFM_HD inline void sample_uniforms(uint64_t seed, uint64_t s, uint64_t p, double* u1, double* u2) {
+  uint32_t c[4] = {(uint32_t)p, (uint32_t)(p >> 32), (uint32_t)s, (uint32_t)(s >> 32)};
+  philox4x32_10(c, (uint32_t)seed, (uint32_t)(seed >> 32));
+  const uint64_t a = ((uint64_t)c[0] | (uint64_t)c[1] << 32) >> 11;
+  const uint64_t b = ((uint64_t)c[2] | (uint64_t)c[3] << 32) >> 11;
+  *u1 = (double)(a + 1) * 0x1p-53;
+  *u2 = (double)(b + 1) * 0x1p-53;
+}
+
+// One draw of nsamp joint samples from N(loc, scale), scale n x n (lfm_mvn_sample_f64,
+// lfm_post_sample_f64): scale's lower triangle sits in an Mp x Mp matrix (Mp = round_up(n + 1,
+// 128): the augmented matrix chol_factor_solve factors in place), Z (zrows x ldz, samples as
+// rows, every element generated, padding included: finite) holds the normals and X (nsamp x n,
+// dense) the result. One workgroup per 128 x 128 tile of X: grid (tiles_i, tiles_j), workgroup
+// (bx, by) owns sample rows [128 bx, 128 bx + 128) and column tile sample_tile_col(P, by),
+// deepest first; its product runs over columns [0, sample_depth(tj)) of Z and L.
+constexpr int64_t SAMPLE_MAX_NSAMP = (int64_t)1 << 24;  // per call; sample0 continues a draw
+constexpr int64_t SAMPLE_RANDN_GRID = 1 << 16;          // workgroups of the generator at most
+struct SamplePlan {
+  enum Reject { OK = 0, BAD_N, BAD_NSAMP, BAD_SAMPLE0, RANGE, TOO_MANY };
+  int reject = OK;
+  std::string why;           // the message of a rejection
+  int64_t n = 0, nsamp = 0, sample0 = 0;
+  int64_t Np = 0, Mp = 0;    // round_up(n, 128), round_up(n + 1, 128)
+  int64_t ldz = 0, zrows = 0;  // Z: ldz = Np, zrows = round_up(nsamp, 128)
+  size_t mat_bytes = 0;      // Mp x Mp doubles
+  size_t z_bytes = 0;        // zrows x ldz
+  size_t x_bytes = 0;        // nsamp x n
+  int tiles_i = 0, tiles_j = 0;  // the product's grid
+  int64_t pairs = 0;         // the generator's threads' work: zrows x ldz / 2 pairs
+  int randn_grid = 0;        // its workgroups of 256 (grid-stride above SAMPLE_RANDN_GRID)
+};
+inline int sample_tile_col(const SamplePlan& P, int by) { return P.tiles_j - 1 - by; }
+inline int64_t sample_depth(int tj) { return 128 * ((int64_t)tj + 1); }
+// Rejections in order: n < 1 or above 2^30; nsamp < 1; sample0 < 0; sample0 + nsamp above
+// 2^63 - 1; nsamp above SAMPLE_MAX_NSAMP.
+SamplePlan plan_sample(int64_t n, int64_t nsamp, int64_t sample0);
 
 // Readers-writer lock over one GPU's library work (lfm_ctx.hip DeviceTenancy: a schedule-3
 // factorisation exclusive, all other GPU work shared). In-process a std::shared_mutex; across

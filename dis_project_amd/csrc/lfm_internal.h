@@ -40,6 +40,8 @@ enum KClass {
   K_MID_INVERSE,  // mid-size batch: X = L^{-1} and S^{-1} = X^T X (fp64 MFMA)
   K_MID_PAIRS,    // mid-size batch: W-weighted kernel derivatives per lower tile
   K_MID_FINISH,   // mid-size batch: the values / the gradients joined in a fixed order
+  K_SAMPLE_RANDN, // joint samples: the counter-based normal generator
+  K_SAMPLE_TRMM,  // joint samples: X = loc + Z L^T per 128 x 128 tile (fp64 MFMA)
   K_NCLASS
 };
 
@@ -164,6 +166,8 @@ struct lfm_ctx : lfm::CtxStreams {
   lfm::Buf<double> gtab;       // gradient tables (grid layout)
   lfm::Buf<double> result;     // [0..] scalar results
   lfm::Buf<double> gacc;       // gradient accumulators + output
+  lfm::Buf<double> smp_z;      // joint samples: the normals Z (lfm_randn_f64, lfm_mvn_sample_f64)
+  lfm::Buf<double> smp_x;      // joint samples: X = loc + Z L^T
 
   lfm::Buf<unsigned long long> dbg_stamps;      // lfm_debug_stamps: chain phases 256 x 16, then
                                                 // step launches 256 x 8
@@ -314,6 +318,16 @@ enum CholMode { CHOL_MLL = 0, CHOL_INVERSE = 1, CHOL_SCHUR = 2, CHOL_RESIDENT = 
 int chol_factor_solve(lfm_ctx* ctx, double* A, int64_t lda, int64_t n, int64_t Mp, int negative,
                       double* d_out, int mode = CHOL_MLL, const GramGen* gen = nullptr);
 bool chol_fuses_gram(const lfm_ctx* ctx, int mode, const GridLayout& lay, int64_t n);
+
+// joint samples (lfm_sample.hip): A (stride P.Mp) holds scale's lower triangle and d_loc [n] the
+// mean, both on the device. Enqueues the augmented row, the factorisation (CHOL_RESIDENT, in
+// place; its status lands in ctx->result), the generator into Z and the product into X (P's
+// sizes). Nothing is downloaded and nothing synchronised.
+int sample_enqueue(lfm_ctx* ctx, const SamplePlan& P, double* A, const double* d_loc,
+                   uint64_t seed, double* Z, double* X);
+// The end of a sampling call: X and the factorisation's status to the host, synchronised. Not
+// positive definite: out (and mean, if given) NaN and LFM_E_NOT_PD.
+int sample_finish(lfm_ctx* ctx, const SamplePlan& P, const double* X, double* out, double* mean);
 
 // gradient kernels (lfm_grad.hip)
 int launch_border_init(lfm_ctx* ctx, double* A, int64_t lda, int64_t Mp);

@@ -22,6 +22,10 @@
 // shape depend on neither m nor the chunk, rows have one owner per launch and the launches
 // follow each other on one stream: no atomics, no device-side waits, the same bits whatever
 // the split.
+// lfm_post_sample_f64 draws joint samples from such a predict without the covariance leaving the
+// device: the predict with the covariance, cov copied into an Mp' = round_up(m + 1, 128)-stride
+// matrix of the handle's, diag_add on its diagonal, then lfm_sample.hip's factor, generator and
+// product (sample_enqueue). The handle's L, z and dinv are only read.
 #include "lfm_api_internal.h"
 #include "lfm_chol_dev.h"
 
@@ -42,6 +46,9 @@ struct lfm_post {
   // grown by the predicts (ResidentPlan's byte counts)
   double *vt = nullptr, *acc = nullptr, *t = nullptr, *out = nullptr, *cov = nullptr;
   size_t vt_cap = 0, acc_cap = 0, t_cap = 0, out_cap = 0, cov_cap = 0;
+  // grown by the samples (SamplePlan's byte counts): the covariance's factor, Z and X
+  double *smat = nullptr, *sz = nullptr, *sx = nullptr;
+  size_t smat_cap = 0, sz_cap = 0, sx_cap = 0;
 };
 
 namespace lfm {
@@ -335,7 +342,8 @@ int grow(lfm_ctx* ctx, double** p, size_t* cap, size_t bytes, const char* what) 
 }
 
 void release(lfm_post* q) {
-  for (double* p : {q->L, q->dinv, q->z, q->x, q->par, q->vt, q->acc, q->t, q->out, q->cov})
+  for (double* p : {q->L, q->dinv, q->z, q->x, q->par, q->vt, q->acc, q->t, q->out, q->cov,
+                    q->smat, q->sz, q->sx})
     if (p) hipFree(p);
   delete q;
 }
@@ -431,6 +439,41 @@ int post_chunk(lfm_ctx* ctx, lfm_post* q, const ResidentPlan& P, const PostChunk
   return hip_fail(ctx, hipGetLastError(), "resident posterior: chunk launches");
 }
 
+// One predict with the covariance when the plan has it, left on the device: mean in q->out [m],
+// var in q->out + m (marginals only), cov in q->cov (m x m, dense). Nothing is downloaded.
+int post_enqueue(lfm_ctx* ctx, lfm_post* q, const ResidentPlan& P, const double* t) {
+  const bool cov = P.cov_bytes != 0;
+  int r = grow(ctx, &q->vt, &q->vt_cap, P.vt_bytes, "the solve workspace");
+  if (!r) r = grow(ctx, &q->acc, &q->acc_cap, P.acc_bytes, "the row accumulators");
+  if (!r) r = grow(ctx, &q->t, &q->t_cap, P.t_bytes, "the test inputs");
+  if (!r) r = grow(ctx, &q->out, &q->out_cap, P.out_bytes, "mean / var");
+  if (!r && cov) r = grow(ctx, &q->cov, &q->cov_cap, P.cov_bytes, "the covariance");
+  if (r) return r;
+  hipStream_t st = ctx->stream;
+  const int64_t G = q->G, m = P.m;
+  const HypDev h{q->par, q->par + G, q->par + 2 * G, (int)G, q->l};
+  hipMemcpyAsync(q->t, t, P.t_bytes, hipMemcpyHostToDevice, st);
+  for (const PostChunk& c : P.chunks) {
+    r = post_chunk(ctx, q, P, c, h);
+    if (r) return r;
+  }
+  if (cov) {
+    // one chunk (the plan rejected anything else): its Vt is whole
+    r = launch_gram_direct<double>(ctx, h, q->t, m, q->t, m, 0.0, 0.0, LFM_UPLO_LOWER, q->cov, m);
+    if (r) return r;
+    hipLaunchKernelGGL(post_cov_kernel, dim3((unsigned)P.cov_tiles, (unsigned)P.cov_tiles),
+                       dim3(256), 0, st, q->vt, P.Np, q->cov, m);
+    r = hip_fail(ctx, hipGetLastError(), "post_cov_kernel");
+  }
+  return r;
+}
+
+// A[i][i] += d: the caller's diag_add on the sampled covariance, in one addition
+__global__ void post_shift_kernel(double* __restrict__ A, int64_t lda, double d, int64_t n) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) A[i * lda + i] += d;
+}
+
 }  // namespace
 }  // namespace lfm
 
@@ -497,38 +540,53 @@ int lfm_post_predict_f64(lfm_ctx* ctx, lfm_post* post, const double* t, int64_t 
   if (P.reject) return set_err(ctx, LFM_E_ARG, P.why);
   DeviceGuard g(ctx->device);
   DeviceTenancy tenancy(ctx, false);  // no factorisation: shared
-  int r = grow(ctx, &q->vt, &q->vt_cap, P.vt_bytes, "the solve workspace");
-  if (!r) r = grow(ctx, &q->acc, &q->acc_cap, P.acc_bytes, "the row accumulators");
-  if (!r) r = grow(ctx, &q->t, &q->t_cap, P.t_bytes, "the test inputs");
-  if (!r) r = grow(ctx, &q->out, &q->out_cap, P.out_bytes, "mean / var");
-  if (!r && cov) r = grow(ctx, &q->cov, &q->cov_cap, P.cov_bytes, "the covariance");
+  int r = post_enqueue(ctx, q, P, t);
   if (r) return r;
   hipStream_t st = ctx->stream;
-  const int64_t G = q->G;
-  const HypDev h{q->par, q->par + G, q->par + 2 * G, (int)G, q->l};
-  hipMemcpyAsync(q->t, t, P.t_bytes, hipMemcpyHostToDevice, st);
-  for (const PostChunk& c : P.chunks) {
-    r = post_chunk(ctx, q, P, c, h);
-    if (r) return r;
-  }
   hipMemcpyAsync(mean, q->out, (size_t)m * 8, hipMemcpyDeviceToHost, st);
-  if (cov) {
-    // one chunk (the plan rejected anything else): its Vt is whole
-    r = launch_gram_direct<double>(ctx, h, q->t, m, q->t, m, 0.0, 0.0, LFM_UPLO_LOWER, q->cov, m);
-    if (r) return r;
-    hipLaunchKernelGGL(post_cov_kernel, dim3((unsigned)P.cov_tiles, (unsigned)P.cov_tiles),
-                       dim3(256), 0, st, q->vt, P.Np, q->cov, m);
-    r = hip_fail(ctx, hipGetLastError(), "post_cov_kernel");
-    if (r) return r;
+  if (cov)
     hipMemcpyAsync(cov, q->cov, P.cov_bytes, hipMemcpyDeviceToHost, st);
-  } else {
+  else
     hipMemcpyAsync(var, q->out + m, (size_t)m * 8, hipMemcpyDeviceToHost, st);
-  }
   r = finish(ctx);
   if (r) return r;
   if (cov && var)
     for (int64_t i = 0; i < m; ++i) var[i] = cov[i * m + i];  // diag(cov), bit for bit
   return LFM_OK;
+}
+
+int lfm_post_sample_f64(lfm_ctx* ctx, lfm_post* post, const double* t, int64_t m, double diag_add,
+                        uint64_t seed, int64_t sample0, int64_t nsamp, double* mean,
+                        double* out) {
+  if (!ctx) return LFM_E_ARG;
+  if (!post) return set_err(ctx, LFM_E_ARG, "post is NULL");
+  if (ctx->device != post->device)
+    return set_err(ctx, LFM_E_ARG, "the handle belongs to another device than this ctx");
+  if (!t || !out) return set_err(ctx, LFM_E_ARG, "t / out is NULL");
+  lfm_post* q = post;
+  const ResidentPlan P = plan_post(q->n, q->G, m, q->chunk, true);
+  if (P.reject) return set_err(ctx, LFM_E_ARG, P.why);
+  const SamplePlan S = plan_sample(m, nsamp, sample0);
+  if (S.reject) return set_err(ctx, LFM_E_ARG, S.why);
+  DeviceGuard g(ctx->device);
+  DeviceTenancy tenancy(ctx, false);  // CHOL_RESIDENT is schedule 1: shared
+  int r = grow(ctx, &q->smat, &q->smat_cap, S.mat_bytes, "the covariance's factor");
+  if (!r) r = grow(ctx, &q->sz, &q->sz_cap, S.z_bytes, "the normals");
+  if (!r) r = grow(ctx, &q->sx, &q->sx_cap, S.x_bytes, "the samples");
+  if (!r) r = ctx->hpin.reserve(ctx, 1 << 16);
+  if (r) return r;
+  r = post_enqueue(ctx, q, P, t);  // mean in q->out, cov (m x m, dense) in q->cov
+  if (r) return r;
+  hipStream_t st = ctx->stream;
+  hipError_t e = hipMemcpy2DAsync(q->smat, S.Mp * 8, q->cov, m * 8, m * 8, m,
+                                  hipMemcpyDeviceToDevice, st);
+  if (e != hipSuccess) return hip_fail(ctx, e, "the covariance into the factor's stride");
+  hipLaunchKernelGGL(post_shift_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st,
+                     q->smat, S.Mp, diag_add, m);
+  r = sample_enqueue(ctx, S, q->smat, q->out, seed, q->sz, q->sx);
+  if (r) return r;
+  if (mean) hipMemcpyAsync(mean, q->out, (size_t)m * 8, hipMemcpyDeviceToHost, st);
+  return sample_finish(ctx, S, q->sx, out, mean);
 }
 
 }  // extern "C"

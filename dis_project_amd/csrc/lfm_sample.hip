@@ -1,0 +1,190 @@
+// lfm_sample.hip — joint samples from a Gaussian (include/lfm.h lfm_randn_f64,
+// lfm_mvn_sample_f64; lfm_post_sample_f64 in lfm_post.hip ends here too).
+//
+// Reference: gpjax 0.8.2 GaussianDistribution.sample(seed, sample_shape): loc + L z per sample,
+// L L^T = scale, z standard normal. Here, with samples as rows:
+//     X[s, i] = loc[i] + sum_{k <= i} L[i, k] Z[s, k].
+//   sample_randn_kernel  Z from the counter-based generator the header defines (Philox4x32-10,
+//                        Box-Muller): one thread per pair (s, p) writes z[2p], z[2p + 1] of
+//                        sample sample0 + s as one 16-byte store. Element (s, j) depends on
+//                        (seed, s, j) alone; Z's padding rows and columns are generated too, so
+//                        every value the product reads is finite.
+//   sample_tril_kernel   the strict upper triangle of the factor's diagonal 128-blocks, which
+//                        the factorisation leaves holding the input's entries: zero.
+//   sample_trmm_kernel   one workgroup per 128 x 128 tile of X: gemm_accumulate at depth
+//                        128 (tj + 1) with the Z rows as panel i and the L rows as panel j,
+//                        deepest column tiles first; loc joins in one addition on the masked store.
+// Every size and grid is plan_sample's (lfm_host.cpp). The K order and the tile shape depend on
+// neither nsamp nor sample0, rows have one owner and the launches follow each other on one
+// stream: no atomics, no device-side waits, the same bits however a draw is split over calls.
+#include "lfm_api_internal.h"
+#include "lfm_chol_dev.h"
+
+using namespace lfm;
+
+namespace lfm {
+namespace {
+
+// rows x ld (ld even) normals: row r is sample s0 + r, columns [0, ld)
+__global__ __launch_bounds__(256) void sample_randn_kernel(double* __restrict__ Z, int64_t ld,
+                                                           int64_t pairs, uint64_t seed,
+                                                           uint64_t s0) {
+  #pragma clang fp contract(off)
+  const int64_t half = ld >> 1;
+  for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < pairs;
+       q += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t r = q / half, p = q - r * half;
+    double u1, u2;
+    sample_uniforms(seed, s0 + (uint64_t)r, (uint64_t)p, &u1, &u2);
+    const double rad = sqrt(-2.0 * log(u1));
+    double sn, cs;
+    sincos(6.283185307179586 * u2, &sn, &cs);
+    double2 v;
+    v.x = rad * cs;
+    v.y = rad * sn;
+    *reinterpret_cast<double2*>(&Z[r * ld + 2 * p]) = v;
+  }
+}
+
+// one workgroup per diagonal 128-block of L
+__global__ __launch_bounds__(256) void sample_tril_kernel(double* __restrict__ L, int64_t ldl) {
+  double* D = L + (int64_t)blockIdx.x * NB * (ldl + 1);
+  for (int idx = threadIdx.x; idx < NB * NB; idx += 256) {
+    const int r = idx / NB, c = idx - r * NB;
+    if (c > r) D[r * ldl + c] = 0.0;
+  }
+}
+
+struct SampleArgs {
+  const double* Z;
+  int64_t ldz;
+  const double* L;
+  int64_t ldl;
+  const double* loc;
+  double* X;          // nsamp x n, dense
+  int64_t n, nsamp;
+  int ntj;            // column tiles: blockIdx.y = 0 is the deepest, ntj - 1
+};
+
+__global__ __launch_bounds__(256, 2) void sample_trmm_kernel(SampleArgs g) {
+  __shared__ __attribute__((aligned(16))) double sPbuf[(ST + ST) * (KB + LDP)];
+  double(*sP)[KB + LDP] = reinterpret_cast<double(*)[KB + LDP]>(sPbuf);
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int tj = g.ntj - 1 - (int)blockIdx.y;
+  const int64_t i0 = (int64_t)blockIdx.x * ST, j0 = (int64_t)tj * ST;
+  double acc[16][4];
+#pragma unroll
+  for (int ir = 0; ir < 16; ++ir)
+#pragma unroll
+    for (int jr = 0; jr < 4; ++jr) acc[ir][jr] = 0.0;
+  gemm_accumulate<ST>(g.Z + i0 * g.ldz, g.ldz, g.L + j0 * g.ldl, g.ldl, (tj + 1) * NB, acc, sP);
+  const int wr = (w >> 1) * 64, wc = (w & 1) * 64;
+#pragma unroll
+  for (int ir = 0; ir < 16; ++ir)
+#pragma unroll
+    for (int jr = 0; jr < 4; ++jr) {
+      const int64_t s = i0 + wr + ir * 4 + (lane >> 4), i = j0 + wc + jr * 16 + (lane & 15);
+      if (s < g.nsamp && i < g.n) g.X[s * g.n + i] = g.loc[i] + acc[ir][jr];
+    }
+}
+
+void launch_randn(lfm_ctx* ctx, double* Z, int64_t ld, int64_t rows, int64_t pairs, int grid,
+                  uint64_t seed, int64_t sample0) {
+  hipEvent_t ev;
+  prof_begin(ctx, K_SAMPLE_RANDN, &ev);
+  hipLaunchKernelGGL(sample_randn_kernel, dim3((unsigned)grid), dim3(256), 0, ctx->stream, Z, ld,
+                     pairs, seed, (uint64_t)sample0);
+  prof_end(ctx, K_SAMPLE_RANDN, ev, 0, (double)rows * ld * 8);
+}
+
+}  // namespace
+
+int sample_enqueue(lfm_ctx* ctx, const SamplePlan& P, double* A, const double* d_loc,
+                   uint64_t seed, double* Z, double* X) {
+  hipStream_t st = ctx->stream;
+  // the augmented row: y = loc, residual 0 (the MLL the factorisation also produces is not used)
+  const HypDev h{nullptr, nullptr, nullptr, 1, 1.0};
+  int r = launch_augment(ctx, h, nullptr, d_loc, d_loc, P.n, A, P.Mp, P.Mp);
+  if (r) return r;
+  r = chol_factor_solve(ctx, A, P.Mp, P.n, P.Mp, 0, ctx->result, CHOL_RESIDENT);
+  if (r) return r;
+  hipLaunchKernelGGL(sample_tril_kernel, dim3((unsigned)P.tiles_j), dim3(256), 0, st, A, P.Mp);
+  launch_randn(ctx, Z, P.ldz, P.zrows, P.pairs, P.randn_grid, seed, P.sample0);
+  SampleArgs g{Z, P.ldz, A, P.Mp, d_loc, X, P.n, P.nsamp, P.tiles_j};
+  hipEvent_t ev;
+  prof_begin(ctx, K_SAMPLE_TRMM, &ev);
+  hipLaunchKernelGGL(sample_trmm_kernel, dim3((unsigned)P.tiles_i, (unsigned)P.tiles_j), dim3(256),
+                     0, st, g);
+  double issued = 0.0;
+  for (int tj = 0; tj < P.tiles_j; ++tj) issued += 2.0 * P.zrows * ST * (double)sample_depth(tj);
+  prof_end(ctx, K_SAMPLE_TRMM, ev, (double)P.nsamp * P.n * P.n,
+           ((double)P.zrows * P.ldz + 0.5 * P.Np * P.Np + (double)P.nsamp * P.n) * 8, nullptr,
+           issued);
+  return hip_fail(ctx, hipGetLastError(), "joint samples: launches");
+}
+
+int sample_finish(lfm_ctx* ctx, const SamplePlan& P, const double* X, double* out, double* mean) {
+  double* hres = ctx->hpin;
+  hipMemcpyAsync(hres, ctx->result, 5 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream);
+  hipMemcpyAsync(out, X, P.x_bytes, hipMemcpyDeviceToHost, ctx->stream);
+  int r = finish(ctx);
+  if (r) return r;
+  r = status_code(ctx, hres[3], hres[4]);
+  if (r == LFM_E_NOT_PD) {
+    std::fill(out, out + P.nsamp * P.n, std::nan(""));
+    if (mean) std::fill(mean, mean + P.n, std::nan(""));
+  }
+  return r;
+}
+
+}  // namespace lfm
+
+extern "C" {
+
+int lfm_randn_f64(lfm_ctx* ctx, uint64_t seed, int64_t sample0, int64_t nsamp, int64_t n,
+                  double* out) {
+  if (!ctx) return LFM_E_ARG;
+  if (!out) return set_err(ctx, LFM_E_ARG, "out is NULL");
+  const SamplePlan P = plan_sample(n, nsamp, sample0);
+  if (P.reject) return set_err(ctx, LFM_E_ARG, P.why);
+  DeviceGuard g(ctx->device);
+  DeviceTenancy tenancy(ctx, false);  // no factorisation: shared
+  // the generator alone: nsamp rows of ld = n rounded up to a pair
+  const int64_t ld = (n + 1) / 2 * 2, pairs = nsamp * (ld / 2);
+  int r = ctx->smp_z.reserve(ctx, (size_t)nsamp * ld * sizeof(double));
+  if (r) return r;
+  launch_randn(ctx, ctx->smp_z, ld, nsamp, pairs,
+               (int)std::min<int64_t>((pairs + 255) / 256, SAMPLE_RANDN_GRID), seed, sample0);
+  r = hip_fail(ctx, hipGetLastError(), "sample_randn_kernel");
+  if (r) return r;
+  hipError_t e = hipMemcpy2DAsync(out, n * 8, ctx->smp_z, ld * 8, n * 8, nsamp,
+                                  hipMemcpyDeviceToHost, ctx->stream);
+  if (e != hipSuccess) return hip_fail(ctx, e, "download the normals");
+  return finish(ctx);
+}
+
+int lfm_mvn_sample_f64(lfm_ctx* ctx, const double* loc, const double* scale, int64_t n,
+                       int64_t lds, uint64_t seed, int64_t sample0, int64_t nsamp, double* out) {
+  if (!ctx) return LFM_E_ARG;
+  if (!loc || !scale || !out) return set_err(ctx, LFM_E_ARG, "loc / scale / out is NULL");
+  const SamplePlan P = plan_sample(n, nsamp, sample0);
+  if (P.reject) return set_err(ctx, LFM_E_ARG, P.why);
+  if (lds < n) return set_err(ctx, LFM_E_ARG, "lds must be >= n");
+  DeviceGuard g(ctx->device);
+  int r = ctx->A.reserve(ctx, P.mat_bytes);
+  if (!r) r = ctx->smp_z.reserve(ctx, P.z_bytes);
+  if (!r) r = ctx->smp_x.reserve(ctx, P.x_bytes);
+  if (!r) r = ctx->xin.reserve(ctx, (size_t)n * sizeof(double));
+  if (!r) r = ctx->hpin.reserve(ctx, 1 << 16);
+  if (r) return r;
+  DeviceTenancy tenancy(ctx, false);  // CHOL_RESIDENT is schedule 1: shared
+  hipMemcpyAsync(ctx->xin, loc, n * 8, hipMemcpyHostToDevice, ctx->stream);
+  hipError_t e = hipMemcpy2DAsync(ctx->A, P.Mp * 8, scale, lds * 8, n * 8, n,
+                                  hipMemcpyHostToDevice, ctx->stream);
+  if (e != hipSuccess) return hip_fail(ctx, e, "upload scale");
+  r = sample_enqueue(ctx, P, ctx->A, ctx->xin, seed, ctx->smp_z, ctx->smp_x);
+  if (r) return r;
+  return sample_finish(ctx, P, ctx->smp_x, out, nullptr);
+}
+
+}  // extern "C"

@@ -337,6 +337,39 @@ class Posterior:
             scale = cov + np.eye(m) * self.jitter
         return GaussianDistribution(mean, scale, device=self.ctx.device)
 
+    def sample(self, test_inputs, num_samples, seed, sample0: int = 0):
+        """``(mean [m], samples [num_samples, m])``: joint draws from N(mean(t), cov(t) +
+        jitter I), one ``lfm_post_sample_f64``: the covariance is formed, factored and multiplied
+        on the device and only the samples come back. Both kinds use the DENSE covariance. For
+        ``kind="gene"`` that is ``predict(t).sample(...)``. For ``kind="latent"`` it is the joint
+        posterior, which the reference's ``latent_predict`` discards by diagonalising
+        (model.py:420-465); ``predict(t).sample(...)`` still reproduces the reference's diagonal
+        distribution exactly. Gene rows (flag 1) can be drawn jointly under either kind. Latent
+        rows (flag 0) cannot: the joint covariance the reference's flag-switched kernel gives them
+        is indefinite, and the draw is NaN with ``LFM_E_NOT_PD`` swallowed,
+        as JAX's Cholesky would return NaN. m must fit one chunk (``set_chunk``). ``seed`` as
+        ``GaussianDistribution.sample``; sample ``sample0 + s`` depends on the seed and its own
+        index alone. The bits are not JAX's threefry bits. After a failed fit: NaN, as
+        ``predict``."""
+        from .distributions import seed_to_u64
+
+        t = self._test(test_inputs)
+        k = int(num_samples)
+        if k < 1:
+            raise ValueError("num_samples must be >= 1")
+        if int(sample0) < 0:
+            raise ValueError("sample0 must be >= 0")
+        key = seed_to_u64(seed)
+        m = t.shape[0]
+        mean = np.full(m, np.nan)
+        out = np.full((k, m), np.nan)
+        if self._handle:
+            rc = self.ctx.lib.lfm_post_sample_f64(
+                self.ctx.handle, self._handle, dptr(t), m, self.jitter, key, int(sample0), k,
+                dptr(mean), dptr(out))
+            self.ctx.check(rc, allow_not_pd=True)
+        return mean, out
+
     def close(self):
         if self._final is not None:
             self._final()  # runs lfm_post_destroy once

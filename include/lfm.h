@@ -468,6 +468,91 @@ int lfm_post_predict_f64(lfm_ctx* ctx, lfm_post* post, const double* t, int64_t 
 int lfm_log_prob_f64(lfm_ctx* ctx, const double* loc, const double* scale, int64_t n,
                      int64_t lds, const double* y, double* out);
 
+/* ------------- joint samples: GaussianDistribution(loc, scale).sample (gpjax 0.8.2) */
+/* The distribution latent_predict / multi_gene_predict return (model.py:420-514) is drawn from
+ * as loc + L z_s, L L^T = scale, z_s standard normal. gpjax takes its normals from JAX's threefry
+ * key; this library cannot reproduce those bits and does not try: the equivalence with the
+ * reference is IN DISTRIBUTION. What it fixes instead is its own generator, so that a sample can
+ * be reproduced on the host, or continued in a later call, from (seed, s, j) alone.
+ *
+ * The generator. Element j of sample s (s the absolute sample index, sample0 + row) depends on
+ * (seed, s, j) and on nothing else: not on the launch geometry, not on nsamp, n or sample0, no
+ * state. With p = j >> 1:
+ *   Philox4x32-10, multipliers M0 = 0xD2511F53, M1 = 0xCD9E8D57, Weyl constants 0x9E3779B9,
+ *   0xBB67AE85; one round maps (c0, c1, c2, c3) to
+ *       (hi(M1 c2) ^ c1 ^ k0,  lo(M1 c2),  hi(M0 c0) ^ c3 ^ k1,  lo(M0 c0)),
+ *   hi / lo the halves of the 64-bit product, and the key (k0, k1) is bumped by the Weyl
+ *   constants after each round;
+ *   key = (seed lo32, seed hi32), counter = (p lo32, p hi32, s lo32, s hi32) -> words w0..w3;
+ *   a = (w0 | w1 << 32) >> 11, b = (w2 | w3 << 32) >> 11; u1 = (a + 1) 2^-53, u2 = (b + 1) 2^-53,
+ *   both in (0, 1] and exact; r = sqrt(-2 ln u1), theta = 2 pi u2;
+ *   z[2p] = r cos theta, z[2p + 1] = r sin theta.
+ * Known answers: counter 0^4, key 0^2 -> 6627e8d5 e169c58d bc57ac4c 9b00dbd8; seed 42, s = 0:
+ * z[0:4] = -0.66537487, 1.03602381, -1.43388918, 0.42327818. The device's ln / sqrt / sin / cos
+ * differ from a host libm's by a few ulp: a host restatement agrees to about 1e-14, not bit for
+ * bit (tests/philox_ref.py is one).
+ *
+ * lfm_randn_f64: the generator alone, out[s * n + j] for s < nsamp, j < n (host).
+ *
+ * lfm_mvn_sample_f64: out[s] = loc + L z_s for samples sample0 .. sample0 + nsamp - 1. loc [n],
+ * scale (n x n row-major, leading dim lds >= n; ONLY the lower triangle is read) and out
+ * [nsamp x n] are host pointers. Works in the ctx workspace, as lfm_log_prob_f64 does:
+ *   8 (Mp^2 + 128 ceil(nsamp / 128) Np + nsamp n + n) bytes, Mp = 128 ceil((n + 1) / 128),
+ *   Np = 128 ceil(n / 128).
+ * scale is factored on schedule 1 (shared hold of the device's lock); the product
+ * X[s, i] = loc[i] + sum_{k <= i} L[i, k] Z[s, k] runs one workgroup per 128 x 128 tile of X on
+ * the fp64 MFMA, at a K order and tile shape that depend on neither nsamp nor sample0. So: the
+ * same call twice gives the same bits; rows [0, k) of an nsamp-sample call are the k-sample
+ * call's, and rows [k, nsamp) are those of the call at sample0 + k.
+ *
+ * lfm_post_sample_f64: the same from a resident posterior (lfm_post_create): nsamp joint samples
+ * of N(mean(t), cov(t) + diag_add I), mean and cov as lfm_post_predict_f64 defines them. cov never
+ * leaves the device: it is formed as by a predict, copied into a matrix of stride
+ * Mp' = 128 ceil((m + 1) / 128) that the handle owns, diag_add joins its diagonal in one addition,
+ * and it is factored, multiplied and only X [nsamp x m] (and the mean, if mean != NULL) comes
+ * back. m has lfm_post_predict_f64's rules with the covariance: m >= 1, m % num_genes == 0 and m
+ * within one chunk, else LFM_E_ARG (the message names the limit). On top of a predict with the
+ * covariance the handle grows by
+ *   8 (Mp'^2 + 128 ceil(nsamp / 128) 128 ceil(m / 128) + nsamp m) bytes.
+ * The result equals lfm_mvn_sample_f64 fed this handle's lfm_post_predict_f64 mean and
+ * cov + diag_add I, bit for bit. The handle's factor, z and predict results are not disturbed: a
+ * predict after a sample returns the bits it returned before.
+ *
+ * All three: nsamp < 1, sample0 < 0, sample0 + nsamp overflowing 2^63, nsamp above 2^24 in one
+ * call (continue the draw with sample0), n outside [1, 2^30], a NULL required pointer or a handle
+ * of another device is LFM_E_ARG with a message naming the cause. Not positive definite: every
+ * output is NaN (the mean included) and the return is LFM_E_NOT_PD, JAX's NaN Cholesky. A failed
+ * allocation is LFM_E_OOM, and the ctx and the handle stay usable. Synchronous; no atomics, no
+ * device-side waits and no cooperative launch.
+ *
+ * Validity is the caller's: gene rows (flag 1) of the reference's kernel give a covariance that is
+ * positive semi-definite to rounding, and diag_add makes it definite. Latent rows (flag 0) do not:
+ * the joint covariance the flag-switched kernel (model.py:152-195) gives them is indefinite (its
+ * smallest eigenvalue was -3 on the p53 data at m = 100), so a joint draw of latent rows is
+ * LFM_E_NOT_PD, as jnp.linalg.cholesky would return NaN; latent_predict's diagonalised
+ * distribution (model.py:420-465) is the one that can be sampled.
+ *
+ * Measured on an MI355X (scripts/sample_rate.py, profiles/post_sample.json, DESIGN.md section
+ * 4.10; a resident N = 16384 model, gene rows, diag_add = obs_stddev^2, medians of synchronous
+ * calls): lfm_post_sample_f64 takes 15.3 ms at m = 384, 47 ms at m = 4096 and 231 / 237 ms at
+ * m = 16384 for 16 / 1024 samples; lfm_post_predict_f64 with the covariance followed by numpy's
+ * cholesky and matmul takes 12.9 / 18.4 ms, 1.50 / 1.57 s and 8.4 / 8.7 s (0.85x / 1.21x, 32x /
+ * 33x, 36x / 37x), and downloads 2.1 GB at m = 16384 where this call downloads 2.2 / 134 MB. At
+ * m = 16384 and 1024 samples the call is the solve 100 ms, the factorisation 75 ms, the generator
+ * 0.08 ms, the product 5.8 ms (0.60 of the 78.6 TFLOP/s fp64 matrix spec on its nsamp m^2 flop)
+ * and 55 ms of covariance tiles, copy and download. With 16 samples the product still issues 128
+ * rows: 2.6 ms, 0.02 of the spec on the algorithmic flop. */
+int lfm_randn_f64(lfm_ctx* ctx, uint64_t seed, int64_t sample0, int64_t nsamp, int64_t n,
+                  double* out /* host [nsamp x n] */);
+/* GaussianDistribution(loc, scale).sample (gpjax 0.8.2): out[s] = loc + L z_s, L L^T = scale */
+int lfm_mvn_sample_f64(lfm_ctx* ctx, const double* loc, const double* scale, int64_t n,
+                       int64_t lds, uint64_t seed, int64_t sample0, int64_t nsamp,
+                       double* out /* [nsamp x n] */);
+/* the same from a resident posterior: N(mean(t), cov(t) + diag_add I); cov never leaves the device */
+int lfm_post_sample_f64(lfm_ctx* ctx, lfm_post* post, const double* t, int64_t m, double diag_add,
+                        uint64_t seed, int64_t sample0, int64_t nsamp,
+                        double* mean /* [m], may be NULL */, double* out /* [nsamp x m] */);
+
 /* ----------------------- device-resident variants (inputs already in HBM) */
 int lfm_dev_alloc(lfm_ctx* ctx, size_t bytes, void** out);
 int lfm_dev_free(lfm_ctx* ctx, void* p);

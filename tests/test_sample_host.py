@@ -1,0 +1,157 @@
+"""CPU checks of the joint samples (lfm_randn_f64, lfm_mvn_sample_f64, lfm_post_sample_f64,
+GaussianDistribution.sample, predict.Posterior.sample): the generator's known answers from the
+numpy restatement (tests/philox_ref.py), the launch plan under AddressSanitizer + UBSan
+(tests/native/sample_plan_check.cpp, a stand-alone program built here with the flags of
+tests/native/Makefile), the new entry points in the header and the ctypes table, the calls that
+need no GPU, the host-side moments of GaussianDistribution, and the strict build."""
+
+import os
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+
+from tests import philox_ref
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+NEW = ["lfm_randn_f64", "lfm_mvn_sample_f64", "lfm_post_sample_f64"]
+
+
+def _hex(words):
+    return " ".join(f"{int(w):08x}" for w in words)
+
+
+def test_philox_known_answers():
+    ff = 0xFFFFFFFF
+    assert _hex(philox_ref.philox4x32_10([0] * 4, [0] * 2)) == \
+        "6627e8d5 e169c58d bc57ac4c 9b00dbd8"
+    assert _hex(philox_ref.philox4x32_10([ff] * 4, [ff] * 2)) == \
+        "408f276d 41c83b0e a20bc7c6 6d5451fd"
+    assert _hex(philox_ref.philox4x32_10([0x243F6A88, 0x85A308D3, 0x13198A2E, 0x03707344],
+                                         [0xA4093822, 0x299F31D0])) == \
+        "d16cfe09 94fdcceb 5001e420 24126ea1"
+
+
+def test_normals_known_answers():
+    z = philox_ref.randn(42, 0, 1, 4)[0]
+    assert np.max(np.abs(z - [-0.66537487, 1.03602381, -1.43388918, 0.42327818])) <= 1e-8
+    z = philox_ref.randn(42, 7, 1, 3)[0]
+    assert np.max(np.abs(z - [-0.23572248, 0.4055612, 0.64305171])) <= 1e-8
+    # the high counter and key words
+    z = philox_ref.randn(2 ** 40 + 5, 2 ** 33 + 1, 1, 2)[0]
+    assert np.max(np.abs(z - [-0.92533466, 0.18825383])) <= 1e-8
+    # an element depends on (seed, s, j) alone: rows and prefixes of a larger draw
+    big = philox_ref.randn(42, 0, 9, 7)
+    assert np.array_equal(big[7, :3], philox_ref.randn(42, 7, 1, 3)[0])
+    assert np.array_equal(big[0, :4], philox_ref.randn(42, 0, 1, 4)[0])
+
+
+@pytest.mark.skipif(shutil.which("g++") is None, reason="needs g++ with libasan")
+def test_plan_sample_under_asan_and_ubsan(tmp_path):
+    exe = str(tmp_path / "sample_plan_check")
+    san = ["-fsanitize=address,undefined", "-fno-omit-frame-pointer",
+           "-fno-sanitize-recover=undefined"]
+    r = subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-Wall", *san, "-pthread",
+                        os.path.join(ROOT, "tests", "native", "sample_plan_check.cpp"),
+                        os.path.join(ROOT, "dis_project_amd", "csrc", "lfm_host.cpp"),
+                        "-o", exe], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=1",
+               UBSAN_OPTIONS="print_stacktrace=1")
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=600, env=env)
+    assert r.returncode == 0, (r.stdout[-3000:], r.stderr[-3000:])
+    assert "sample_plan_check: all passed" in r.stdout
+    assert "ERROR: AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr
+
+
+def test_header_and_signatures_carry_the_new_entry_points():
+    from dis_project_amd import _lib
+    from tests.test_abi import header_functions
+
+    declared = header_functions()
+    bound = {name for name, _, _ in _lib.PRODUCT_SIGNATURES}
+    assert bound == set(declared)
+    for name in NEW:
+        assert name in declared and name in bound
+    lib = _lib.load_library()
+    assert lib.lfm_abi_version() == 5
+    for name in NEW:
+        assert hasattr(lib, name)
+    # the two profiling classes follow the 22 of KCLASSES, within lfm_profile_classes' mask
+    assert _lib.SAMPLE_KCLASSES == ["sample_randn", "sample_trmm"]
+    assert len(_lib.KCLASSES) + len(_lib.SAMPLE_KCLASSES) == 24 <= 32
+
+
+def test_null_context_and_handle_are_rejected_without_a_gpu():
+    from dis_project_amd import _lib
+
+    lib = _lib.load_library()
+    out = np.zeros(4)
+    assert lib.lfm_randn_f64(None, 1, 0, 2, 2, out.ctypes.data) == _lib.LFM_E_ARG
+    assert lib.lfm_mvn_sample_f64(None, None, None, 2, 2, 1, 0, 1, None) == _lib.LFM_E_ARG
+    assert lib.lfm_post_sample_f64(None, None, None, 5, 0.0, 1, 0, 1, None,
+                                   None) == _lib.LFM_E_ARG
+    assert np.all(out == 0)
+
+
+def test_moments_of_a_hand_built_distribution():
+    """stddev / variance / covariance are host numpy: no context is asked for."""
+    import dis_project_amd as lfm
+
+    scale = np.array([[4.0, 1.0, 0.5], [1.0, 9.0, -2.0], [0.5, -2.0, 0.25]])
+    d = lfm.GaussianDistribution([1.0, -2.0, 3.0], scale)
+    assert np.array_equal(d.covariance(), scale)
+    assert np.array_equal(d.variance(), np.diag(scale))
+    assert np.array_equal(d.stddev(), np.sqrt(np.diag(scale)))
+    assert np.array_equal(d.stddev(), [2.0, 3.0, 0.5])
+    assert np.array_equal(d.mean(), [1.0, -2.0, 3.0])
+    d.variance()[0] = -1.0  # a copy: the distribution is not changed through it
+    assert d.covariance()[0, 0] == 4.0
+
+
+def test_seed_words():
+    import dis_project_amd as lfm
+
+    assert lfm.seed_to_u64(42) == 42
+    assert lfm.seed_to_u64(np.array([1, 2], dtype=np.uint32)) == (1 << 32) | 2
+    assert lfm.seed_to_u64(-1) == 2 ** 64 - 1
+    with pytest.raises(ValueError, match="pair"):
+        lfm.seed_to_u64([1, 2, 3])
+    with pytest.raises(ValueError, match="uint32"):
+        lfm.seed_to_u64([2 ** 32, 0])
+    d = lfm.GaussianDistribution(np.zeros(2), np.eye(2))
+    with pytest.raises(ValueError, match="sample_shape"):
+        d.sample(1, sample_shape=(2, 3))
+
+
+def test_posterior_sample_argument_checks_need_no_gpu():
+    import dis_project_amd as lfm
+
+    # a constructed object without a handle: as after a failed fit
+    post = object.__new__(lfm.Posterior)
+    post.num_genes, post.kind, post.jitter = 5, "latent", 1e-4
+    post._handle, post._final, post.ctx = None, None, None
+    with pytest.raises(ValueError, match=r"\[m, 3\]"):
+        post.sample(np.zeros((10, 2)), 4, 1)
+    with pytest.raises(ValueError, match="multiple"):
+        post.sample(np.zeros((7, 3)), 4, 1)
+    with pytest.raises(ValueError, match="num_samples"):
+        post.sample(np.ones((10, 3)), 0, 1)
+    with pytest.raises(ValueError, match="sample0"):
+        post.sample(np.ones((10, 3)), 2, 1, sample0=-1)
+    with pytest.raises(ValueError, match="pair"):
+        post.sample(np.ones((10, 3)), 2, [1, 2, 3])
+    mean, x = post.sample(np.ones((10, 3)), 3, 7)
+    assert mean.shape == (10,) and x.shape == (3, 10)
+    assert np.all(np.isnan(mean)) and np.all(np.isnan(x))
+    post.close()
+
+
+@pytest.mark.skipif(not os.path.exists("/opt/rocm/bin/hipcc"), reason="needs hipcc")
+def test_strict_build():
+    """Every unit, lfm_sample.hip included, with warnings as errors."""
+    r = subprocess.run(["make", "-s", "-C", os.path.join(ROOT, "dis_project_amd", "csrc"),
+                        "-j", str(min(16, os.cpu_count() or 4)), "strict"],
+                       capture_output=True, text=True, timeout=1800)
+    assert r.returncode == 0, (r.stdout[-3000:], r.stderr[-3000:])
