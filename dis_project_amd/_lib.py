@@ -149,6 +149,9 @@ PRODUCT_SIGNATURES = [
     ("lfm_mbatch_mll_grad_f64", c_int, [_c_ctx, c_void_p, _dptr, c_int, _dptr, _dptr, _dptr]),
     ("lfm_mbatch_posterior_f64", c_int,
      [_c_ctx, c_void_p, _dptr, _dptr, _dptr, _dptr, _dptr, _dptr, _dptr, _dptr, _dptr]),
+    ("lfm_mbatch_predictive_f64", c_int,
+     [_c_ctx, c_void_p, _dptr, _dptr, _dptr, _dptr, _dptr, _dptr, _dptr, _dptr, _dptr, c_int64,
+      c_int64, _dptr, _dptr, _dptr]),
     ("lfm_mbatch_fit_f64", c_int,
      [_c_ctx, c_void_p, POINTER(LfmAdam), c_int, c_int64, c_int64, _dptr, _dptr, _dptr, _dptr,
       _dptr]),

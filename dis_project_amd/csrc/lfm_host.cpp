@@ -808,4 +808,124 @@ MidFitPlan plan_mid_fit(const std::vector<MidShape>& shapes, int64_t nsteps) {
   return F;
 }
 
+size_t mid_draw_problem_bytes(int64_t m, bool has_ystar, int64_t nsamp) {
+  const int64_t nq = mid_blocks((int)m), Mq = nq * MID_TILE;
+  const int64_t cb = (m + MID_TILE - 1) / MID_TILE, sb = (nsamp + MID_TILE - 1) / MID_TILE;
+  int64_t d = 2 * Mq * Mq + nq * MID_TILE * MID_TILE + 2;
+  if (has_ystar) d += m;
+  if (nsamp > 0) d += (int64_t)MID_TILE * MID_TILE * sb * cb + nsamp * m;
+  return (size_t)d * 8 + sizeof(uint64_t) + sizeof(MidProb) + sizeof(MidDrawProb);
+}
+
+MidDrawPlan plan_mid_draw(const std::vector<MidShape>& shapes, const int64_t* m, bool has_cov_add,
+                          bool has_ystar, int64_t nsamp, int64_t sample0) {
+  MidDrawPlan P;
+  const std::string who = "lfm_mbatch_predictive_f64: ";
+  auto rejected = [&](int code, const std::string& why) {
+    P.reject = code;
+    P.why = who + why;
+    return P;
+  };
+  if (!has_cov_add) return rejected(MidDrawPlan::NO_COV_ADD, "cov_add is NULL");
+  if (nsamp < 0) return rejected(MidDrawPlan::BAD_NSAMP, "nsamp must be >= 0");
+  if (!has_ystar && nsamp == 0)
+    return rejected(MidDrawPlan::NOTHING, "nothing asked for: give ystar and logp, or nsamp > 0");
+  if (nsamp > MID_DRAW_MAX_NSAMP)
+    return rejected(MidDrawPlan::TOO_MANY,
+                    "nsamp = " + std::to_string(nsamp) + " is above the limit of " +
+                        std::to_string(MID_DRAW_MAX_NSAMP) +
+                        " samples a call (continue the draw with sample0)");
+  if (sample0 < 0) return rejected(MidDrawPlan::BAD_SAMPLE0, "sample0 must be >= 0");
+  if (sample0 > INT64_MAX - nsamp)
+    return rejected(MidDrawPlan::RANGE, "sample0 + nsamp overflows 2^63");
+  for (size_t q = 0; q < shapes.size(); ++q) {
+    const std::string pm = "problem " + std::to_string(q) + " has m = " + std::to_string(m[q]);
+    if (m[q] < 1) return rejected(MidDrawPlan::NO_ROWS, pm + ", needs m >= 1");
+    if (m[q] % shapes[q].G != 0)
+      return rejected(MidDrawPlan::BAD_M, pm + ", no multiple of num_genes = " +
+                                              std::to_string(shapes[q].G) +
+                                              " (mean_function, model.py:145-149)");
+    if (m[q] > MID_MAX_N)
+      return rejected(MidDrawPlan::TOO_MANY_ROWS,
+                      pm + ", past " + std::to_string(MID_MAX_N) +
+                          " (LFM_MID_MAX_N: the covariance goes through the mid-size "
+                          "factorisation); use lfm_post_* for a larger m on one model");
+  }
+  P.nprob = (int64_t)shapes.size();
+  P.nsamp = nsamp;
+  P.sample0 = sample0;
+  for (size_t q = 0; q < shapes.size(); ++q) P.sm += m[q];
+  const int64_t sb = (nsamp + MID_TILE - 1) / MID_TILE;
+  int64_t at = 0;
+  P.cadd = at;
+  at += even(P.nprob);
+  P.out = at;
+  at += even(P.nprob);
+  if (has_ystar) {
+    P.ystar = at;
+    at += even(P.sm);
+  }
+  P.probs.reserve(shapes.size());
+  P.dp.reserve(shapes.size());
+  int64_t om = 0, oc = 0;
+  for (size_t q = 0; q < shapes.size(); ++q) {
+    MidProb e{};
+    e.n = (int)m[q];
+    e.G = (int)shapes[q].G;
+    e.nb = mid_blocks(e.n);
+    e.Mp = e.nb * MID_TILE;
+    const int64_t mat = (int64_t)e.Mp * e.Mp;
+    e.S = at;
+    e.L = e.S + mat;
+    e.dinv = e.L + mat;
+    at = e.dinv + (int64_t)e.nb * MID_TILE * MID_TILE;
+    MidDrawProb d{};
+    d.m = e.n;
+    d.cb = (e.n + MID_TILE - 1) / MID_TILE;
+    d.sb = (int)sb;
+    d.cov = oc;
+    d.mean = om;
+    d.ystar = has_ystar ? P.ystar + om : -1;
+    d.Z = -1;
+    d.X = -1;
+    if (nsamp > 0) {
+      d.Z = at;
+      at += (int64_t)MID_TILE * MID_TILE * sb * d.cb;
+      d.X = nsamp * om;  // within the packed samples: their base is added below
+    }
+    om += m[q];
+    oc += m[q] * m[q];
+    P.maxnq = std::max(P.maxnq, e.nb);
+    P.maxcb = std::max(P.maxcb, d.cb);
+    P.probs.push_back(e);
+    P.dp.push_back(d);
+  }
+  if (nsamp > 0) {
+    P.X = at;
+    at += even(nsamp * P.sm);
+    for (MidDrawProb& d : P.dp) d.X += P.X;
+  }
+  P.maxsb = (int)sb;
+  P.maxtiles = mid_tiles(P.maxnq);
+  P.doubles = at;
+  auto up16 = [](size_t b) { return (b + 15) / 16 * 16; };
+  P.seeds = (size_t)at * sizeof(double);
+  P.table = P.seeds + up16((size_t)P.nprob * sizeof(uint64_t));
+  P.dtable = P.table + up16((size_t)P.nprob * sizeof(MidProb));
+  P.bytes = P.dtable + (size_t)P.nprob * sizeof(MidDrawProb);
+  const unsigned gx = (unsigned)P.nprob;
+  P.launches.push_back({MID_DRAW_SCALE, 0, gx, (unsigned)P.maxtiles});
+  for (int k = 0; k < P.maxnq; ++k)
+    P.launches.push_back({MID_COLUMN, k, gx, (unsigned)(P.maxnq - k)});
+  if (has_ystar) P.launches.push_back({MID_VALUE, 0, gx, 1u});
+  if (nsamp > 0) {
+    // 64 sb x 64 cb / 2 pairs of the largest problem, 256 a workgroup
+    const int64_t wgs = 8 * sb * P.maxcb;
+    P.launches.push_back(
+        {MID_DRAW_RANDN, 0, gx, (unsigned)std::min<int64_t>(wgs, MID_DRAW_RANDN_GY)});
+    P.launches.push_back({MID_DRAW_PRODUCT, 0, gx, (unsigned)(sb * P.maxcb)});
+  }
+  return P;
+}
+
 }  // namespace lfm

@@ -38,7 +38,18 @@
 //                      chain rule, the Adam update and after_epoch as small_fit_kernel's, and the
 //                      next step's constrained hyperparameters where mid_fill_kernel reads them
 //                      (before step 0: the constrain alone)
-// with no host wait between the steps.
+// with no host wait between the steps;
+// and GaussianDistribution.sample / .log_prob (objectives.py:78) of every problem's
+// multi_gene_predict distribution N(mean, cov + cov_add I) (lfm_mbatch_predictive_f64; its arena,
+// second problem table and launch list: plan_mid_draw): after the posterior call's launches
+//   mid_draw_scale_kernel    the covariance as an augmented matrix in mid_fill_kernel's layout:
+//                      cov_add on the diagonal, row m = ystar - mean (or 0), identity rows
+//   mid_column_kernel  as above, on the second table (n = m)
+//   mid_value_kernel   as above: the augmented row of the factor -> the log density
+//   mid_draw_randn_kernel    the problem's normals Z from its own seed (sample_randn_kernel's
+//                      arithmetic: lfm_randn_f64's bits)
+//   mid_draw_product_kernel  one workgroup per 64 x 64 tile of X = mean + Z L^T, depth
+//                      64 (tj + 1) over the factor's lower tiles (fp64 MFMA).
 // No atomics and no device-side waits: consecutive launches on one stream are the only ordering,
 // so a problem's bits depend on its own data and hyperparameters alone.
 #include <cstring>
@@ -63,6 +74,8 @@ struct lfm_mbatch {
   size_t pbytes = 0;
   char* fmem = nullptr;  // the fit calls' arena (plan_mid_fit), grown on demand
   size_t fbytes = 0;
+  char* qmem = nullptr;  // the predictive calls' arena (plan_mid_draw), grown on demand
+  size_t qbytes = 0;
   double* hbuf = nullptr;
   size_t h_out = 0, h_grad = 0, h_status = 0;  // doubles into hbuf
 };
@@ -686,6 +699,119 @@ __global__ __launch_bounds__(256) void mid_cov_kernel(MidArgs a, MidPostArgs q) 
   });
 }
 
+// ------------------------------------------------------------------ the predictive distribution
+// The predictive call's fourth arena (plan_mid_draw) and its table. The launches on it take a
+// MidArgs whose table is the second one (n = m_p, offsets into this arena) and whose status words
+// are the first arena's: a problem whose S failed is skipped, one whose covariance fails is
+// marked there.
+struct MidDrawArgs {
+  const MidDrawProb* dp;
+  double* base;           // the fourth arena
+  const double* mean;     // the posterior call's packed mean ...
+  const double* cov;      // ... and covariance, in its arena
+  const uint64_t* seeds;  // [nprob]
+  int64_t cadd;           // cov_add [nprob], doubles from base
+  int64_t nsamp;
+  uint64_t sample0;
+  int maxcb;
+  double flops;           // host side: the product's nsamp sum m^2, for the profile
+};
+
+// Lower tile (I, J) of the covariance's augmented matrix, in mid_fill_kernel's layout: the lower
+// triangle of cov_p with cov_add[p] joining the diagonal in one addition, row m the residual
+// ystar - mean (0 without ystar), identity rows past it; above the diagonal of a diagonal tile 0.
+__global__ __launch_bounds__(256) void mid_draw_scale_kernel(MidArgs a, MidDrawArgs d) {
+  const int p = blockIdx.x, tid = threadIdx.x;
+  const MidProb P = a.probs[p];
+  if ((int)blockIdx.y >= mid_tiles(P.nb) || a.status[p] != 0) return;
+  int I, J;
+  mid_tile_of((int)blockIdx.y, &I, &J);
+  const MidDrawProb D = d.dp[p];
+  const int m = P.n, c = TS * J + (tid & 63);
+  const double* cov = d.cov + D.cov;
+  const double* mean = d.mean + D.mean;
+  const double* ys = D.ystar >= 0 ? d.base + D.ystar : nullptr;
+  const double ca = d.base[d.cadd + p];
+  double* A = a.base + P.S;
+  for (int e = 0; e < 16; ++e) {
+    const int i = TS * I + (tid >> 6) + 4 * e;
+    double v;
+    if (i < m && c <= i) {
+      v = cov[(int64_t)i * m + c];
+      if (i == c) v = v + ca;
+    } else if (i == m && c < m) {
+      v = ys ? ys[c] - mean[c] : 0.0;
+    } else {
+      v = (i == c) ? 1.0 : 0.0;
+    }
+    A[(int64_t)i * P.Mp + c] = v;
+  }
+}
+
+// The problem's normals Z [64 sb x 64 cb], row r sample sample0 + r: sample_randn_kernel's
+// arithmetic (lfm_sample.hip) on the problem's own seed, so element (r, j) is lfm_randn_f64's
+// (seeds[p], sample0 + r, j) bit for bit; the padding rows and columns are generated too.
+__global__ __launch_bounds__(256) void mid_draw_randn_kernel(MidArgs a, MidDrawArgs d) {
+  #pragma clang fp contract(off)
+  const int p = blockIdx.x;
+  if (a.status[p] != 0) return;
+  const MidDrawProb D = d.dp[p];
+  const int64_t ld = (int64_t)TS * D.cb, half = ld >> 1, pairs = (int64_t)TS * D.sb * half;
+  const uint64_t seed = d.seeds[p];
+  double* Z = d.base + D.Z;
+  for (int64_t q = (int64_t)blockIdx.y * 256 + threadIdx.x; q < pairs;
+       q += (int64_t)gridDim.y * 256) {
+    const int64_t r = q / half, pp = q - r * half;
+    double u1, u2;
+    sample_uniforms(seed, d.sample0 + (uint64_t)r, (uint64_t)pp, &u1, &u2);
+    const double rad = sqrt(-2.0 * log(u1));
+    double sn, cs;
+    sincos(6.283185307179586 * u2, &sn, &cs);
+    double2 v;
+    v.x = rad * cs;
+    v.y = rad * sn;
+    *reinterpret_cast<double2*>(&Z[r * ld + 2 * pp]) = v;
+  }
+}
+
+constexpr size_t MID_DRAW_LDS = 2 * (size_t)TS * LD * sizeof(double);
+
+// The 64 x 64 tile (sample block, column block tj) of X = mean + Z L^T: depth 64 (tj + 1) over
+// the factor's lower tiles (tj, k), k <= tj, in that order whatever nsamp and sample0 are; a row
+// of X depends on its own row of Z alone. mean joins in one addition on the masked store. A
+// failed problem's samples are NaN.
+__global__ __launch_bounds__(256) void mid_draw_product_kernel(MidArgs a, MidDrawArgs d) {
+  extern __shared__ __attribute__((aligned(16))) double sm[];
+  Tile sA = reinterpret_cast<Tile>(sm), sB = sA + TS;
+  const int p = blockIdx.x;
+  const MidProb P = a.probs[p];
+  const MidDrawProb D = d.dp[p];
+  const int sblk = (int)blockIdx.y / d.maxcb, c = (int)blockIdx.y - sblk * d.maxcb;
+  if (c >= D.cb) return;
+  const int tj = D.cb - 1 - c, m = P.n;
+  const bool failed = a.status[p] != 0;
+  double4v acc[4];
+  acc_zero(acc);
+  if (!failed) {
+    const int64_t ldz = (int64_t)TS * D.cb, ld = P.Mp;
+    const double* Z = d.base + D.Z + (int64_t)sblk * TS * ldz;
+    const double* L = a.base + P.L + (int64_t)tj * TS * ld;
+    for (int k = 0; k <= tj; ++k) {
+      __syncthreads();
+      stage(sA, Z + k * TS, ldz, false);
+      stage(sB, L + k * TS, ld, false);
+      __syncthreads();
+      mma_nt(acc, sA, sB);
+    }
+  }
+  const double* mean = d.mean + D.mean;
+  double* X = d.base + D.X;
+  acc_each(acc, [&](int r, int cc, double v) {
+    const int64_t s = (int64_t)TS * sblk + r, j = (int64_t)TS * tj + cc;
+    if (s < d.nsamp && j < m) X[s * m + j] = failed ? __builtin_nan("") : mean[j] + v;
+  });
+}
+
 // ------------------------------------------------------------------ the fit's update
 // The fit call's third arena (plan_mid_fit) and optimiser; s: the step of this call, or -1 for
 // the constrain before step 0.
@@ -759,7 +885,7 @@ __global__ __launch_bounds__(256) void mid_adam_kernel(MidArgs a, MidFitArgs f) 
 }
 
 int launch_mid(lfm_ctx* ctx, const MidLaunch& l, MidArgs a, const MidPostArgs* q = nullptr,
-               const MidFitArgs* f = nullptr) {
+               const MidFitArgs* f = nullptr, const MidDrawArgs* d = nullptr) {
   static const bool attrs = [] {
     for (const void* f : {reinterpret_cast<const void*>(&mid_column_kernel),
                           reinterpret_cast<const void*>(&mid_invert_kernel),
@@ -767,6 +893,8 @@ int launch_mid(lfm_ctx* ctx, const MidLaunch& l, MidArgs a, const MidPostArgs* q
                           reinterpret_cast<const void*>(&mid_solve_kernel),
                           reinterpret_cast<const void*>(&mid_cov_kernel)})
       hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)MID_LDS);
+    hipFuncSetAttribute(reinterpret_cast<const void*>(&mid_draw_product_kernel),
+                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)MID_DRAW_LDS);
     return true;
   }();
   (void)attrs;
@@ -845,6 +973,24 @@ int launch_mid(lfm_ctx* ctx, const MidLaunch& l, MidArgs a, const MidPostArgs* q
       what = "mid_adam_kernel";
       break;
     }
+    case MID_DRAW_SCALE:
+      prof_begin(ctx, K_MID_FILL, &ev);
+      hipLaunchKernelGGL(mid_draw_scale_kernel, grid, block, 0, ctx->stream, a, *d);
+      prof_end(ctx, K_MID_FILL, ev, 0, 0);
+      what = "mid_draw_scale_kernel";
+      break;
+    case MID_DRAW_RANDN:
+      prof_begin(ctx, K_SAMPLE_RANDN, &ev);
+      hipLaunchKernelGGL(mid_draw_randn_kernel, grid, block, 0, ctx->stream, a, *d);
+      prof_end(ctx, K_SAMPLE_RANDN, ev, 0, 0);
+      what = "mid_draw_randn_kernel";
+      break;
+    case MID_DRAW_PRODUCT:
+      prof_begin(ctx, K_SAMPLE_TRMM, &ev);
+      hipLaunchKernelGGL(mid_draw_product_kernel, grid, block, MID_DRAW_LDS, ctx->stream, a, *d);
+      prof_end(ctx, K_SAMPLE_TRMM, ev, d->flops, 0);
+      what = "mid_draw_product_kernel";
+      break;
     default:
       return set_err(ctx, LFM_E_STATE, "plan_mid: unknown launch kind");
   }
@@ -889,11 +1035,11 @@ int mid_call(lfm_ctx* ctx, lfm_mbatch* b, const double* hyp, int negative, bool 
 
 // One posterior call: the hyperparameters into the first arena, the diagonal and the test inputs
 // into the second (grown here when this call needs more), the plan's launches, the outputs down.
-int mid_post_call(lfm_ctx* ctx, lfm_mbatch* b, const MidPostPlan& Q, const double* hyp,
-                  const double* diag_vec, const double* diag_add, const double* t, double* mean,
-                  double* var, double* cov, int* status) {
-  DeviceGuard g(ctx->device);
-  DeviceTenancy tenancy(ctx, false);  // shared
+// mid_post_enqueue is the first half, which the predictive call shares: the uploads and the
+// launches. `who` names the entry point in a message.
+int mid_post_enqueue(lfm_ctx* ctx, lfm_mbatch* b, const MidPostPlan& Q, const double* hyp,
+                     const double* diag_vec, const double* diag_add, const double* t,
+                     const std::string& who) {
   const MidPlan& P = b->plan;
   const int64_t np = P.nprob, nh = P.nhyp;
   if (b->pbytes < Q.bytes) {
@@ -905,7 +1051,7 @@ int mid_post_call(lfm_ctx* ctx, lfm_mbatch* b, const MidPostPlan& Q, const doubl
     if (e != hipSuccess) {
       b->pmem = nullptr;
       (void)hipGetLastError();
-      return set_err(ctx, LFM_E_OOM, "lfm_mbatch_posterior_f64: " + std::to_string(Q.bytes) +
+      return set_err(ctx, LFM_E_OOM, who + ": " + std::to_string(Q.bytes) +
                                          " bytes of device memory: " + hipGetErrorString(e));
     }
     b->pbytes = Q.bytes;
@@ -924,7 +1070,7 @@ int mid_post_call(lfm_ctx* ctx, lfm_mbatch* b, const MidPostPlan& Q, const doubl
   if (e == hipSuccess)
     e = hipMemcpyAsync(b->pmem + Q.table, Q.pp.data(), (size_t)np * sizeof(MidPostProb),
                        hipMemcpyHostToDevice, ctx->stream);
-  if (e != hipSuccess) return hip_fail(ctx, e, "lfm_mbatch_posterior_f64: upload");
+  if (e != hipSuccess) return hip_fail(ctx, e, (who + ": upload").c_str());
   MidArgs a{};
   a.probs = reinterpret_cast<const MidProb*>(b->dmem + P.table);
   a.base = base;
@@ -936,6 +1082,20 @@ int mid_post_call(lfm_ctx* ctx, lfm_mbatch* b, const MidPostPlan& Q, const doubl
   q.maxtiles = Q.maxtiles;
   for (const MidLaunch& l : Q.launches)
     if (int r = launch_mid(ctx, l, a, &q)) return r;
+  return LFM_OK;
+}
+
+int mid_post_call(lfm_ctx* ctx, lfm_mbatch* b, const MidPostPlan& Q, const double* hyp,
+                  const double* diag_vec, const double* diag_add, const double* t, double* mean,
+                  double* var, double* cov, int* status) {
+  DeviceGuard g(ctx->device);
+  DeviceTenancy tenancy(ctx, false);  // shared
+  if (int r = mid_post_enqueue(ctx, b, Q, hyp, diag_vec, diag_add, t, "lfm_mbatch_posterior_f64"))
+    return r;
+  const int64_t np = Q.nprob;
+  double* pbase = reinterpret_cast<double*>(b->pmem);
+  int* dst = reinterpret_cast<int*>(b->dmem + b->plan.status);
+  hipError_t e;
   int* hst = reinterpret_cast<int*>(b->hbuf + b->h_status);
   e = hipMemcpyAsync(mean, pbase + Q.mean, (size_t)Q.sm * 8, hipMemcpyDeviceToHost, ctx->stream);
   if (e == hipSuccess && var)
@@ -943,10 +1103,95 @@ int mid_post_call(lfm_ctx* ctx, lfm_mbatch* b, const MidPostPlan& Q, const doubl
   if (e == hipSuccess && cov)
     e = hipMemcpyAsync(cov, pbase + Q.cov, (size_t)Q.sc * 8, hipMemcpyDeviceToHost, ctx->stream);
   if (e == hipSuccess)
-    e = hipMemcpyAsync(hst, a.status, (size_t)np * sizeof(int), hipMemcpyDeviceToHost, ctx->stream);
+    e = hipMemcpyAsync(hst, dst, (size_t)np * sizeof(int), hipMemcpyDeviceToHost, ctx->stream);
   if (e != hipSuccess) return hip_fail(ctx, e, "lfm_mbatch_posterior_f64: download");
   if (int r = finish(ctx)) return r;
   return batch_status(ctx, hst, np, status);
+}
+
+// One predictive call: the posterior call's uploads and launches with the covariance, cov_add,
+// ystar, the seeds and the two tables into the fourth arena (grown here when this call needs
+// more), the plan's launches on the second table, and logp, the samples, the mean and the status
+// words down. A problem whose covariance failed to factor has a valid mean on the device: the
+// host replaces it with NaN.
+int mid_draw_call(lfm_ctx* ctx, lfm_mbatch* b, const MidPostPlan& Q, const MidDrawPlan& D,
+                  const double* hyp, const double* diag_vec, const double* diag_add,
+                  const double* t, const double* cov_add, const double* ystar, double* logp,
+                  const uint64_t* seeds, double* mean, double* samples, int* status) {
+  const std::string who = "lfm_mbatch_predictive_f64";
+  DeviceGuard g(ctx->device);
+  DeviceTenancy tenancy(ctx, false);  // shared
+  const MidPlan& P = b->plan;
+  const int64_t np = P.nprob;
+  if (b->qbytes < D.bytes) {
+    // every call on the handle is synchronous: nothing of the old arena is in flight
+    if (b->qmem) hipFree(b->qmem);
+    b->qmem = nullptr;
+    b->qbytes = 0;
+    const hipError_t e = hipMalloc((void**)&b->qmem, D.bytes);
+    if (e != hipSuccess) {
+      b->qmem = nullptr;
+      (void)hipGetLastError();
+      return set_err(ctx, LFM_E_OOM, who + ": " + std::to_string(D.bytes) +
+                                         " bytes of device memory: " + hipGetErrorString(e));
+    }
+    b->qbytes = D.bytes;
+  }
+  if (int r = mid_post_enqueue(ctx, b, Q, hyp, diag_vec, diag_add, t, who)) return r;
+  double* pbase = reinterpret_cast<double*>(b->pmem);
+  double* qbase = reinterpret_cast<double*>(b->qmem);
+  hipError_t e = hipMemcpyAsync(qbase + D.cadd, cov_add, (size_t)np * 8, hipMemcpyHostToDevice,
+                                ctx->stream);
+  if (e == hipSuccess && ystar)
+    e = hipMemcpyAsync(qbase + D.ystar, ystar, (size_t)D.sm * 8, hipMemcpyHostToDevice, ctx->stream);
+  if (e == hipSuccess && D.nsamp > 0)
+    e = hipMemcpyAsync(b->qmem + D.seeds, seeds, (size_t)np * sizeof(uint64_t),
+                       hipMemcpyHostToDevice, ctx->stream);
+  if (e == hipSuccess)
+    e = hipMemcpyAsync(b->qmem + D.table, D.probs.data(), (size_t)np * sizeof(MidProb),
+                       hipMemcpyHostToDevice, ctx->stream);
+  if (e == hipSuccess)
+    e = hipMemcpyAsync(b->qmem + D.dtable, D.dp.data(), (size_t)np * sizeof(MidDrawProb),
+                       hipMemcpyHostToDevice, ctx->stream);
+  if (e != hipSuccess) return hip_fail(ctx, e, "lfm_mbatch_predictive_f64: upload");
+  int* dst = reinterpret_cast<int*>(b->dmem + P.status);
+  MidArgs a{};
+  a.probs = reinterpret_cast<const MidProb*>(b->qmem + D.table);
+  a.base = qbase;
+  a.status = dst;
+  a.out = D.out;
+  a.negative = 0;
+  MidDrawArgs d{};
+  d.dp = reinterpret_cast<const MidDrawProb*>(b->qmem + D.dtable);
+  d.base = qbase;
+  d.mean = pbase + Q.mean;
+  d.cov = pbase + Q.cov;
+  d.seeds = reinterpret_cast<const uint64_t*>(b->qmem + D.seeds);
+  d.cadd = D.cadd;
+  d.nsamp = D.nsamp;
+  d.sample0 = (uint64_t)D.sample0;
+  d.maxcb = D.maxcb;
+  d.flops = (double)D.nsamp * (double)Q.sc;
+  for (const MidLaunch& l : D.launches)
+    if (int r = launch_mid(ctx, l, a, nullptr, nullptr, &d)) return r;
+  int* hst = reinterpret_cast<int*>(b->hbuf + b->h_status);
+  e = hipMemcpyAsync(hst, dst, (size_t)np * sizeof(int), hipMemcpyDeviceToHost, ctx->stream);
+  if (e == hipSuccess && mean)
+    e = hipMemcpyAsync(mean, pbase + Q.mean, (size_t)Q.sm * 8, hipMemcpyDeviceToHost, ctx->stream);
+  if (e == hipSuccess && logp)
+    e = hipMemcpyAsync(logp, qbase + D.out, (size_t)np * 8, hipMemcpyDeviceToHost, ctx->stream);
+  if (e == hipSuccess && D.nsamp > 0)
+    e = hipMemcpyAsync(samples, qbase + D.X, (size_t)(D.nsamp * D.sm) * 8, hipMemcpyDeviceToHost,
+                       ctx->stream);
+  if (e != hipSuccess) return hip_fail(ctx, e, "lfm_mbatch_predictive_f64: download");
+  if (int r = finish(ctx)) return r;
+  if (mean)
+    for (int64_t q = 0; q < np; ++q)
+      if (hst[q] != 0)
+        std::fill(mean + D.dp[q].mean, mean + D.dp[q].mean + D.dp[q].m, std::nan(""));
+  return batch_status(ctx, hst, np, status,
+                      "Cholesky failed: non-positive pivot in a batch problem's S or in its "
+                      "predictive covariance");
 }
 
 // One fit call: raw, mu, nu and the bias corrections into the third arena (grown here when this
@@ -1102,6 +1347,7 @@ int lfm_mbatch_destroy(lfm_mbatch* batch) {
   hipFree(batch->dmem);  // every call on the handle is synchronous: nothing of it is in flight
   if (batch->pmem) hipFree(batch->pmem);
   if (batch->fmem) hipFree(batch->fmem);
+  if (batch->qmem) hipFree(batch->qmem);
   hipHostFree(batch->hbuf);
   delete batch;
   return LFM_OK;
@@ -1161,6 +1407,31 @@ int lfm_mbatch_fit_f64(lfm_ctx* ctx, lfm_mbatch* batch, const lfm_adam* opt, int
   const MidFitPlan F = plan_mid_fit(batch->shapes, nsteps);
   if (F.reject) return set_err(ctx, LFM_E_ARG, F.why);
   return mid_fit_call(ctx, batch, F, opt, negative, step0, raw, mu, nu, history, status);
+}
+
+int lfm_mbatch_predictive_f64(lfm_ctx* ctx, lfm_mbatch* batch, const double* hyp,
+                              const double* diag_vec, const double* diag_add, const int64_t* m,
+                              const double* t, const double* cov_add, const double* ystar,
+                              double* logp, const uint64_t* seeds, int64_t sample0, int64_t nsamp,
+                              double* mean, double* samples, int* status) {
+  if (!ctx) return LFM_E_ARG;
+  const std::string who = "lfm_mbatch_predictive_f64: ";
+  if (!batch || !hyp || !diag_add || !m || !t)
+    return set_err(ctx, LFM_E_ARG, who + "batch / hyp / diag_add / m / t is NULL");
+  if ((ystar != nullptr) != (logp != nullptr))
+    return set_err(ctx, LFM_E_ARG, who + "ystar and logp must be given together");
+  if (nsamp > 0 && !seeds) return set_err(ctx, LFM_E_ARG, who + "seeds is NULL with nsamp > 0");
+  if ((nsamp > 0) != (samples != nullptr))
+    return set_err(ctx, LFM_E_ARG, who + "samples must be given exactly when nsamp > 0");
+  if (batch->device != ctx->device)
+    return set_err(ctx, LFM_E_ARG, who + "batch of another device");
+  const MidDrawPlan D =
+      plan_mid_draw(batch->shapes, m, cov_add != nullptr, ystar != nullptr, nsamp, sample0);
+  if (D.reject) return set_err(ctx, LFM_E_ARG, D.why);
+  const MidPostPlan Q = plan_mid_post(batch->shapes, m, diag_vec != nullptr, true);
+  if (Q.reject) return set_err(ctx, LFM_E_ARG, Q.why);
+  return mid_draw_call(ctx, batch, Q, D, hyp, diag_vec, diag_add, t, cov_add, ystar, logp, seeds,
+                       mean, samples, status);
 }
 
 }  // extern "C"

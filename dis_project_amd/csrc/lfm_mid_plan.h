@@ -77,9 +77,15 @@ struct MidProb {
 //                  step 0 (and its first-bad-step word cleared)
 //   MID_ADAM       step k's loss and first-bad-step word, the problem's Adam update and the next
 //                  step's constrained hyperparameters
+// and of a predictive call (plan_mid_draw), on the second table (n = m, nq block rows):
+//   MID_DRAW_SCALE    lower tile u of the covariance's augmented matrix
+//   MID_DRAW_RANDN    the pairs u, u + gy, ... of the problem's normals Z
+//   MID_DRAW_PRODUCT  u = sblk * maxcb + c: the 64 x 64 tile of X = mean + Z L^T of sample block
+//                     sblk and column block cb - 1 - c (deepest first)
 enum MidKind {
   MID_FILL = 0, MID_COLUMN, MID_VALUE, MID_INVERT, MID_SINV, MID_PAIRS, MID_GRAD,
-  MID_POST_FILL, MID_SOLVE, MID_COV, MID_CONSTRAIN, MID_ADAM
+  MID_POST_FILL, MID_SOLVE, MID_COV, MID_CONSTRAIN, MID_ADAM,
+  MID_DRAW_SCALE, MID_DRAW_RANDN, MID_DRAW_PRODUCT
 };
 struct MidLaunch {
   int kind, k;
@@ -168,5 +174,60 @@ struct MidFitPlan {
 // Rejections in order: shapes that plan_mid rejects (its message); nsteps < 1; nsteps >
 // MID_FIT_MAX_STEPS (the limit is named in `why`)
 MidFitPlan plan_mid_fit(const std::vector<MidShape>& shapes, int64_t nsteps);
+
+// ---------------------------------------------------------------- the predictive call
+// lfm_mbatch_predictive_f64 draws from, and scores held-out values under, N(mean_p, cov_p +
+// cov_add[p] I) of every problem: after the posterior call's launches (plan_mid_post with the
+// covariance, unchanged) the m_p x m_p covariance is itself an augmented matrix that
+// mid_column_kernel factors, described by a second MidProb table (n = m_p) whose offsets lie in a
+// fourth device arena that the handle owns (allocated at the first predictive call, regrown when a
+// call needs more). With Mq = 64 ceil((m + 1) / 64), nq = Mq / 64, cb = ceil(m / 64) and
+// sb = ceil(nsamp / 64), in doubles from its base, each region rounded up to 2 doubles (16-byte
+// alignment): cov_add [nprob], logp [nprob], ystar [sum m] (when given); per problem the augmented
+// matrix A [Mq x Mq] (lower tiles: cov + cov_add I, row m: ystar - mean or 0, identity rows), its
+// factor [Mq x Mq], the nq inverses of the factor's diagonal blocks and, with samples, the
+// normals Z [64 sb x 64 cb] (sample rows, padding generated too); then the samples X
+// [nsamp sum m], packed as the caller gets them. In bytes after them: the seeds [nprob], the
+// MidProb table and the MidDrawProb table. Per problem that is
+//   8 (2 Mq^2 + 4096 nq + 2) + 8 + sizeof(MidProb) + sizeof(MidDrawProb) bytes,
+//   plus 8 m with ystar, plus 8 (4096 sb cb + nsamp m) with samples
+// (mid_draw_problem_bytes; the whole arena adds the rounding of the shared regions, < 64 bytes).
+// The launches after the posterior's, in stream order: MID_DRAW_SCALE, MID_COLUMN for
+// k = 0 .. maxnq - 1, MID_VALUE with ystar, MID_DRAW_RANDN and MID_DRAW_PRODUCT with samples:
+// 1 + maxnq + (ystar ? 1 : 0) + (nsamp ? 2 : 0), whatever the problem count.
+// tests/native/mid_draw_plan_check.cpp checks the plan by enumeration under the sanitizers.
+constexpr int64_t MID_DRAW_MAX_NSAMP = 1 << 16;  // one call's samples (sample0 continues a draw)
+constexpr int MID_DRAW_RANDN_GY = 4096;          // the generator's grid.y at most (grid-stride)
+
+// One problem's entry of the predictive table. cov / mean: doubles into the posterior call's
+// packed covariance / mean; ystar (-1 without), Z, X (-1 without samples): doubles from the
+// fourth arena's base.
+struct MidDrawProb {
+  int m, cb, sb, pad;
+  int64_t cov, mean, ystar, Z, X;
+};
+
+struct MidDrawPlan {
+  enum Reject { OK = 0, NO_COV_ADD, BAD_NSAMP, NOTHING, TOO_MANY, BAD_SAMPLE0, RANGE, NO_ROWS,
+                BAD_M, TOO_MANY_ROWS };
+  int reject = OK;
+  std::string why;
+  int64_t nprob = 0, sm = 0, nsamp = 0, sample0 = 0;
+  int maxnq = 0, maxtiles = 0, maxcb = 0, maxsb = 0;
+  std::vector<MidProb> probs;   // the second table: n = m_p, offsets into the fourth arena
+  std::vector<MidDrawProb> dp;
+  int64_t cadd = 0, out = 0, ystar = -1, X = -1, doubles = 0;
+  size_t seeds = 0, table = 0, dtable = 0, bytes = 0;
+  std::vector<MidLaunch> launches;  // in stream order, after the posterior's
+};
+
+// bytes of one problem in the fourth arena (the formula above)
+size_t mid_draw_problem_bytes(int64_t m, bool has_ystar, int64_t nsamp);
+// Rejections in order: cov_add not given; nsamp < 0; neither ystar nor samples asked for;
+// nsamp > MID_DRAW_MAX_NSAMP; sample0 < 0; sample0 + nsamp above 2^63 - 1; then per problem in
+// order and within a problem in this order: m < 1; m no multiple of G; m > MID_MAX_N (the first
+// offending problem and the limit are named in `why`).
+MidDrawPlan plan_mid_draw(const std::vector<MidShape>& shapes, const int64_t* m, bool has_cov_add,
+                          bool has_ystar, int64_t nsamp, int64_t sample0);
 
 }  // namespace lfm

@@ -180,7 +180,9 @@ class MidBatchPredictor(_Assembly):
     on the largest n alone. ``train_datas`` as ``BatchPredictor``'s; the problems are registered
     through ``farm.MidBatchEvaluator``. With ``evaluator=`` (``MidBatchTrainer.evaluator``) that
     handle is used and the data is not uploaded a second time; its x / y must be the data's,
-    else ValueError. The context may be asked for as late as the first call."""
+    else ValueError. The context may be asked for as late as the first call. ``sample`` and
+    ``log_prob`` draw from, and score held-out values under, every problem's predictive
+    distribution on the same handle (``lfm_mbatch_predictive_f64``, at most 1024 test rows each)."""
 
     MAX_M = 4096  # LFM_MID_MAX_M
 
@@ -229,6 +231,111 @@ class MidBatchPredictor(_Assembly):
             dptr(cov) if want_cov else None, dptr(self.status))
         self.ctx.check(rc, allow_not_pd=True)
         return unpack_outputs(m, mean, var, cov)
+
+    MAX_DRAW_M = 1024       # LFM_MID_MAX_N: the covariance goes through the mid factorisation
+    MAX_DRAW_SAMPLES = 65536  # per call; sample0 continues a draw
+
+    def _predictive(self, models, test_inputs, kind, cov_add, y_star=None, num_samples=0,
+                    seeds=None, sample0=0):
+        """One ``lfm_mbatch_predictive_f64``; every argument is checked before the first device
+        call. Returns (m, mean, logp or None, samples or None), packed."""
+        models = list(models)
+        if len(models) != len(self):
+            raise ValueError("one model per registered problem")
+        if kind == "latent":
+            dadd = as_f64([mm.jitter for mm in models]).reshape(-1)
+        elif kind == "gene":
+            dadd = as_f64([mm.obs_stddev ** 2 for mm in models]).reshape(-1)
+        else:
+            raise ValueError('kind must be "latent" or "gene"')
+        P = len(models)
+        genes = [int(mm.num_genes) for mm in models]
+        t, m = pack_test_inputs(test_inputs, genes)
+        if np.any(m > self.MAX_DRAW_M):
+            raise ValueError(f"at most {self.MAX_DRAW_M} test rows per problem (LFM_MID_MAX_N: the "
+                             "covariance is factored on the handle); use Posterior.sample for "
+                             "more on one model")
+        if cov_add is None:
+            cadd = as_f64([mm.jitter for mm in models]).reshape(-1)
+        else:
+            cadd = as_f64(cov_add).reshape(-1)
+            if cadd.size == 1:
+                cadd = np.full(P, cadd[0])
+            if cadd.size != P:
+                raise ValueError("cov_add: one value, or one per problem")
+        ys = None
+        if y_star is not None:
+            if isinstance(y_star, np.ndarray) and y_star.ndim == 1 and P == 1:
+                y_star = [y_star]
+            per = [as_f64(y).reshape(-1) for y in y_star]
+            if len(per) != P or any(y.size != k for y, k in zip(per, m)):
+                raise ValueError("y_star: one array of m_p values per problem")
+            ys = np.ascontiguousarray(np.concatenate(per))
+        k = int(num_samples)
+        sd = None
+        if k > 0:
+            if k > self.MAX_DRAW_SAMPLES:
+                raise ValueError(f"at most {self.MAX_DRAW_SAMPLES} samples per call; continue "
+                                 "the draw with sample0")
+            if int(sample0) < 0:
+                raise ValueError("sample0 must be >= 0")
+            sd = np.ascontiguousarray(np.asarray(seeds, np.uint64).reshape(-1))
+            if sd.size != P:
+                raise ValueError("seeds: one per problem")
+        self._ev._pack(models)  # the packed hyperparameters; registers this gene layout
+        self.ctx = self.ctx or self._ev.ctx
+        sm = int(m.sum())
+        mean = np.empty(sm)
+        logp = np.empty(P) if ys is not None else None
+        out = np.empty(k * sm) if k > 0 else None
+        self.status = np.zeros(P, np.int32)
+        rc = self.ctx.lib.lfm_mbatch_predictive_f64(
+            self.ctx.handle, self._ev.batch, dptr(self._ev._buf), dptr(self.variances), dptr(dadd),
+            dptr(m), dptr(t), dptr(cadd), dptr(ys) if ys is not None else None,
+            dptr(logp) if logp is not None else None, dptr(sd) if sd is not None else None,
+            int(sample0), k, dptr(mean), dptr(out) if out is not None else None,
+            dptr(self.status))
+        self.ctx.check(rc, allow_not_pd=True)
+        return m, mean, logp, out
+
+    def sample(self, models, test_inputs, num_samples, seed, sample0: int = 0,
+               kind: str = "gene", cov_add=None, seeds=None):
+        """Joint draws from every fitted model's predictive distribution in one
+        ``lfm_mbatch_predictive_f64``: a list of ``(mean [m_p], samples [num_samples, m_p])`` from
+        N(mean_p, cov_p + cov_add_p I), the covariance formed, factored and multiplied on the
+        handle (at most 1024 test rows per problem). ``kind`` picks S's diagonal as ``Posterior``
+        does ("latent": jitter; "gene": obs_stddev**2); ``cov_add`` defaults to each model's
+        jitter, which with ``kind="gene"`` is ``multi_gene_predict(...)[p].sample(...)``'s
+        distribution. Problem p's seed is ``seeds[p]``, or ``(seed_to_u64(seed) + p) mod 2^64``;
+        sample ``sample0 + s`` depends on that seed and its own index alone. A problem that is
+        not positive definite gives NaN (``status`` holds the codes)."""
+        from .distributions import seed_to_u64
+
+        k = int(num_samples)
+        if k < 1:
+            raise ValueError("num_samples must be >= 1")
+        if seeds is None:
+            key = seed_to_u64(seed)
+            seeds = [(key + p) % (1 << 64) for p in range(len(self))]
+        m, mean, _, out = self._predictive(models, test_inputs, kind, cov_add, None, k, seeds,
+                                           sample0)
+        res, o = [], 0
+        for mp in (int(v) for v in m):
+            res.append((mean[o:o + mp].copy(), out[k * o:k * (o + mp)].reshape(k, mp).copy()))
+            o += mp
+        return res
+
+    def log_prob(self, models, test_inputs, y_star, kind: str = "gene", cov_add=None):
+        """``[P]``: log N(y_star_p; mean_p, cov_p + cov_add_p I) of every problem in one
+        ``lfm_mbatch_predictive_f64`` — with the defaults ``multi_gene_predict(...)[p].log_prob(
+        y_star_p)``, the held-out log density of, say, replicate 2's measurements under a model
+        fitted on replicate 1. A caller scoring noisy replicates passes ``cov_add =
+        obs_stddev**2 + jitter``. ``y_star``: one array of m_p values per problem. NaN where not
+        positive definite (``status`` holds the codes)."""
+        if y_star is None:
+            raise ValueError("y_star: one array of m_p values per problem")
+        _, _, logp, _ = self._predictive(models, test_inputs, kind, cov_add, y_star)
+        return logp
 
     def close(self):
         if self._own:

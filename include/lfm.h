@@ -293,6 +293,87 @@ int lfm_mbatch_mll_grad_f64(lfm_ctx* ctx, lfm_mbatch* batch, const double* hyp, 
 int lfm_mbatch_posterior_f64(lfm_ctx* ctx, lfm_mbatch* batch, const double* hyp,
                              const double* diag_vec, const double* diag_add, const int64_t* m,
                              const double* t, double* mean, double* var, double* cov, int* status);
+/* Joint samples from, and the log density of held-out values under, the distribution that
+ * multi_gene_predict returns (model.py:467-514) for every problem of an lfm_mbatch, without the
+ * covariance leaving the device: GaussianDistribution.sample / .log_prob (the gpjax call of
+ * objectives.py:78) of N(mean_p, cov_p + cov_add[p] I), mean_p and cov_p as
+ * lfm_mbatch_posterior_f64 defines them. hyp, diag_vec, diag_add, m, t, mean and status follow
+ * that call exactly; the caller applies the jitter through cov_add (the shim,
+ * dis_project_amd.predict.MidBatchPredictor.sample / .log_prob, passes each model's), which joins
+ * each diagonal entry of cov_p in one addition.
+ *   cov_add [nprob]
+ *   ystar   packed [sum m_p] or NULL; logp [nprob], given exactly when ystar is:
+ *           logp[p] = log N(ystar_p; mean_p, cov_p + cov_add[p] I)
+ *   seeds   [nprob], required when nsamp > 0; sample0 >= 0, nsamp >= 0
+ *   mean    packed [sum m_p], may be NULL
+ *   samples given exactly when nsamp > 0: problem p's block is [nsamp x m_p] row-major at offset
+ *           nsamp * sum_{q<p} m_q; row s is mean_p + L_p z, L_p L_p^T the matrix above, element j
+ *           of z the generator's normal (seeds[p], sample0 + s, j) defined below at lfm_randn_f64,
+ *           bit for bit what lfm_randn_f64(seeds[p], ...) returns.
+ * At least one of (ystar, logp) and nsamp > 0 must be asked for. Every m_p must satisfy
+ * 1 <= m_p <= LFM_MID_MAX_N (1024: the covariance goes through the mid-size factorisation; for a
+ * larger m on one model use lfm_post_*) and m_p % G_p == 0; nsamp <= 65536 a call (continue a
+ * draw with sample0), sample0 + nsamp must not overflow. A violation, a NULL required pointer, a
+ * pointer of a pair given without the other, or a handle of another device is LFM_E_ARG with a
+ * message naming the limit or the pointer, and touches no caller buffer. The plan rejects in this
+ * order: cov_add NULL; nsamp < 0; nothing asked for; nsamp > 65536; sample0 < 0; sample0 + nsamp
+ * overflowing; then per problem m_p < 1, m_p % G_p != 0, m_p > LFM_MID_MAX_N.
+ *
+ * Not positive definite means a failed pivot in S_p or in the factor of cov_p + cov_add[p] I:
+ * that problem's logp, samples and mean are NaN, status[p] = LFM_E_NOT_PD and the call returns
+ * LFM_E_NOT_PD; every other problem's outputs are valid and the same bits as without it. (Latent
+ * test rows, flag 0, give an indefinite joint covariance: DESIGN.md section 4.10.)
+ *
+ * Launches, on the ctx's stream in order: those of lfm_mbatch_posterior_f64 with the covariance
+ * (ceil((n_max + 1) / 64) + 3, unchanged); one scale launch (problem x lower tile) that copies
+ * cov_p into a fresh augmented matrix of stride 64 ceil((m_p + 1) / 64) with cov_add on the
+ * diagonal and ystar_p - mean_p (or 0) as its row m_p; the mid-size factorisation's column launch,
+ * unchanged, ceil((m_max + 1) / 64) times on a second problem table; with ystar the value launch,
+ * unchanged; with nsamp > 0 the normals and one product launch (one workgroup per 64 x 64 tile
+ * of X_p = mean_p + Z_p L_p^T, depth 64 (tj + 1) on the fp64 MFMA over the factor's lower tiles;
+ * the K order and the tile shape depend on neither nsamp nor sample0). In all
+ *   ceil((n_max + 1) / 64) + ceil((m_max + 1) / 64) + 4 + (ystar ? 1 : 0) + (nsamp > 0 ? 2 : 0)
+ * launches, whatever the problem count. No atomics, no device-side waits, no cooperative launch,
+ * no graph capture. The same inputs give the same bits; a problem's bits depend on its own data,
+ * hyperparameters, test rows, cov_add, ystar and seed alone, not on the other problems, their
+ * sizes or its position. Rows [0, k) of an nsamp-sample call are the k-sample call's, and rows
+ * [k, nsamp) those of the call at sample0 + k. mean is lfm_mbatch_posterior_f64's mean bit for
+ * bit; logp has the same bits whether or not samples are asked for, and the samples whether or
+ * not ystar is given. A later lfm_mbatch_mll_f64, lfm_mbatch_mll_grad_f64,
+ * lfm_mbatch_posterior_f64 or lfm_mbatch_fit_f64 call on the handle returns the bits it returns
+ * on a fresh handle, because each call refills what it reads. Synchronous; holds the device's
+ * lock shared.
+ *
+ * The call works in the posterior call's arena (with the covariance) and in a fourth device arena
+ * that the handle owns (allocated at the first predictive call, regrown when a call needs more,
+ * freed by lfm_mbatch_destroy; never the ctx workspace): per problem, with
+ * Mq = 64 ceil((m_p + 1) / 64), nq = Mq / 64, cb = ceil(m_p / 64) and sb = ceil(nsamp / 64),
+ *   8 (2 Mq^2 + 4096 nq + 2) + 152 bytes, plus 8 m_p with ystar,
+ *   plus 8 (4096 sb cb + nsamp m_p) with samples
+ * (at m = 1024: 19.5 MB, and 16.8 MB more per 1024 samples). A failed allocation is LFM_E_OOM and
+ * the handle stays usable.
+ *
+ * Measured on an MI355X (scripts/mid_sample_rate.py,
+ * profiles/mid_sample.json, mid_sample_p4.json; 5-gene grids, gene rows, cov_add = jitter; medians
+ * of synchronous calls) against lfm_mbatch_posterior_f64 with the covariance followed by one
+ * lfm_mvn_sample_f64 (for logp: lfm_log_prob_f64) per problem. With 15 problems and m = 100 the
+ * one call takes 1.17 ms for 16 samples at n = 160 against the loop's 4.70 (4.0x), 1.92 against
+ * 5.55 at 320 (2.9x), 3.88 against 7.39 at 640 (1.9x), 6.99 against 10.65 at 1020 (1.5x); 1024
+ * samples 3.8x, 2.8x, 2.0x, 1.5x; logp alone 2.8x, 2.1x, 1.5x, 1.3x. At m = 400: 16 samples 4.8x,
+ * 3.9x, 2.8x, 2.1x; 1024 samples 4.4x, 3.8x, 2.8x, 2.2x (9.97 ms against 22.31 at n = 1020); logp
+ * 3.0x, 2.5x, 1.9x, 1.5x. A call's time is set by the largest n and m, hardly by the problem
+ * count, so with 4 problems the lead is smaller: m = 100, 16 samples 1.6x, 1.4x, 1.2x, 1.13x;
+ * 1024 samples 1.8x, 1.5x, 1.2x, 1.14x; logp 1.3x, 1.2x, 1.10x, 1.07x; m = 400, 16 samples 2.1x,
+ * 1.8x, 1.5x, 1.2x; 1024 samples 1.7x, 1.6x, 1.4x, 1.3x; logp 1.2x, 1.1x, 1.09x, 1.06x. No shape
+ * measured has the loop ahead. The product launch is 0.4 to 7.4 % of the call (0.027 ms for 16
+ * samples at m = 100, 0.27 ms for 1024 samples at m = 400 with 15 problems) and reaches 0.1 %
+ * (16 samples, m = 100) to 12 % (1024 samples, m = 400) of the 78.6 TFLOP/s fp64 matrix spec on
+ * nsamp sum m^2 flops; the call's time is in the column launches. */
+int lfm_mbatch_predictive_f64(lfm_ctx* ctx, lfm_mbatch* batch, const double* hyp,
+                              const double* diag_vec, const double* diag_add, const int64_t* m,
+                              const double* t, const double* cov_add, const double* ystar,
+                              double* logp, const uint64_t* seeds, int64_t sample0, int64_t nsamp,
+                              double* mean, double* samples, int* status);
 
 /* optax.adam(learning_rate, b1, b2, eps, eps_root) and JaxTrainer.fit's epoch handling
  * (src/trainer.py:162-228; src/main.py:45 and notebook.py:55 use adam(0.01)). */

@@ -1,0 +1,522 @@
+"""Joint samples and held-out log density on the mid-size resident batch
+(lfm_mbatch_predictive_f64, predict.MidBatchPredictor.sample / .log_prob): N(mean_p, cov_p +
+cov_add_p I) of every problem of an lfm_mbatch, the covariance factored on the handle.
+
+The reference of every numeric check is numpy's Cholesky on (mean, cov + cov_add I) taken from
+lfm_mbatch_posterior_f64 on the same handle, with the normals of lfm_randn_f64; the bound is
+50 kappa m eps max(1, |ref|) (the samples: max|ref|) with kappa computed here, the form
+tests/test_gpu_sample.py uses for the resident path. Inputs: tests/mid_draw_inputs.py.
+
+  1. log density, 2. samples: every edge problem in one batch and the cap alone, cov_add 1e-4
+     and 0.49; 3. bit identities; 4. moments; 5. failures and refusals; 6. the Python shim.
+"""
+
+import ctypes
+
+import numpy as np
+import pytest
+
+from tests import mid_draw_inputs as DI
+
+pytestmark = pytest.mark.gpu
+
+SEED0 = 1000
+
+
+def ctx0():
+    from dis_project_amd import _lib
+
+    return _lib.get_context(0)
+
+
+def randn(seed, sample0, nsamp, n):
+    from dis_project_amd import _lib
+
+    ctx = ctx0()
+    out = np.full((nsamp, n), 7.0)
+    ctx.check(ctx.lib.lfm_randn_f64(ctx.handle, int(seed), sample0, nsamp, n, _lib.dptr(out)))
+    return out
+
+
+class Batch:
+    """An lfm_mbatch over the given problems, its posterior call and its predictive call."""
+
+    def __init__(self, probs):
+        import dis_project_amd as lfm
+        from dis_project_amd import farm
+        from dis_project_amd.dataset import Dataset
+
+        self.probs = list(probs)
+        self.ctx = ctx0()
+        self.models = [lfm.ExactLFM(jitter=1e-4, num_genes=p["G"], true_d=p["D"], true_s=p["S"],
+                                    true_b=p["B"], l=DI.L, obs_stddev=DI.OBS)
+                       for p in self.probs]
+        self.ev = farm.MidBatchEvaluator(self.ctx, [Dataset(np.array(p["x"]), np.array(p["y"]))
+                                                    for p in self.probs])
+        self.ev._pack(self.models)
+        self.hyp = self.ev._buf
+        self.m = np.asarray([p["m"] for p in self.probs], np.int64)
+        self.seeds = np.arange(SEED0, SEED0 + len(self.probs), dtype=np.uint64)
+
+    def _common(self, ts, dv, dadd):
+        ts = [p["t"] for p in self.probs] if ts is None else ts
+        m = np.asarray([t.shape[0] for t in ts], np.int64)
+        t = np.ascontiguousarray(np.concatenate(ts))
+        if dv is None:
+            dv = np.concatenate([p["v"] for p in self.probs])
+        dadd = np.ascontiguousarray(np.broadcast_to(np.asarray(dadd, np.float64), m.shape))
+        return m, t, np.ascontiguousarray(dv), dadd
+
+    def post(self):
+        """lfm_mbatch_posterior_f64 with the covariance -> [(mean, cov)]."""
+        from dis_project_amd import _lib
+
+        m, t, dv, dadd = self._common(None, None, DI.OBS ** 2)
+        mean, cov = np.empty(int(m.sum())), np.empty(int((m * m).sum()))
+        rc = self.ctx.lib.lfm_mbatch_posterior_f64(
+            self.ctx.handle, self.ev.batch, _lib.dptr(self.hyp), _lib.dptr(dv), _lib.dptr(dadd),
+            _lib.dptr(m), _lib.dptr(t), _lib.dptr(mean), None, _lib.dptr(cov), None)
+        assert rc == 0
+        out, o1, o2 = [], 0, 0
+        for k in (int(v) for v in m):
+            out.append((mean[o1:o1 + k].copy(), cov[o2:o2 + k * k].reshape(k, k).copy()))
+            o1 += k
+            o2 += k * k
+        return out
+
+    def pred(self, cov_add, ystar=None, nsamp=0, sample0=2, seeds=None, ts=None, dv=None,
+             dadd=DI.OBS ** 2, want_mean=True, raw=None):
+        """-> (rc, [(mean, logp, samples)], status). ystar: a list of arrays or None. raw: a dict
+        of pointer overrides by argument name (None = NULL), for the refusals."""
+        from dis_project_amd import _lib
+
+        m, t, dv, dadd = self._common(ts, dv, dadd)
+        P, sm = len(m), int(m.sum())
+        cadd = np.ascontiguousarray(np.broadcast_to(np.asarray(cov_add, np.float64), m.shape))
+        ys = None if ystar is None else np.ascontiguousarray(np.concatenate(ystar))
+        logp = None if ystar is None else np.full(P, 7.0)
+        seeds = self.seeds if seeds is None else np.ascontiguousarray(seeds, dtype=np.uint64)
+        mean = np.full(sm, 7.0) if want_mean else None
+        out = np.full(nsamp * sm, 7.0) if nsamp > 0 and "samples" not in (raw or {}) else None
+        status = np.full(P, -1, np.int32)
+        args = dict(hyp=self.hyp, diag_vec=dv, diag_add=dadd, m=m, t=t, cov_add=cadd, ystar=ys,
+                    logp=logp, seeds=seeds if nsamp > 0 else None, mean=mean, samples=out,
+                    status=status)
+        args.update(raw or {})
+        self.last = args
+        ptr = lambda a: None if a is None else _lib.dptr(a)  # noqa: E731
+        rc = self.ctx.lib.lfm_mbatch_predictive_f64(
+            self.ctx.handle, self.ev.batch, ptr(args["hyp"]), ptr(args["diag_vec"]),
+            ptr(args["diag_add"]), ptr(args["m"]), ptr(args["t"]), ptr(args["cov_add"]),
+            ptr(args["ystar"]), ptr(args["logp"]), ptr(args["seeds"]), int(sample0), int(nsamp),
+            ptr(args["mean"]), ptr(args["samples"]), ptr(args["status"]))
+        res, o = [], 0
+        for q, k in enumerate(int(v) for v in m):
+            res.append((None if mean is None else mean[o:o + k].copy(),
+                        None if logp is None else float(logp[q]),
+                        None if out is None else out[nsamp * o:nsamp * (o + k)]
+                        .reshape(nsamp, k).copy()))
+            o += k
+        return rc, res, status
+
+    def err(self):
+        return self.ctx.lib.lfm_last_error(self.ctx.handle)
+
+    def close(self):
+        self.ev.close()
+
+
+@pytest.fixture(scope="module")
+def edge():
+    b = Batch(DI.edge_problems())
+    yield b
+    b.close()
+
+
+@pytest.fixture(scope="module")
+def cap():
+    b = Batch([DI.problem(*DI.CAP)])
+    yield b
+    b.close()
+
+
+_REFS = {}
+
+
+def refs(batch, name):
+    """Per problem and cov_add: (mean, scale, cholesky, 50 kappa m eps), computed once from the
+    handle's own posterior call and never modified."""
+    store = _REFS.setdefault(name, {})
+    if not store:
+        for ca in DI.COV_ADDS:
+            rows = []
+            for mean, cov in batch.post():
+                scale = cov + ca * np.eye(len(mean))
+                chol = np.linalg.cholesky(scale)
+                for a in (mean, scale, chol):
+                    a.setflags(write=False)
+                rows.append((mean, scale, chol, DI.bound_factor(scale)))
+            store[ca] = rows
+    return store
+
+
+def ystars(batch, name):
+    return [DI.ystar(mean, q) for q, (mean, _, _, _) in enumerate(refs(batch, name)[1e-4])]
+
+
+def same(a, b):
+    for u, v in zip(a, b):
+        if u is None or v is None:
+            assert u is None and v is None
+        else:
+            np.testing.assert_array_equal(u, v)
+
+
+# ------------------------------------------------------------------ 1. log density
+@pytest.mark.parametrize("cov_add", DI.COV_ADDS)
+@pytest.mark.parametrize("name", ["edge", "cap"])
+def test_log_density(request, name, cov_add):
+    b = request.getfixturevalue(name)
+    ys = ystars(b, name)
+    rc, res, status = b.pred(cov_add, ystar=ys)
+    assert rc == 0 and not status.any(), b.err()
+    for q, ((mean, logp, x), (rmean, scale, _, f)) in enumerate(zip(res, refs(b, name)[cov_add])):
+        np.testing.assert_array_equal(mean, rmean)
+        assert x is None
+        ref = DI.chol_log_prob(ys[q], rmean, scale)
+        d, bound = abs(logp - ref), f * max(1.0, abs(ref))
+        print(f"{name} m = {len(mean)} cov_add = {cov_add:g}: logp {logp:.6f} |d| = {d:.2e}, "
+              f"bound {bound:.2e}")
+        assert d <= bound
+
+
+# ------------------------------------------------------------------ 2. samples
+@pytest.mark.parametrize("cov_add", DI.COV_ADDS)
+@pytest.mark.parametrize("name", ["edge", "cap"])
+def test_samples(request, name, cov_add):
+    b = request.getfixturevalue(name)
+    for nsamp in (1, 3, 65, 130):
+        rc, res, status = b.pred(cov_add, nsamp=nsamp, sample0=2)
+        assert rc == 0 and not status.any(), b.err()
+        for q, ((mean, logp, x), (rmean, _, chol, f)) in enumerate(
+                zip(res, refs(b, name)[cov_add])):
+            assert logp is None and x.shape == (nsamp, len(rmean))
+            z = randn(b.seeds[q], 2, nsamp, len(rmean))
+            ref = rmean + z @ chol.T
+            d, bound = float(np.max(np.abs(x - ref))), f * float(np.max(np.abs(ref)))
+            print(f"{name} m = {len(rmean)} cov_add = {cov_add:g} nsamp = {nsamp}: "
+                  f"max|d| = {d:.2e}, bound {bound:.2e}")
+            assert d <= bound
+
+
+# ------------------------------------------------------------------ 3. bit identities
+def test_bit_identities(edge):
+    ca, nsamp, k = 1e-4, 130, 37
+    ys = ystars(edge, "edge")
+    rc, ref, _ = edge.pred(ca, ystar=ys, nsamp=nsamp)
+    assert rc == 0
+    rc, again, _ = edge.pred(ca, ystar=ys, nsamp=nsamp)
+    assert rc == 0
+    for a, r in zip(again, ref):
+        same(a, r)
+    # mean against the posterior call
+    for (mean, _), r in zip(edge.post(), ref):
+        np.testing.assert_array_equal(mean, r[0])
+    # logp with and without samples, samples with and without ystar; no mean asked for
+    rc, lp_only, _ = edge.pred(ca, ystar=ys)
+    assert rc == 0
+    rc, x_only, _ = edge.pred(ca, nsamp=nsamp, want_mean=False)
+    assert rc == 0
+    for a, b_, r in zip(lp_only, x_only, ref):
+        assert a[1] == r[1] and b_[0] is None
+        np.testing.assert_array_equal(b_[2], r[2])
+    # splits of the draw
+    rc, head, _ = edge.pred(ca, nsamp=k, sample0=2)
+    assert rc == 0
+    rc, tail, _ = edge.pred(ca, nsamp=nsamp - k, sample0=2 + k)
+    assert rc == 0
+    for h, t, r in zip(head, tail, ref):
+        np.testing.assert_array_equal(h[2], r[2][:k])
+        np.testing.assert_array_equal(t[2], r[2][k:])
+    # other seeds
+    rc, other, _ = edge.pred(ca, nsamp=k, seeds=edge.seeds + np.uint64(77))
+    assert rc == 0
+    for o, h in zip(other, head):
+        assert not np.array_equal(o[2], h[2])
+    # each problem alone, and the batch reversed
+    for q, p in enumerate(edge.probs):
+        one = Batch([p])
+        try:
+            rc, [got], _ = one.pred(ca, ystar=[ys[q]], nsamp=nsamp, seeds=edge.seeds[q:q + 1])
+        finally:
+            one.close()
+        assert rc == 0
+        same(got, ref[q])
+    rev = Batch(edge.probs[::-1])
+    try:
+        rc, got, _ = rev.pred(ca, ystar=ys[::-1], nsamp=nsamp, seeds=edge.seeds[::-1])
+    finally:
+        rev.close()
+    assert rc == 0
+    for a, r in zip(got, ref[::-1]):
+        same(a, r)
+
+
+def _handle_calls(b):
+    """mll, mll_grad, posterior and a 3-step fit on the handle: everything they return."""
+    from dis_project_amd import trainer as TR
+
+    out = [b.ev(b.models)]
+    v, g = b.ev.value_and_grad(b.models)
+    out.append(v)
+    out += [np.asarray(gq[k]) for gq in g for k in sorted(gq)]
+    for mean, cov in b.post():
+        out += [mean, cov]
+    raw = TR.pack_raw([TR.unconstrain(m) for m in b.models], [m.jitter for m in b.models])
+    mu, nu = np.zeros_like(raw), np.zeros_like(raw)
+    hist, st = b.ev.fit_packed(raw, mu, nu, TR.adam(0.01), False, 4, 0, 3)
+    out += [raw, mu, nu, hist, np.asarray(st)]
+    return out
+
+
+def test_the_handle_is_unchanged_by_a_predictive_call():
+    probs = [DI.problem(*DI.EDGE[0]), DI.problem(*DI.EDGE[5])]
+    fresh = Batch(probs)
+    try:
+        before = _handle_calls(fresh)
+    finally:
+        fresh.close()
+    b = Batch(probs)
+    try:
+        same_handle = _handle_calls(b)
+        ys = [np.zeros(p["m"]) for p in probs]
+        rc, _, _ = b.pred(1e-4, ystar=ys, nsamp=65)
+        assert rc == 0
+        after = _handle_calls(b)
+    finally:
+        b.close()
+    assert len(before) == len(after) == len(same_handle)
+    for u, v, w in zip(before, after, same_handle):
+        np.testing.assert_array_equal(u, v)  # a fresh handle's bits
+        np.testing.assert_array_equal(w, v)  # and this handle's before the call
+        assert np.all(np.isfinite(u))
+
+
+# ------------------------------------------------------------------ 4. moments
+def test_moments():
+    S, ca = 2048, 0.49
+    b = Batch([DI.problem(5, 64, 130)])
+    try:
+        [(mean, cov)] = b.post()
+        rc, [(_, _, x)], _ = b.pred(ca, nsamp=S, sample0=0)
+    finally:
+        b.close()
+    assert rc == 0
+    c = cov + ca * np.eye(len(mean))
+    xc = x - mean
+    second = xc.T @ xc / S
+    se = np.sqrt((c * c + np.outer(np.diag(c), np.diag(c))) / S)
+    zmom = float(np.max(np.abs(second - c) / se))
+    zmean = float(np.max(np.abs(xc.mean(0)) / np.sqrt(np.diag(c) / S)))
+    print(f"second moments: max |d| / SE = {zmom:.2f}; means: {zmean:.2f}")
+    assert zmom <= 5.0
+    assert zmean <= 4.5
+
+
+# ------------------------------------------------------------------ 5. failures
+def _failing_diag(p, row, dadd):
+    """diag_vec whose entry `row` makes pivot `row` of S <= -1 (tests/test_gpu_mid_predict.py)."""
+    from oracle import lfm_oracle as O
+
+    x = p["x"][row:row + 1]
+    k = float(O.cross_covariance(x, x, p["D"], p["S"], DI.L)[0, 0])
+    v = np.array(p["v"])
+    v[row] = -(k + dadd + 1.0)
+    return v
+
+
+def test_not_pd_problems_are_nan_and_the_others_keep_their_bits(edge):
+    from dis_project_amd import _lib
+
+    nsamp = 65
+    ys = ystars(edge, "edge")
+    rc, clean, _ = edge.pred(1e-4, ystar=ys, nsamp=nsamp)
+    assert rc == 0
+    bad_add, bad_latent, bad_s = 1, 6, 4
+    assert DI.EDGE[bad_latent] == DI.LATENT
+    cadd = np.full(len(edge.probs), 1e-4)
+    cadd[bad_add] = -50.0
+    ts = [p["t"] for p in edge.probs]
+    ts[bad_latent] = DI.problem(*DI.LATENT, flag=0.0)["t"]
+    vs = [np.array(p["v"]) for p in edge.probs]
+    vs[bad_s] = _failing_diag(edge.probs[bad_s], 100, DI.OBS ** 2)
+    rc, res, status = edge.pred(cadd, ystar=ys, nsamp=nsamp, ts=ts, dv=np.concatenate(vs))
+    assert rc == _lib.LFM_E_NOT_PD
+    for q, (got, ref) in enumerate(zip(res, clean)):
+        if q in (bad_add, bad_latent, bad_s):
+            assert status[q] == _lib.LFM_E_NOT_PD
+            assert np.all(np.isnan(got[0])) and np.isnan(got[1]) and np.all(np.isnan(got[2]))
+        else:
+            assert status[q] == 0
+            same(got, ref)
+    # with cov_add = 0.49 the latent rows' covariance is definite
+    cadd[:] = 0.49
+    rc, res, status = edge.pred(cadd, ystar=ys, nsamp=1, ts=ts)
+    assert rc == 0 and not status.any() and np.isfinite(res[bad_latent][1])
+    rc, again, _ = edge.pred(1e-4, ystar=ys, nsamp=nsamp)
+    assert rc == 0
+    for a, r in zip(again, clean):
+        same(a, r)
+
+
+def test_argument_rules(edge):
+    from dis_project_amd import _lib
+
+    ys = ystars(edge, "edge")
+    rc, clean, _ = edge.pred(1e-4, ystar=ys, nsamp=3)
+    assert rc == 0
+
+    def refused(word, **kw):
+        rc, _, _ = edge.pred(1e-4, **kw)
+        assert rc == _lib.LFM_E_ARG, (word, rc)
+        assert word in edge.err(), (word, edge.err())
+        for name in ("logp", "mean", "samples"):
+            a = edge.last.get(name)
+            if isinstance(a, np.ndarray):
+                assert np.all(a == 7.0), name
+        st = edge.last.get("status")
+        if isinstance(st, np.ndarray):
+            assert np.all(st == -1)
+
+    refused(b"nothing")                                      # neither logp nor samples
+    refused(b"nsamp", nsamp=-1)
+    refused(b"65536", ystar=ys, nsamp=65537, raw=dict(samples=np.full(1, 7.0)))
+    refused(b"sample0", nsamp=2, sample0=-1)
+    refused(b"overflows", nsamp=2, sample0=2 ** 63 - 2)
+    refused(b"logp", ystar=ys, raw=dict(logp=None))
+    refused(b"ystar", raw=dict(logp=np.full(len(ys), 7.0)))
+    refused(b"seeds", nsamp=2, raw=dict(seeds=None))
+    refused(b"samples", nsamp=2, raw=dict(samples=None))
+    refused(b"samples", ystar=ys, raw=dict(samples=np.full(4, 7.0)))
+    refused(b"cov_add", ystar=ys, raw=dict(cov_add=None))
+    for hole in ("hyp", "diag_add", "m", "t"):
+        refused(hole.encode(), ystar=ys, raw={hole: None})
+    ts = [p["t"] for p in edge.probs]
+    bad = list(ts)
+    bad[5] = ts[5][:65]  # 65 % 3 != 0
+    refused(b"multiple", nsamp=2, ts=bad)
+    bad[5] = ts[5][:0]
+    refused(b"m >= 1", nsamp=2, ts=bad)
+    bad = list(ts)
+    bad[7] = np.tile(ts[7], (4, 1))[:1025]  # G = 5: 1025 rows
+    refused(b"1024", nsamp=2, ts=bad)
+    assert b"lfm_post" in edge.err()
+    assert edge.ctx.lib.lfm_mbatch_predictive_f64(
+        edge.ctx.handle, None, *([ctypes.c_void_p(8)] * 9), 0, 1, None, None,
+        None) == _lib.LFM_E_ARG
+    if _lib.device_count() >= 2:
+        other = _lib.Context(1)
+        try:
+            save, edge.ctx = edge.ctx, other
+            rc, _, _ = edge.pred(1e-4, ystar=ys)
+            edge.ctx = save
+            assert rc == _lib.LFM_E_ARG
+        finally:
+            other.close()
+    rc, again, _ = edge.pred(1e-4, ystar=ys, nsamp=3)  # the handle works afterwards
+    assert rc == 0
+    for a, r in zip(again, clean):
+        same(a, r)
+
+
+def test_launch_count_depends_on_the_largest_sizes_alone():
+    p = DI.problem(3, 43, 129)  # n = 129: 3 block columns; m = 129: 3 block columns
+    nb = (p["n"] + 1 + 63) // 64
+    nq = (p["m"] + 1 + 63) // 64
+    counts = {}
+    for copies in (1, 6):
+        b = Batch([p] * copies)
+        ys = [np.zeros(p["m"])] * copies
+        try:
+            b.ctx.profile(True)
+            for key, kw in (("logp", dict(ystar=ys)), ("draw", dict(nsamp=3)),
+                            ("both", dict(ystar=ys, nsamp=3))):
+                b.ctx.profile_reset()
+                rc, _, _ = b.pred(1e-4, **kw)
+                assert rc == 0
+                stats = b.ctx.profile_read()
+                counts[copies, key] = sum(s["launches"] for k, s in stats.items()
+                                          if k.startswith(("mid_", "sample_")))
+        finally:
+            b.ctx.profile(False)
+            b.close()
+    base = nb + nq + 4
+    want = {(c, k): base + e for c in (1, 6) for k, e in (("logp", 1), ("draw", 2), ("both", 3))}
+    assert counts == want, counts
+
+
+# ------------------------------------------------------------------ 6. the shim
+def test_predictor_sample_and_log_prob_after_a_device_fit():
+    import dis_project_amd as lfm
+    from dis_project_amd import _lib
+    from dis_project_amd import trainer as TR
+    from dis_project_amd.dataset import (Dataset, SyntheticP53Data, dataset_3d,
+                                         generate_test_times_pred)
+
+    datas = [SyntheticP53Data(replicate=0, num_timepoints=30),
+             SyntheticP53Data(replicate=0, num_timepoints=64)]
+    sets = []
+    for d in datas:
+        x, y, _ = dataset_3d(d)
+        sets.append(Dataset(np.asarray(x, np.float64).reshape(-1, 3),
+                            np.asarray(y, np.float64).reshape(-1)))
+    models = [lfm.ExactLFM(jitter=1e-4, num_genes=5, device=0) for _ in datas]
+    bt = TR.MidBatchTrainer(models, lfm.CustomConjMLL(negative=True), sets, TR.adam(0.01),
+                            num_iters=3, on_device=True)
+    bp = None
+    try:
+        fitted, _ = bt.fit(fix_params=False)
+        bp = lfm.MidBatchPredictor(datas, evaluator=bt.evaluator)
+        t_gene = np.asarray(generate_test_times_pred(20, 5), np.float64)
+        m = t_gene.shape[0]
+        dists = bp.multi_gene_predict(fitted, t_gene)
+        ys = [DI.ystar(np.asarray(d.loc), q) for q, d in enumerate(dists)]
+        lp = bp.log_prob(fitted, t_gene, ys)
+        assert lp.shape == (2,) and not bp.status.any()
+        drawn = bp.sample(fitted, t_gene, 5, 42, sample0=3)
+        assert not bp.status.any()
+        # the raw call on the same handle
+        ctx, ev = bp.ctx, bp._ev
+        ev._pack(fitted)
+        mm = np.full(2, m, np.int64)
+        t = np.ascontiguousarray(np.concatenate([t_gene, t_gene]))
+        dadd = np.asarray([f.obs_stddev ** 2 for f in fitted], np.float64)
+        cadd = np.asarray([f.jitter for f in fitted], np.float64)
+        ysp = np.concatenate(ys)
+        seeds = np.asarray([42, 43], np.uint64)
+        logp, mean, out = np.empty(2), np.empty(2 * m), np.empty(5 * 2 * m)
+        rc = ctx.lib.lfm_mbatch_predictive_f64(
+            ctx.handle, ev.batch, _lib.dptr(ev._buf), _lib.dptr(bp.variances), _lib.dptr(dadd),
+            _lib.dptr(mm), _lib.dptr(t), _lib.dptr(cadd), _lib.dptr(ysp), _lib.dptr(logp),
+            _lib.dptr(seeds), 3, 5, _lib.dptr(mean), _lib.dptr(out), None)
+        assert rc == 0
+        np.testing.assert_array_equal(lp, logp)
+        for q in range(2):
+            np.testing.assert_array_equal(drawn[q][0], mean[q * m:(q + 1) * m])
+            np.testing.assert_array_equal(drawn[q][1],
+                                          out[5 * q * m:5 * (q + 1) * m].reshape(5, m))
+            np.testing.assert_array_equal(drawn[q][0], np.asarray(dists[q].loc))
+            scale = np.asarray(dists[q].scale)
+            ref = dists[q].log_prob(ys[q])
+            bound = DI.bound_factor(scale) * max(1.0, abs(ref))
+            print(f"problem {q}: log_prob {lp[q]:.6f} vs multi_gene_predict().log_prob "
+                  f"|d| = {abs(lp[q] - ref):.2e}, bound {bound:.2e}")
+            assert abs(lp[q] - ref) <= bound
+        # seeds= overrides seed
+        again = bp.sample(fitted, t_gene, 5, 0, sample0=3, seeds=[42, 43])
+        for a, d in zip(again, drawn):
+            np.testing.assert_array_equal(a[1], d[1])
+    finally:
+        if bp is not None:
+            bp.close()
+        bt.close()

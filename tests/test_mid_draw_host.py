@@ -1,0 +1,171 @@
+"""CPU checks of the mid-size batch's predictive call (lfm_mbatch_predictive_f64,
+predict.MidBatchPredictor.sample / .log_prob): the launch plan under AddressSanitizer + UBSan
+(tests/native/mid_draw_plan_check.cpp, a stand-alone program built here exactly as
+tests/test_sample_host.py builds sample_plan_check.cpp), the entry point in the header, the
+ctypes table and the library, the calls that need no GPU, the shim's argument checks, the
+conditioning of the GPU tests' inputs, and the strict build."""
+
+import os
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+
+from tests import mid_draw_inputs as DI
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+NEW = "lfm_mbatch_predictive_f64"
+
+
+@pytest.mark.skipif(shutil.which("g++") is None, reason="needs g++ with libasan")
+def test_plan_mid_draw_under_asan_and_ubsan(tmp_path):
+    exe = str(tmp_path / "mid_draw_plan_check")
+    san = ["-fsanitize=address,undefined", "-fno-omit-frame-pointer",
+           "-fno-sanitize-recover=undefined"]
+    r = subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-Wall", *san, "-pthread",
+                        os.path.join(ROOT, "tests", "native", "mid_draw_plan_check.cpp"),
+                        os.path.join(ROOT, "dis_project_amd", "csrc", "lfm_host.cpp"),
+                        "-o", exe], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=1",
+               UBSAN_OPTIONS="print_stacktrace=1")
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=600, env=env)
+    assert r.returncode == 0, (r.stdout[-3000:], r.stderr[-3000:])
+    assert "mid_draw_plan_check: all passed" in r.stdout
+    assert "ERROR: AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr
+
+
+def test_header_and_signatures_carry_the_entry_point():
+    from dis_project_amd import _lib
+    from tests.test_abi import header_functions
+
+    declared = header_functions()
+    bound = {name: args for name, _, args in _lib.PRODUCT_SIGNATURES}
+    assert set(bound) == set(declared)
+    assert NEW in declared and NEW in bound
+    assert len(bound[NEW]) == 16
+    lib = _lib.load_library()
+    assert lib.lfm_abi_version() == 5
+    assert hasattr(lib, NEW)
+    # no profiling class was added
+    assert len(_lib.KCLASSES) + len(_lib.SAMPLE_KCLASSES) == 24
+
+
+def test_null_context_is_rejected_without_a_gpu():
+    from dis_project_amd import _lib
+
+    lib = _lib.load_library()
+    out = np.full(4, 7.0)
+    p = out.ctypes.data
+    assert lib.lfm_mbatch_predictive_f64(None, None, p, p, p, p, p, p, p, p, p, 0, 1, p, p,
+                                         None) == _lib.LFM_E_ARG
+    assert np.all(out == 7.0)
+
+
+class _Model:
+    def __init__(self, G=5):
+        self.num_genes, self.jitter, self.obs_stddev = G, 1e-4, 0.7
+
+
+def _predictor(P=2):
+    """A MidBatchPredictor that was never given a device: any device call would fail on the
+    evaluator that is not there."""
+    import dis_project_amd as lfm
+
+    bp = object.__new__(lfm.MidBatchPredictor)
+    bp._ev = type("NoDevice", (), {"datasets": [None] * P})()
+    bp.ctx, bp._own = None, False
+    bp.status = np.zeros(P, np.int32)
+    return bp
+
+
+def test_shim_argument_errors_need_no_gpu():
+    bp = _predictor(2)
+    models = [_Model(), _Model()]
+    t = np.ones((10, 3))
+    y = [np.zeros(10), np.zeros(10)]
+    with pytest.raises(ValueError, match="one model"):
+        bp.sample(models[:1], t, 2, 1)
+    with pytest.raises(ValueError, match="num_samples"):
+        bp.sample(models, t, 0, 1)
+    with pytest.raises(ValueError, match="65536"):
+        bp.sample(models, t, 65537, 1)
+    with pytest.raises(ValueError, match="sample0"):
+        bp.sample(models, t, 2, 1, sample0=-1)
+    with pytest.raises(ValueError, match="pair"):
+        bp.sample(models, t, 2, [1, 2, 3])
+    with pytest.raises(ValueError, match="kind"):
+        bp.sample(models, t, 2, 1, kind="both")
+    with pytest.raises(ValueError, match="seeds"):
+        bp.sample(models, t, 2, 1, seeds=[1, 2, 3])
+    with pytest.raises(ValueError, match="multiple"):
+        bp.sample(models, np.ones((7, 3)), 2, 1)
+    with pytest.raises(ValueError, match=r"\[m, 3\]"):
+        bp.log_prob(models, np.ones((10, 2)), y)
+    with pytest.raises(ValueError, match="1024"):
+        bp.log_prob(models, np.ones((1025, 3)), [np.zeros(1025)] * 2)
+    with pytest.raises(ValueError, match="cov_add"):
+        bp.log_prob(models, t, y, cov_add=[1e-4, 1e-4, 1e-4])
+    with pytest.raises(ValueError, match="y_star"):
+        bp.log_prob(models, t, None)
+    with pytest.raises(ValueError, match="y_star"):
+        bp.log_prob(models, t, y[:1])
+    with pytest.raises(ValueError, match="y_star"):
+        bp.log_prob(models, t, [np.zeros(10), np.zeros(9)])
+    with pytest.raises(ValueError, match="kind"):
+        bp.log_prob(models, t, y, kind="x")
+    # valid arguments get as far as the device, which this predictor does not have
+    with pytest.raises(AttributeError):
+        bp.log_prob(models, t, y)
+
+
+@pytest.mark.parametrize("shape", DI.EDGE)
+def test_the_edge_inputs_are_well_conditioned(shape):
+    """The gene-row covariances are PSD to rounding (smallest eigenvalue within 1.1e-11 of 0), so
+    cov + 1e-4 I has kappa of about 1.5e4 to 1.4e5 (asserted: within [1e4, 2e5], where the GPU
+    tests' bound 50 kappa m eps stays below 3e-6) and cov + 0.49 I kappa <= 30: no case of
+    tests/test_gpu_mid_draw.py is vacuous or skipped."""
+    from oracle import lfm_oracle as O
+
+    p = DI.problem(*shape)
+    _, cov = O.multi_gene_predict(p["x"], p["y"], p["v"], p["t"], p["D"], p["S"], p["B"], DI.L,
+                                  DI.OBS, 0.0)
+    w = np.linalg.eigvalsh(0.5 * (cov + cov.T))
+    assert abs(w[0]) <= 1.1e-11 or w[0] > 0
+    k4, k49 = (w[-1] + 1e-4) / (w[0] + 1e-4), (w[-1] + 0.49) / (w[0] + 0.49)
+    print(f"{shape}: min eig {w[0]:.2e}, kappa {k4:.3g} / {k49:.3g}")
+    assert 1e4 <= k4 <= 2e5 and k49 <= 30
+
+
+def test_the_latent_rows_are_the_not_pd_case():
+    from oracle import lfm_oracle as O
+
+    p = DI.problem(*DI.LATENT, flag=0.0)
+    assert np.all(p["t"][:, 2] == 0)
+    _, cov = O.multi_gene_predict(p["x"], p["y"], p["v"], p["t"], p["D"], p["S"], p["B"], DI.L,
+                                  DI.OBS, 0.0)
+    w = np.linalg.eigvalsh(0.5 * (cov + cov.T))
+    print(f"latent rows: smallest eigenvalue {w[0]:.3f}")
+    assert -0.49 < w[0] < -1e-4  # not PD at cov_add = 1e-4, definite at 0.49
+
+
+def test_reference_helpers():
+    rng = np.random.default_rng(5)
+    a = rng.standard_normal((6, 6))
+    c = a @ a.T + np.eye(6)
+    mean, y = rng.standard_normal(6), rng.standard_normal(6)
+    ref = -0.5 * (6 * np.log(2 * np.pi) + np.linalg.slogdet(c)[1]
+                  + (y - mean) @ np.linalg.solve(c, y - mean))
+    assert abs(DI.chol_log_prob(y, mean, c) - ref) <= 1e-12 * abs(ref)
+    w = np.linalg.eigvalsh(c)
+    assert DI.bound_factor(c) == 50.0 * (w[-1] / w[0]) * 6 * 2.0 ** -52
+
+
+@pytest.mark.skipif(not os.path.exists("/opt/rocm/bin/hipcc"), reason="needs hipcc")
+def test_strict_build():
+    """Every unit, lfm_mid.hip's new kernels included, with warnings as errors."""
+    r = subprocess.run(["make", "-s", "-C", os.path.join(ROOT, "dis_project_amd", "csrc"),
+                        "-j", str(min(16, os.cpu_count() or 4)), "strict"],
+                       capture_output=True, text=True, timeout=1800)
+    assert r.returncode == 0, (r.stdout[-3000:], r.stderr[-3000:])
