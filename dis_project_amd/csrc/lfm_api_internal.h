@@ -1,5 +1,5 @@
 // lfm_api_internal.h — what the units of the extern "C" boundary share (lfm_ctx.hip, lfm_api.hip,
-// lfm_batch.hip, lfm_farm.hip). The kernel units see lfm_internal.h only.
+// lfm_batch.hip, lfm_mbatch.hip, lfm_farm.hip). The kernel units see lfm_internal.h only.
 #pragma once
 
 #include <algorithm>

@@ -606,9 +606,35 @@ SamplePlan plan_sample(int64_t n, int64_t nsamp, int64_t sample0) {
   return P;
 }
 
-// ------------------------------------------------- mid-size resident batch (lfm_mid.hip)
+// ------------------- mid-size resident batch (lfm_mbatch.hip; its kernels: lfm_mid.hip)
 namespace {
+// a region's size rounded up to 16 bytes: in doubles, and in bytes
 int64_t even(int64_t d) { return (d + 1) / 2 * 2; }
+size_t up16(size_t b) { return (b + 15) / 16 * 16; }
+
+// The factorisation's launches: one per block column k of the largest problem, its units the row
+// blocks from k on.
+void push_columns(std::vector<MidLaunch>& v, unsigned gx, int maxnb) {
+  for (int k = 0; k < maxnb; ++k) v.push_back({MID_COLUMN, k, gx, (unsigned)(maxnb - k)});
+}
+
+// The sizes of a table entry for an n x n problem and, from `at`, the regions the factorisation
+// works in: the augmented matrix S, the factor L, W behind it if the entry has one, and the
+// inverses of the factor's diagonal blocks. Returns the first double past them.
+int64_t factor_regions(MidProb& m, int64_t n, int64_t at, bool has_W) {
+  m.n = (int)n;
+  m.nb = mid_blocks(m.n);
+  m.Mp = m.nb * MID_TILE;
+  const int64_t mat = (int64_t)m.Mp * m.Mp;
+  m.S = at;
+  m.L = m.S + mat;
+  m.dinv = m.L + mat;
+  if (has_W) {
+    m.W = m.dinv;
+    m.dinv = m.W + mat;
+  }
+  return m.dinv + (int64_t)m.nb * MID_TILE * MID_TILE;
+}
 }  // namespace
 
 int64_t mid_problem_doubles(int64_t n) {
@@ -649,22 +675,14 @@ MidPlan plan_mid(const std::vector<MidShape>& shapes) {
   P.probs.reserve(shapes.size());
   for (const MidShape& s : shapes) {
     MidProb m{};
-    m.n = (int)s.n;
     m.G = (int)s.G;
-    m.nb = mid_blocks(m.n);
-    m.Mp = m.nb * MID_TILE;
     m.hv = hv;
     m.hs = hs;
     hv += 3 * s.G;
     hs += 3;
-    const int64_t mat = (int64_t)m.Mp * m.Mp;
     m.x = at;
     m.y = m.x + even(3 * s.n);
-    m.S = m.y + even(s.n);
-    m.L = m.S + mat;
-    m.W = m.L + mat;
-    m.dinv = m.W + mat;
-    m.part = m.dinv + (int64_t)m.nb * MID_TILE * MID_TILE;
+    m.part = factor_regions(m, s.n, m.y + even(s.n), true);
     at = m.part + even((int64_t)mid_tiles(m.nb) * MID_PART);
     P.maxnb = std::max(P.maxnb, m.nb);
     P.probs.push_back(m);
@@ -672,12 +690,12 @@ MidPlan plan_mid(const std::vector<MidShape>& shapes) {
   P.maxtiles = mid_tiles(P.maxnb);
   P.doubles = at;
   P.status = (size_t)at * sizeof(double);
-  P.table = P.status + ((size_t)P.nprob * sizeof(int) + 15) / 16 * 16;
+  P.table = P.status + up16((size_t)P.nprob * sizeof(int));
   P.bytes = P.table + (size_t)P.nprob * sizeof(MidProb);
   // the launches: their count depends on the largest problem alone
   const unsigned gx = (unsigned)P.nprob;
   P.value.push_back({MID_FILL, 0, gx, (unsigned)P.maxtiles});
-  for (int k = 0; k < P.maxnb; ++k) P.value.push_back({MID_COLUMN, k, gx, (unsigned)(P.maxnb - k)});
+  push_columns(P.value, gx, P.maxnb);
   P.value.push_back({MID_VALUE, 0, gx, 1u});
   P.value_grad = P.value;  // the same launches first: the same value bits
   P.value_grad.push_back({MID_INVERT, 0, gx, (unsigned)P.maxnb});
@@ -764,8 +782,7 @@ MidPostPlan plan_mid_post(const std::vector<MidShape>& shapes, const int64_t* m,
   P.bytes = P.table + (size_t)P.nprob * sizeof(MidPostProb);
   const unsigned gx = (unsigned)P.nprob;
   P.launches.push_back({MID_POST_FILL, 0, gx, (unsigned)(P.maxtiles + P.maxunits)});
-  for (int k = 0; k < P.maxnb; ++k)
-    P.launches.push_back({MID_COLUMN, k, gx, (unsigned)(P.maxnb - k)});
+  push_columns(P.launches, gx, P.maxnb);
   P.launches.push_back({MID_SOLVE, 0, gx, (unsigned)P.maxmb});
   if (want_cov) P.launches.push_back({MID_COV, 0, gx, (unsigned)P.maxcov});
   return P;
@@ -796,7 +813,7 @@ MidFitPlan plan_mid_fit(const std::vector<MidShape>& shapes, int64_t nsteps) {
   F.hist = F.bias + 2 * nsteps;
   F.doubles = F.hist + even(nsteps * F.nprob);
   F.first_bad = (size_t)F.doubles * sizeof(double);
-  F.bytes = F.first_bad + ((size_t)F.nprob * sizeof(int) + 15) / 16 * 16;
+  F.bytes = F.first_bad + up16((size_t)F.nprob * sizeof(int));
   const unsigned gx = (unsigned)F.nprob;
   F.per_step = P.value_grad.size() + 1;
   F.launches.reserve(1 + (size_t)nsteps * F.per_step);
@@ -870,15 +887,8 @@ MidDrawPlan plan_mid_draw(const std::vector<MidShape>& shapes, const int64_t* m,
   int64_t om = 0, oc = 0;
   for (size_t q = 0; q < shapes.size(); ++q) {
     MidProb e{};
-    e.n = (int)m[q];
     e.G = (int)shapes[q].G;
-    e.nb = mid_blocks(e.n);
-    e.Mp = e.nb * MID_TILE;
-    const int64_t mat = (int64_t)e.Mp * e.Mp;
-    e.S = at;
-    e.L = e.S + mat;
-    e.dinv = e.L + mat;
-    at = e.dinv + (int64_t)e.nb * MID_TILE * MID_TILE;
+    at = factor_regions(e, m[q], at, false);
     MidDrawProb d{};
     d.m = e.n;
     d.cb = (e.n + MID_TILE - 1) / MID_TILE;
@@ -908,15 +918,13 @@ MidDrawPlan plan_mid_draw(const std::vector<MidShape>& shapes, const int64_t* m,
   P.maxsb = (int)sb;
   P.maxtiles = mid_tiles(P.maxnq);
   P.doubles = at;
-  auto up16 = [](size_t b) { return (b + 15) / 16 * 16; };
   P.seeds = (size_t)at * sizeof(double);
   P.table = P.seeds + up16((size_t)P.nprob * sizeof(uint64_t));
   P.dtable = P.table + up16((size_t)P.nprob * sizeof(MidProb));
   P.bytes = P.dtable + (size_t)P.nprob * sizeof(MidDrawProb);
   const unsigned gx = (unsigned)P.nprob;
   P.launches.push_back({MID_DRAW_SCALE, 0, gx, (unsigned)P.maxtiles});
-  for (int k = 0; k < P.maxnq; ++k)
-    P.launches.push_back({MID_COLUMN, k, gx, (unsigned)(P.maxnq - k)});
+  push_columns(P.launches, gx, P.maxnq);
   if (has_ystar) P.launches.push_back({MID_VALUE, 0, gx, 1u});
   if (nsamp > 0) {
     // 64 sb x 64 cb / 2 pairs of the largest problem, 256 a workgroup

@@ -6,7 +6,7 @@
 // launch plans (plan_small_*, which lfm_small.hip and lfm_batch.hip only read); and the resident
 // posterior's predict plan (plan_post, which lfm_post.hip only reads); with lfm_mid_plan.h the
 // mid-size resident batch's arenas and launch plans (plan_mid, plan_mid_post, plan_mid_fit,
-// plan_mid_draw, which lfm_mid.hip only reads); and
+// plan_mid_draw, which lfm_mbatch.hip and lfm_mid.hip only read); and
 // the joint samples' generator and launch plan (plan_sample, which lfm_sample.hip only reads).
 // Plain C++ (no HIP types), so lfm_host.cpp also builds into the host sanitizer check
 // (tests/native, `make -C tests/native asan`) with g++ -fsanitize=address,undefined.

@@ -393,6 +393,64 @@ struct SmallPostLaunch {
 };
 int launch_small_post(lfm_ctx* ctx, const SmallPostLaunch& f, size_t lds);
 
+// The mid-size resident batch (lfm_mid.hip: the kernels and launch_mid; lfm_mbatch.hip: the handle
+// and its calls). The kernels' argument structs, filled from the plans of lfm_mid_plan.h.
+struct MidArgs {
+  const MidProb* probs;
+  double* base;  // the arena; the packed hyperparameters at its start
+  int* status;   // [nprob]: 0, or 1 + the first failing pivot
+  int64_t out, grad;
+  int negative, k;
+};
+// The posterior call's second arena and table; `none` for the MLL's fill.
+struct MidPostArgs {
+  const MidPostProb* pp;
+  double* base;
+  int64_t dadd;  // diag_add [nprob], doubles from base
+  int maxtiles;  // units of the fill launch before the first T unit
+};
+struct MidNoPost {};
+// The fit call's third arena (plan_mid_fit) and optimiser; s: the step of this call, or -1 for
+// the constrain before step 0.
+struct MidFitArgs {
+  double* base;
+  int64_t raw, mu, nu, bias, hist;  // doubles from base
+  int* first_bad;                   // [nprob]: 1 + the first step whose factor failed, or 0
+  double lr, b1, b2, eps, eps_root;
+  int64_t step0, spe, s;
+  int nprob, fix;
+};
+// The predictive call's fourth arena (plan_mid_draw) and its table. The launches on it take a
+// MidArgs whose table is the second one (n = m_p, offsets into this arena) and whose status words
+// are the first arena's: a problem whose S failed is skipped, one whose covariance fails is
+// marked there.
+struct MidDrawArgs {
+  const MidDrawProb* dp;
+  double* base;           // the fourth arena
+  const double* mean;     // the posterior call's packed mean ...
+  const double* cov;      // ... and covariance, in its arena
+  const uint64_t* seeds;  // [nprob]
+  int64_t cadd;           // cov_add [nprob], doubles from base
+  int64_t nsamp;
+  uint64_t sample0;
+  int maxcb;
+  double flops;           // host side: the product's nsamp sum m^2, for the profile
+};
+// One call's arguments, filled once: `a` always, and of q / f / d those that `has` names
+// (MID_HAS_*). launch_mid refuses a launch whose kernel takes a block the call has not filled.
+enum : unsigned { MID_HAS_POST = 1, MID_HAS_FIT = 2, MID_HAS_DRAW = 4 };
+struct MidCall {
+  MidArgs a;
+  MidPostArgs q;
+  MidFitArgs f;
+  MidDrawArgs d;
+  MidNoPost none;
+  unsigned has;
+};
+// One launch of a plan's list on ctx->stream. The launch's own fields are set in the block here:
+// a.k = l.k, and f.s = l.k for MID_ADAM, -1 for MID_CONSTRAIN.
+int launch_mid(lfm_ctx* ctx, const MidLaunch& l, MidCall& c);
+
 // Path of the advisory lock file behind schedule 3's cross-process tenancy (lfm_ctx.hip;
 // empty if the device has no PCI bus id)
 std::string tenancy_lock_path(int dev);

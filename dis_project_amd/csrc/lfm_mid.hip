@@ -52,33 +52,16 @@
 //                      64 (tj + 1) over the factor's lower tiles (fp64 MFMA).
 // No atomics and no device-side waits: consecutive launches on one stream are the only ordering,
 // so a problem's bits depend on its own data and hyperparameters alone.
-#include <cstring>
-#include <memory>
+//
+// This unit holds the kernels and launch_mid, which issues one launch of a plan's list; their
+// argument structs are in lfm_internal.h. The handle, the calls and the entry points:
+// lfm_mbatch.hip.
 #include <type_traits>
 
-#include "lfm_api_internal.h"
+#include "lfm_internal.h"
 #include "lfm_bijectors.h"
 #include "lfm_chol_dev.h"
 #include "lfm_dual.h"
-
-using namespace lfm;
-
-// The handle: the plan, the device arena it lays out, and a pinned buffer for a call's packed
-// hyperparameters and results (hyp | out | grad | status words).
-struct lfm_mbatch {
-  int device = 0;
-  MidPlan plan;
-  std::vector<lfm::MidShape> shapes;
-  char* dmem = nullptr;
-  char* pmem = nullptr;  // the posterior calls' arena (plan_mid_post), grown on demand
-  size_t pbytes = 0;
-  char* fmem = nullptr;  // the fit calls' arena (plan_mid_fit), grown on demand
-  size_t fbytes = 0;
-  char* qmem = nullptr;  // the predictive calls' arena (plan_mid_draw), grown on demand
-  size_t qbytes = 0;
-  double* hbuf = nullptr;
-  size_t h_out = 0, h_grad = 0, h_status = 0;  // doubles into hbuf
-};
 
 namespace lfm {
 
@@ -87,14 +70,6 @@ namespace {
 constexpr int TS = MID_TILE, LD = TS + LDP;
 typedef double (*Tile)[LD];
 constexpr size_t MID_LDS = (3 * (size_t)TS * LD + 2 * TS) * sizeof(double);
-
-struct MidArgs {
-  const MidProb* probs;
-  double* base;  // the arena; the packed hyperparameters at its start
-  int* status;   // [nprob]: 0, or 1 + the first failing pivot
-  int64_t out, grad;
-  int negative, k;
-};
 
 // A 64 x 64 tile at g (row stride ld) into LDS, as it is or transposed; rows >= rows read as 0.
 __device__ __forceinline__ void stage(Tile s, const double* __restrict__ g, int64_t ld, bool tr,
@@ -134,15 +109,6 @@ __device__ __forceinline__ void acc_each(double4v (&acc)[4], F f) {
 #pragma unroll
     for (int q = 0; q < 4; ++q) f(16 * w + lk + 4 * q, 16 * jr + li, acc[jr][q]);
 }
-
-// The posterior call's second arena and table; `none` for the MLL's fill.
-struct MidPostArgs {
-  const MidPostProb* pp;
-  double* base;
-  int64_t dadd;  // diag_add [nprob], doubles from base
-  int maxtiles;  // units of the fill launch before the first T unit
-};
-struct MidNoPost {};
 
 __device__ __forceinline__ HypDev mid_hyp(const MidProb& P, const double* hyp) {
   const double* v = hyp + P.hv;
@@ -700,22 +666,8 @@ __global__ __launch_bounds__(256) void mid_cov_kernel(MidArgs a, MidPostArgs q) 
 }
 
 // ------------------------------------------------------------------ the predictive distribution
-// The predictive call's fourth arena (plan_mid_draw) and its table. The launches on it take a
-// MidArgs whose table is the second one (n = m_p, offsets into this arena) and whose status words
-// are the first arena's: a problem whose S failed is skipped, one whose covariance fails is
-// marked there.
-struct MidDrawArgs {
-  const MidDrawProb* dp;
-  double* base;           // the fourth arena
-  const double* mean;     // the posterior call's packed mean ...
-  const double* cov;      // ... and covariance, in its arena
-  const uint64_t* seeds;  // [nprob]
-  int64_t cadd;           // cov_add [nprob], doubles from base
-  int64_t nsamp;
-  uint64_t sample0;
-  int maxcb;
-  double flops;           // host side: the product's nsamp sum m^2, for the profile
-};
+// The launches on the predictive call's fourth arena (MidDrawArgs) take a MidArgs whose table is
+// the second one (n = m_p) and whose status words are the first arena's.
 
 // Lower tile (I, J) of the covariance's augmented matrix, in mid_fill_kernel's layout: the lower
 // triangle of cov_p with cov_add[p] joining the diagonal in one addition, row m the residual
@@ -813,17 +765,6 @@ __global__ __launch_bounds__(256) void mid_draw_product_kernel(MidArgs a, MidDra
 }
 
 // ------------------------------------------------------------------ the fit's update
-// The fit call's third arena (plan_mid_fit) and optimiser; s: the step of this call, or -1 for
-// the constrain before step 0.
-struct MidFitArgs {
-  double* base;
-  int64_t raw, mu, nu, bias, hist;  // doubles from base
-  int* first_bad;                   // [nprob]: 1 + the first step whose factor failed, or 0
-  double lr, b1, b2, eps, eps_root;
-  int64_t step0, spe, s;
-  int nprob, fix;
-};
-
 // JaxTrainer.step's tail (trainer.py:105-132) and after_epoch (trainer.py:133-160, 205-210) of
 // every problem after step s's value-and-gradient launches, as small_fit_kernel's update in the
 // same arithmetic order: history[s] = the value; the first-bad-step word latched from the
@@ -884,554 +825,80 @@ __global__ __launch_bounds__(256) void mid_adam_kernel(MidArgs a, MidFitArgs f) 
   }
 }
 
-int launch_mid(lfm_ctx* ctx, const MidLaunch& l, MidArgs a, const MidPostArgs* q = nullptr,
-               const MidFitArgs* f = nullptr, const MidDrawArgs* d = nullptr) {
-  static const bool attrs = [] {
-    for (const void* f : {reinterpret_cast<const void*>(&mid_column_kernel),
-                          reinterpret_cast<const void*>(&mid_invert_kernel),
-                          reinterpret_cast<const void*>(&mid_sinv_kernel),
-                          reinterpret_cast<const void*>(&mid_solve_kernel),
-                          reinterpret_cast<const void*>(&mid_cov_kernel)})
-      hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)MID_LDS);
-    hipFuncSetAttribute(reinterpret_cast<const void*>(&mid_draw_product_kernel),
-                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)MID_DRAW_LDS);
-    return true;
-  }();
-  (void)attrs;
-  a.k = l.k;
-  const dim3 grid(l.gx, l.gy), block(256);
-  hipEvent_t ev;
-  const char* what = "";
-  switch (l.kind) {
-    case MID_FILL:
-      prof_begin(ctx, K_MID_FILL, &ev);
-      hipLaunchKernelGGL(mid_fill_kernel<false>, grid, block, 0, ctx->stream, a, MidNoPost{});
-      prof_end(ctx, K_MID_FILL, ev, 0, 0);
-      what = "mid_fill_kernel";
-      break;
-    case MID_COLUMN:
-      prof_begin(ctx, K_MID_COLUMN, &ev);
-      hipLaunchKernelGGL(mid_column_kernel, grid, block, MID_LDS, ctx->stream, a);
-      prof_end(ctx, K_MID_COLUMN, ev, 0, 0);
-      what = "mid_column_kernel";
-      break;
-    case MID_VALUE:
-      prof_begin(ctx, K_MID_FINISH, &ev);
-      hipLaunchKernelGGL(mid_value_kernel, grid, block, 0, ctx->stream, a);
-      prof_end(ctx, K_MID_FINISH, ev, 0, 0);
-      what = "mid_value_kernel";
-      break;
-    case MID_INVERT:
-      prof_begin(ctx, K_MID_INVERSE, &ev);
-      hipLaunchKernelGGL(mid_invert_kernel, grid, block, MID_LDS, ctx->stream, a);
-      prof_end(ctx, K_MID_INVERSE, ev, 0, 0);
-      what = "mid_invert_kernel";
-      break;
-    case MID_SINV:
-      prof_begin(ctx, K_MID_INVERSE, &ev);
-      hipLaunchKernelGGL(mid_sinv_kernel, grid, block, MID_LDS, ctx->stream, a);
-      prof_end(ctx, K_MID_INVERSE, ev, 0, 0);
-      what = "mid_sinv_kernel";
-      break;
-    case MID_PAIRS:
-      prof_begin(ctx, K_MID_PAIRS, &ev);
-      hipLaunchKernelGGL(mid_pairs_kernel, grid, block, 0, ctx->stream, a);
-      prof_end(ctx, K_MID_PAIRS, ev, 0, 0);
-      what = "mid_pairs_kernel";
-      break;
-    case MID_GRAD:
-      prof_begin(ctx, K_MID_FINISH, &ev);
-      hipLaunchKernelGGL(mid_grad_kernel, grid, block, 0, ctx->stream, a);
-      prof_end(ctx, K_MID_FINISH, ev, 0, 0);
-      what = "mid_grad_kernel";
-      break;
-    case MID_POST_FILL:
-      prof_begin(ctx, K_MID_FILL, &ev);
-      hipLaunchKernelGGL(mid_fill_kernel<true>, grid, block, 0, ctx->stream, a, *q);
-      prof_end(ctx, K_MID_FILL, ev, 0, 0);
-      what = "mid_fill_kernel (posterior)";
-      break;
-    case MID_SOLVE:
-      prof_begin(ctx, K_MID_INVERSE, &ev);
-      hipLaunchKernelGGL(mid_solve_kernel, grid, block, MID_LDS, ctx->stream, a, *q);
-      prof_end(ctx, K_MID_INVERSE, ev, 0, 0);
-      what = "mid_solve_kernel";
-      break;
-    case MID_COV:
-      prof_begin(ctx, K_MID_FINISH, &ev);
-      hipLaunchKernelGGL(mid_cov_kernel, grid, block, MID_LDS, ctx->stream, a, *q);
-      prof_end(ctx, K_MID_FINISH, ev, 0, 0);
-      what = "mid_cov_kernel";
-      break;
-    case MID_CONSTRAIN:
-    case MID_ADAM: {
-      MidFitArgs fa = *f;
-      fa.s = l.kind == MID_ADAM ? l.k : -1;
-      prof_begin(ctx, K_MID_FINISH, &ev);
-      hipLaunchKernelGGL(mid_adam_kernel, grid, block, 0, ctx->stream, a, fa);
-      prof_end(ctx, K_MID_FINISH, ev, 0, 0);
-      what = "mid_adam_kernel";
-      break;
-    }
-    case MID_DRAW_SCALE:
-      prof_begin(ctx, K_MID_FILL, &ev);
-      hipLaunchKernelGGL(mid_draw_scale_kernel, grid, block, 0, ctx->stream, a, *d);
-      prof_end(ctx, K_MID_FILL, ev, 0, 0);
-      what = "mid_draw_scale_kernel";
-      break;
-    case MID_DRAW_RANDN:
-      prof_begin(ctx, K_SAMPLE_RANDN, &ev);
-      hipLaunchKernelGGL(mid_draw_randn_kernel, grid, block, 0, ctx->stream, a, *d);
-      prof_end(ctx, K_SAMPLE_RANDN, ev, 0, 0);
-      what = "mid_draw_randn_kernel";
-      break;
-    case MID_DRAW_PRODUCT:
-      prof_begin(ctx, K_SAMPLE_TRMM, &ev);
-      hipLaunchKernelGGL(mid_draw_product_kernel, grid, block, MID_DRAW_LDS, ctx->stream, a, *d);
-      prof_end(ctx, K_SAMPLE_TRMM, ev, d->flops, 0);
-      what = "mid_draw_product_kernel";
-      break;
-    default:
-      return set_err(ctx, LFM_E_STATE, "plan_mid: unknown launch kind");
-  }
-  return hip_fail(ctx, hipGetLastError(), what);
+// ------------------------------------------------------------------ the launcher
+// One row per MidKind: the profile class, the dynamic LDS (the size of the launch and of the
+// kernel's raised limit), the name in an error message, the blocks of MidCall the kernel takes
+// besides `a`, the kernel (for its attribute) and its launch.
+struct MidRow {
+  int cls;
+  size_t lds;
+  const char* name;
+  unsigned needs;
+  const void* kernel;
+  void (*issue)(const MidCall& c, dim3 grid, size_t lds, hipStream_t st);
+};
+
+constexpr unsigned mid_need(MidNoPost MidCall::*) { return 0; }
+constexpr unsigned mid_need(MidPostArgs MidCall::*) { return MID_HAS_POST; }
+constexpr unsigned mid_need(MidFitArgs MidCall::*) { return MID_HAS_FIT; }
+constexpr unsigned mid_need(MidDrawArgs MidCall::*) { return MID_HAS_DRAW; }
+
+template <auto Kernel, auto... Block>
+void mid_issue(const MidCall& c, dim3 grid, size_t lds, hipStream_t st) {
+  hipLaunchKernelGGL(Kernel, grid, dim3(256), lds, st, c.a, c.*Block...);
+}
+// The row of a kernel launched as Kernel(c.a, c.*Block...): what it needs follows from Block.
+template <auto Kernel, auto... Block>
+MidRow mid_row(int cls, size_t lds, const char* name) {
+  return {cls, lds, name, (0u | ... | mid_need(Block)), reinterpret_cast<const void*>(Kernel),
+          &mid_issue<Kernel, Block...>};
 }
 
-// One call: the hyperparameters up, the plan's launches, the results and status words down.
-int mid_call(lfm_ctx* ctx, lfm_mbatch* b, const double* hyp, int negative, bool want_grad,
-             double* value, double* grad, int* status) {
-  DeviceGuard g(ctx->device);
-  DeviceTenancy tenancy(ctx, false);  // shared
-  const MidPlan& P = b->plan;
-  const int64_t np = P.nprob, nh = P.nhyp;
-  double* base = reinterpret_cast<double*>(b->dmem);
-  std::memcpy(b->hbuf, hyp, (size_t)nh * 8);
-  hipError_t e = hipMemcpyAsync(base + P.hyp, b->hbuf, (size_t)nh * 8, hipMemcpyHostToDevice,
-                                ctx->stream);
-  if (e != hipSuccess) return hip_fail(ctx, e, "lfm_mbatch: upload");
-  MidArgs a{};
-  a.probs = reinterpret_cast<const MidProb*>(b->dmem + P.table);
-  a.base = base;
-  a.status = reinterpret_cast<int*>(b->dmem + P.status);
-  a.out = P.out;
-  a.grad = P.grad;
-  a.negative = negative;
-  for (const MidLaunch& l : want_grad ? P.value_grad : P.value)
-    if (int r = launch_mid(ctx, l, a)) return r;
-  int* hst = reinterpret_cast<int*>(b->hbuf + b->h_status);
-  e = hipMemcpyAsync(b->hbuf + b->h_out, base + P.out, (size_t)np * 8, hipMemcpyDeviceToHost,
-                     ctx->stream);
-  if (e == hipSuccess && want_grad)
-    e = hipMemcpyAsync(b->hbuf + b->h_grad, base + P.grad, (size_t)nh * 8, hipMemcpyDeviceToHost,
-                       ctx->stream);
-  if (e == hipSuccess)
-    e = hipMemcpyAsync(hst, a.status, (size_t)np * sizeof(int), hipMemcpyDeviceToHost, ctx->stream);
-  if (e != hipSuccess) return hip_fail(ctx, e, "lfm_mbatch: download");
-  if (int r = finish(ctx)) return r;
-  std::memcpy(value, b->hbuf + b->h_out, (size_t)np * 8);
-  if (want_grad) std::memcpy(grad, b->hbuf + b->h_grad, (size_t)nh * 8);
-  return batch_status(ctx, hst, np, status);
-}
-
-// One posterior call: the hyperparameters into the first arena, the diagonal and the test inputs
-// into the second (grown here when this call needs more), the plan's launches, the outputs down.
-// mid_post_enqueue is the first half, which the predictive call shares: the uploads and the
-// launches. `who` names the entry point in a message.
-int mid_post_enqueue(lfm_ctx* ctx, lfm_mbatch* b, const MidPostPlan& Q, const double* hyp,
-                     const double* diag_vec, const double* diag_add, const double* t,
-                     const std::string& who) {
-  const MidPlan& P = b->plan;
-  const int64_t np = P.nprob, nh = P.nhyp;
-  if (b->pbytes < Q.bytes) {
-    // every call on the handle is synchronous: nothing of the old arena is in flight
-    if (b->pmem) hipFree(b->pmem);
-    b->pmem = nullptr;
-    b->pbytes = 0;
-    const hipError_t e = hipMalloc((void**)&b->pmem, Q.bytes);
-    if (e != hipSuccess) {
-      b->pmem = nullptr;
-      (void)hipGetLastError();
-      return set_err(ctx, LFM_E_OOM, who + ": " + std::to_string(Q.bytes) +
-                                         " bytes of device memory: " + hipGetErrorString(e));
-    }
-    b->pbytes = Q.bytes;
-  }
-  double* base = reinterpret_cast<double*>(b->dmem);
-  double* pbase = reinterpret_cast<double*>(b->pmem);
-  std::memcpy(b->hbuf, hyp, (size_t)nh * 8);
-  hipError_t e = hipMemcpyAsync(base + P.hyp, b->hbuf, (size_t)nh * 8, hipMemcpyHostToDevice,
-                                ctx->stream);
-  if (e == hipSuccess)
-    e = hipMemcpyAsync(pbase + Q.dadd, diag_add, (size_t)np * 8, hipMemcpyHostToDevice, ctx->stream);
-  if (e == hipSuccess && diag_vec)
-    e = hipMemcpyAsync(pbase + Q.dv, diag_vec, (size_t)Q.sn * 8, hipMemcpyHostToDevice, ctx->stream);
-  if (e == hipSuccess)
-    e = hipMemcpyAsync(pbase + Q.t, t, (size_t)Q.sm * 24, hipMemcpyHostToDevice, ctx->stream);
-  if (e == hipSuccess)
-    e = hipMemcpyAsync(b->pmem + Q.table, Q.pp.data(), (size_t)np * sizeof(MidPostProb),
-                       hipMemcpyHostToDevice, ctx->stream);
-  if (e != hipSuccess) return hip_fail(ctx, e, (who + ": upload").c_str());
-  MidArgs a{};
-  a.probs = reinterpret_cast<const MidProb*>(b->dmem + P.table);
-  a.base = base;
-  a.status = reinterpret_cast<int*>(b->dmem + P.status);
-  MidPostArgs q{};
-  q.pp = reinterpret_cast<const MidPostProb*>(b->pmem + Q.table);
-  q.base = pbase;
-  q.dadd = Q.dadd;
-  q.maxtiles = Q.maxtiles;
-  for (const MidLaunch& l : Q.launches)
-    if (int r = launch_mid(ctx, l, a, &q)) return r;
-  return LFM_OK;
-}
-
-int mid_post_call(lfm_ctx* ctx, lfm_mbatch* b, const MidPostPlan& Q, const double* hyp,
-                  const double* diag_vec, const double* diag_add, const double* t, double* mean,
-                  double* var, double* cov, int* status) {
-  DeviceGuard g(ctx->device);
-  DeviceTenancy tenancy(ctx, false);  // shared
-  if (int r = mid_post_enqueue(ctx, b, Q, hyp, diag_vec, diag_add, t, "lfm_mbatch_posterior_f64"))
-    return r;
-  const int64_t np = Q.nprob;
-  double* pbase = reinterpret_cast<double*>(b->pmem);
-  int* dst = reinterpret_cast<int*>(b->dmem + b->plan.status);
-  hipError_t e;
-  int* hst = reinterpret_cast<int*>(b->hbuf + b->h_status);
-  e = hipMemcpyAsync(mean, pbase + Q.mean, (size_t)Q.sm * 8, hipMemcpyDeviceToHost, ctx->stream);
-  if (e == hipSuccess && var)
-    e = hipMemcpyAsync(var, pbase + Q.var, (size_t)Q.sm * 8, hipMemcpyDeviceToHost, ctx->stream);
-  if (e == hipSuccess && cov)
-    e = hipMemcpyAsync(cov, pbase + Q.cov, (size_t)Q.sc * 8, hipMemcpyDeviceToHost, ctx->stream);
-  if (e == hipSuccess)
-    e = hipMemcpyAsync(hst, dst, (size_t)np * sizeof(int), hipMemcpyDeviceToHost, ctx->stream);
-  if (e != hipSuccess) return hip_fail(ctx, e, "lfm_mbatch_posterior_f64: download");
-  if (int r = finish(ctx)) return r;
-  return batch_status(ctx, hst, np, status);
-}
-
-// One predictive call: the posterior call's uploads and launches with the covariance, cov_add,
-// ystar, the seeds and the two tables into the fourth arena (grown here when this call needs
-// more), the plan's launches on the second table, and logp, the samples, the mean and the status
-// words down. A problem whose covariance failed to factor has a valid mean on the device: the
-// host replaces it with NaN.
-int mid_draw_call(lfm_ctx* ctx, lfm_mbatch* b, const MidPostPlan& Q, const MidDrawPlan& D,
-                  const double* hyp, const double* diag_vec, const double* diag_add,
-                  const double* t, const double* cov_add, const double* ystar, double* logp,
-                  const uint64_t* seeds, double* mean, double* samples, int* status) {
-  const std::string who = "lfm_mbatch_predictive_f64";
-  DeviceGuard g(ctx->device);
-  DeviceTenancy tenancy(ctx, false);  // shared
-  const MidPlan& P = b->plan;
-  const int64_t np = P.nprob;
-  if (b->qbytes < D.bytes) {
-    // every call on the handle is synchronous: nothing of the old arena is in flight
-    if (b->qmem) hipFree(b->qmem);
-    b->qmem = nullptr;
-    b->qbytes = 0;
-    const hipError_t e = hipMalloc((void**)&b->qmem, D.bytes);
-    if (e != hipSuccess) {
-      b->qmem = nullptr;
-      (void)hipGetLastError();
-      return set_err(ctx, LFM_E_OOM, who + ": " + std::to_string(D.bytes) +
-                                         " bytes of device memory: " + hipGetErrorString(e));
-    }
-    b->qbytes = D.bytes;
-  }
-  if (int r = mid_post_enqueue(ctx, b, Q, hyp, diag_vec, diag_add, t, who)) return r;
-  double* pbase = reinterpret_cast<double*>(b->pmem);
-  double* qbase = reinterpret_cast<double*>(b->qmem);
-  hipError_t e = hipMemcpyAsync(qbase + D.cadd, cov_add, (size_t)np * 8, hipMemcpyHostToDevice,
-                                ctx->stream);
-  if (e == hipSuccess && ystar)
-    e = hipMemcpyAsync(qbase + D.ystar, ystar, (size_t)D.sm * 8, hipMemcpyHostToDevice, ctx->stream);
-  if (e == hipSuccess && D.nsamp > 0)
-    e = hipMemcpyAsync(b->qmem + D.seeds, seeds, (size_t)np * sizeof(uint64_t),
-                       hipMemcpyHostToDevice, ctx->stream);
-  if (e == hipSuccess)
-    e = hipMemcpyAsync(b->qmem + D.table, D.probs.data(), (size_t)np * sizeof(MidProb),
-                       hipMemcpyHostToDevice, ctx->stream);
-  if (e == hipSuccess)
-    e = hipMemcpyAsync(b->qmem + D.dtable, D.dp.data(), (size_t)np * sizeof(MidDrawProb),
-                       hipMemcpyHostToDevice, ctx->stream);
-  if (e != hipSuccess) return hip_fail(ctx, e, "lfm_mbatch_predictive_f64: upload");
-  int* dst = reinterpret_cast<int*>(b->dmem + P.status);
-  MidArgs a{};
-  a.probs = reinterpret_cast<const MidProb*>(b->qmem + D.table);
-  a.base = qbase;
-  a.status = dst;
-  a.out = D.out;
-  a.negative = 0;
-  MidDrawArgs d{};
-  d.dp = reinterpret_cast<const MidDrawProb*>(b->qmem + D.dtable);
-  d.base = qbase;
-  d.mean = pbase + Q.mean;
-  d.cov = pbase + Q.cov;
-  d.seeds = reinterpret_cast<const uint64_t*>(b->qmem + D.seeds);
-  d.cadd = D.cadd;
-  d.nsamp = D.nsamp;
-  d.sample0 = (uint64_t)D.sample0;
-  d.maxcb = D.maxcb;
-  d.flops = (double)D.nsamp * (double)Q.sc;
-  for (const MidLaunch& l : D.launches)
-    if (int r = launch_mid(ctx, l, a, nullptr, nullptr, &d)) return r;
-  int* hst = reinterpret_cast<int*>(b->hbuf + b->h_status);
-  e = hipMemcpyAsync(hst, dst, (size_t)np * sizeof(int), hipMemcpyDeviceToHost, ctx->stream);
-  if (e == hipSuccess && mean)
-    e = hipMemcpyAsync(mean, pbase + Q.mean, (size_t)Q.sm * 8, hipMemcpyDeviceToHost, ctx->stream);
-  if (e == hipSuccess && logp)
-    e = hipMemcpyAsync(logp, qbase + D.out, (size_t)np * 8, hipMemcpyDeviceToHost, ctx->stream);
-  if (e == hipSuccess && D.nsamp > 0)
-    e = hipMemcpyAsync(samples, qbase + D.X, (size_t)(D.nsamp * D.sm) * 8, hipMemcpyDeviceToHost,
-                       ctx->stream);
-  if (e != hipSuccess) return hip_fail(ctx, e, "lfm_mbatch_predictive_f64: download");
-  if (int r = finish(ctx)) return r;
-  if (mean)
-    for (int64_t q = 0; q < np; ++q)
-      if (hst[q] != 0)
-        std::fill(mean + D.dp[q].mean, mean + D.dp[q].mean + D.dp[q].m, std::nan(""));
-  return batch_status(ctx, hst, np, status,
-                      "Cholesky failed: non-positive pivot in a batch problem's S or in its "
-                      "predictive covariance");
-}
-
-// One fit call: raw, mu, nu and the bias corrections into the third arena (grown here when this
-// call needs more), the plan's launches — the constrain, then per step the value-and-gradient
-// launches and the update — enqueued without a host wait between them, one synchronise, and the
-// parameters, the history and the first-bad-step words down.
-int mid_fit_call(lfm_ctx* ctx, lfm_mbatch* b, const MidFitPlan& F, const lfm_adam* opt,
-                 int negative, int64_t step0, double* raw, double* mu, double* nu,
-                 double* history, int* status) {
-  DeviceGuard g(ctx->device);
-  DeviceTenancy tenancy(ctx, false);  // shared, for the whole call
-  const MidPlan& P = b->plan;
-  const int64_t np = P.nprob, nh = P.nhyp, ns = F.nsteps;
-  if (b->fbytes < F.bytes) {
-    // every call on the handle is synchronous: nothing of the old arena is in flight
-    if (b->fmem) hipFree(b->fmem);
-    b->fmem = nullptr;
-    b->fbytes = 0;
-    const hipError_t e = hipMalloc((void**)&b->fmem, F.bytes);
-    if (e != hipSuccess) {
-      b->fmem = nullptr;
-      (void)hipGetLastError();
-      return set_err(ctx, LFM_E_OOM, "lfm_mbatch_fit_f64: " + std::to_string(F.bytes) +
-                                         " bytes of device memory: " + hipGetErrorString(e));
-    }
-    b->fbytes = F.bytes;
-  }
-  double* base = reinterpret_cast<double*>(b->dmem);
-  double* fbase = reinterpret_cast<double*>(b->fmem);
-  // raw | mu | nu | bias are adjacent in the arena: one upload. optax's bias corrections
-  // 1 - b^count, count = step0 + s + 1, with the host's pow (the restatement's numbers:
-  // dis_project_amd/trainer.py adam)
-  std::vector<double> par((size_t)F.hist, 0.0);
-  std::memcpy(par.data() + F.raw, raw, (size_t)nh * 8);
-  std::memcpy(par.data() + F.mu, mu, (size_t)nh * 8);
-  std::memcpy(par.data() + F.nu, nu, (size_t)nh * 8);
-  for (int64_t s = 0; s < ns; ++s) {
-    const double count = (double)(step0 + s + 1);
-    par[(size_t)(F.bias + 2 * s)] = 1.0 - std::pow(opt->b1, count);
-    par[(size_t)(F.bias + 2 * s + 1)] = 1.0 - std::pow(opt->b2, count);
-  }
-  hipError_t e = hipMemcpyAsync(fbase, par.data(), (size_t)F.hist * 8, hipMemcpyHostToDevice,
-                                ctx->stream);
-  if (e != hipSuccess) return hip_fail(ctx, e, "lfm_mbatch_fit_f64: upload");
-  MidArgs a{};
-  a.probs = reinterpret_cast<const MidProb*>(b->dmem + P.table);
-  a.base = base;
-  a.status = reinterpret_cast<int*>(b->dmem + P.status);
-  a.out = P.out;
-  a.grad = P.grad;
-  a.negative = negative;
-  MidFitArgs f{};
-  f.base = fbase;
-  f.raw = F.raw;
-  f.mu = F.mu;
-  f.nu = F.nu;
-  f.bias = F.bias;
-  f.hist = F.hist;
-  f.first_bad = reinterpret_cast<int*>(b->fmem + F.first_bad);
-  f.lr = opt->learning_rate;
-  f.b1 = opt->b1;
-  f.b2 = opt->b2;
-  f.eps = opt->eps;
-  f.eps_root = opt->eps_root;
-  f.step0 = step0;
-  f.spe = opt->num_steps_per_epoch;
-  f.nprob = (int)np;
-  f.fix = opt->fix_params != 0;
-  for (const MidLaunch& l : F.launches)
-    if (int r = launch_mid(ctx, l, a, nullptr, &f)) return r;
-  std::vector<int> st((size_t)np);
-  e = hipMemcpyAsync(par.data(), fbase, (size_t)F.bias * 8, hipMemcpyDeviceToHost, ctx->stream);
-  if (e == hipSuccess)
-    e = hipMemcpyAsync(history, fbase + F.hist, (size_t)(ns * np) * 8, hipMemcpyDeviceToHost,
-                       ctx->stream);
-  if (e == hipSuccess)
-    e = hipMemcpyAsync(st.data(), f.first_bad, (size_t)np * sizeof(int), hipMemcpyDeviceToHost,
-                       ctx->stream);
-  if (e != hipSuccess) return hip_fail(ctx, e, "lfm_mbatch_fit_f64: download");
-  if (int r = finish(ctx)) return r;
-  // the packed layout's jitter slots pass through unchanged (a static field, model.py:64)
-  std::memcpy(raw, par.data() + F.raw, (size_t)nh * 8);
-  std::memcpy(mu, par.data() + F.mu, (size_t)nh * 8);
-  std::memcpy(nu, par.data() + F.nu, (size_t)nh * 8);
-  return batch_status(ctx, st.data(), np, status,
-                      "Cholesky failed during the fit of a batch problem (its loss "
-                      "and parameters are NaN from that step on, as JAX's)",
-                      true);
-}
+const MidRow mid_rows[] = {
+    mid_row<&mid_fill_kernel<false>, &MidCall::none>(K_MID_FILL, 0, "mid_fill_kernel"),
+    mid_row<&mid_column_kernel>(K_MID_COLUMN, MID_LDS, "mid_column_kernel"),
+    mid_row<&mid_value_kernel>(K_MID_FINISH, 0, "mid_value_kernel"),
+    mid_row<&mid_invert_kernel>(K_MID_INVERSE, MID_LDS, "mid_invert_kernel"),
+    mid_row<&mid_sinv_kernel>(K_MID_INVERSE, MID_LDS, "mid_sinv_kernel"),
+    mid_row<&mid_pairs_kernel>(K_MID_PAIRS, 0, "mid_pairs_kernel"),
+    mid_row<&mid_grad_kernel>(K_MID_FINISH, 0, "mid_grad_kernel"),
+    mid_row<&mid_fill_kernel<true>, &MidCall::q>(K_MID_FILL, 0, "mid_fill_kernel (posterior)"),
+    mid_row<&mid_solve_kernel, &MidCall::q>(K_MID_INVERSE, MID_LDS, "mid_solve_kernel"),
+    mid_row<&mid_cov_kernel, &MidCall::q>(K_MID_FINISH, MID_LDS, "mid_cov_kernel"),
+    mid_row<&mid_adam_kernel, &MidCall::f>(K_MID_FINISH, 0, "mid_adam_kernel"),  // MID_CONSTRAIN
+    mid_row<&mid_adam_kernel, &MidCall::f>(K_MID_FINISH, 0, "mid_adam_kernel"),  // MID_ADAM
+    mid_row<&mid_draw_scale_kernel, &MidCall::d>(K_MID_FILL, 0, "mid_draw_scale_kernel"),
+    mid_row<&mid_draw_randn_kernel, &MidCall::d>(K_SAMPLE_RANDN, 0, "mid_draw_randn_kernel"),
+    mid_row<&mid_draw_product_kernel, &MidCall::d>(K_SAMPLE_TRMM, MID_DRAW_LDS,
+                                                   "mid_draw_product_kernel"),
+};
+static_assert(sizeof(mid_rows) / sizeof(mid_rows[0]) == MID_KINDS, "a row per MidKind, in order");
 
 }  // namespace
 
+int launch_mid(lfm_ctx* ctx, const MidLaunch& l, MidCall& c) {
+  static const bool attrs = [] {
+    for (const MidRow& r : mid_rows)
+      if (r.lds > 0)
+        hipFuncSetAttribute(r.kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)r.lds);
+    return true;
+  }();
+  (void)attrs;
+  if (l.kind < 0 || l.kind >= MID_KINDS)
+    return set_err(ctx, LFM_E_STATE, "plan_mid: unknown launch kind " + std::to_string(l.kind));
+  const MidRow& r = mid_rows[l.kind];
+  if ((r.needs & c.has) != r.needs)
+    return set_err(ctx, LFM_E_STATE, std::string("launch_mid: ") + r.name + " (kind " +
+                                         std::to_string(l.kind) +
+                                         ") takes arguments this call has not filled");
+  c.a.k = l.k;
+  if (r.needs & MID_HAS_FIT) c.f.s = l.kind == MID_ADAM ? l.k : -1;
+  hipEvent_t ev;
+  prof_begin(ctx, r.cls, &ev);
+  r.issue(c, dim3(l.gx, l.gy), r.lds, ctx->stream);
+  prof_end(ctx, r.cls, ev, l.kind == MID_DRAW_PRODUCT ? c.d.flops : 0, 0);
+  return hip_fail(ctx, hipGetLastError(), r.name);
+}
+
 }  // namespace lfm
 
-extern "C" {
-
-int lfm_mbatch_create(lfm_ctx* ctx, int64_t nprob, const lfm_problem* probs, lfm_mbatch** out) {
-  if (!ctx) return LFM_E_ARG;
-  if (!out || nprob < 1 || !probs) return set_err(ctx, LFM_E_ARG, "bad batch arguments");
-  *out = nullptr;
-  std::vector<MidShape> shapes((size_t)nprob);
-  for (int64_t q = 0; q < nprob; ++q) {
-    const lfm_problem& p = probs[q];
-    if (int r = validate_x(ctx, p.x, p.n)) return r;
-    if (!p.y) return set_err(ctx, LFM_E_ARG, "problem y is NULL");
-    shapes[q] = {p.n, p.hyp.num_genes};
-  }
-  std::unique_ptr<lfm_mbatch> b(new lfm_mbatch);
-  b->plan = plan_mid(shapes);
-  b->shapes = shapes;
-  const MidPlan& P = b->plan;
-  if (P.reject) return set_err(ctx, LFM_E_ARG, P.why);
-  DeviceGuard g(ctx->device);
-  b->device = ctx->device;
-  auto even = [](int64_t d) { return (size_t)((d + 1) / 2 * 2); };
-  b->h_out = even(P.nhyp);
-  b->h_grad = b->h_out + even(P.nprob);
-  b->h_status = b->h_grad + even(P.nhyp);
-  const size_t hbytes = b->h_status * 8 + (size_t)P.nprob * sizeof(int);
-  hipError_t e = hipMalloc((void**)&b->dmem, P.bytes);
-  if (e != hipSuccess)
-    return set_err(ctx, LFM_E_OOM, "lfm_mbatch_create: " + std::to_string(P.bytes) +
-                                       " bytes of device memory: " + hipGetErrorString(e));
-  e = hipHostMalloc((void**)&b->hbuf, hbytes, hipHostMallocDefault);
-  if (e == hipSuccess) e = hipMemsetAsync(b->dmem, 0, P.bytes, ctx->stream);
-  // x / y of every problem (adjacent in the arena), then the table; the staging outlives the copies
-  std::vector<std::vector<double>> stagings((size_t)nprob);
-  for (int64_t q = 0; q < nprob && e == hipSuccess; ++q) {
-    const MidProb& m = P.probs[q];
-    std::vector<double>& s = stagings[q];
-    s.assign((size_t)(m.S - m.x), 0.0);
-    std::memcpy(s.data(), probs[q].x, (size_t)m.n * 3 * 8);
-    std::memcpy(s.data() + (m.y - m.x), probs[q].y, (size_t)m.n * 8);
-    e = hipMemcpyAsync(reinterpret_cast<double*>(b->dmem) + m.x, s.data(), s.size() * 8,
-                       hipMemcpyHostToDevice, ctx->stream);
-  }
-  if (e == hipSuccess)
-    e = hipMemcpyAsync(b->dmem + P.table, P.probs.data(), (size_t)nprob * sizeof(MidProb),
-                       hipMemcpyHostToDevice, ctx->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-  if (e != hipSuccess) {
-    hipFree(b->dmem);
-    if (b->hbuf) hipHostFree(b->hbuf);
-    return hip_fail(ctx, e, "lfm_mbatch_create: upload");
-  }
-  *out = b.release();
-  return LFM_OK;
-}
-
-int lfm_mbatch_destroy(lfm_mbatch* batch) {
-  if (!batch) return LFM_E_ARG;
-  hipSetDevice(batch->device);
-  hipFree(batch->dmem);  // every call on the handle is synchronous: nothing of it is in flight
-  if (batch->pmem) hipFree(batch->pmem);
-  if (batch->fmem) hipFree(batch->fmem);
-  if (batch->qmem) hipFree(batch->qmem);
-  hipHostFree(batch->hbuf);
-  delete batch;
-  return LFM_OK;
-}
-
-int lfm_mbatch_hyp_size(const lfm_mbatch* batch, int64_t* out) {
-  if (!batch || !out) return LFM_E_ARG;
-  *out = batch->plan.nhyp;
-  return LFM_OK;
-}
-
-int lfm_mbatch_mll_f64(lfm_ctx* ctx, lfm_mbatch* batch, const double* hyp, int negative,
-                       double* out, int* status) {
-  if (!ctx) return LFM_E_ARG;
-  if (!batch || !hyp || !out) return set_err(ctx, LFM_E_ARG, "batch / hyp / out is NULL");
-  if (batch->device != ctx->device) return set_err(ctx, LFM_E_ARG, "batch of another device");
-  return mid_call(ctx, batch, hyp, negative, false, out, nullptr, status);
-}
-
-int lfm_mbatch_mll_grad_f64(lfm_ctx* ctx, lfm_mbatch* batch, const double* hyp, int negative,
-                            double* value, double* grad, int* status) {
-  if (!ctx) return LFM_E_ARG;
-  if (!batch || !hyp || !value || !grad)
-    return set_err(ctx, LFM_E_ARG, "batch / hyp / value / grad is NULL");
-  if (batch->device != ctx->device) return set_err(ctx, LFM_E_ARG, "batch of another device");
-  return mid_call(ctx, batch, hyp, negative, true, value, grad, status);
-}
-
-int lfm_mbatch_posterior_f64(lfm_ctx* ctx, lfm_mbatch* batch, const double* hyp,
-                             const double* diag_vec, const double* diag_add, const int64_t* m,
-                             const double* t, double* mean, double* var, double* cov,
-                             int* status) {
-  if (!ctx) return LFM_E_ARG;
-  if (!batch || !hyp || !diag_add || !m || !t || !mean)
-    return set_err(ctx, LFM_E_ARG, "batch / hyp / diag_add / m / t / mean is NULL");
-  if (!var && !cov) return set_err(ctx, LFM_E_ARG, "one of var / cov must be given");
-  if (batch->device != ctx->device) return set_err(ctx, LFM_E_ARG, "batch of another device");
-  const MidPostPlan Q = plan_mid_post(batch->shapes, m, diag_vec != nullptr, cov != nullptr);
-  if (Q.reject) return set_err(ctx, LFM_E_ARG, Q.why);
-  return mid_post_call(ctx, batch, Q, hyp, diag_vec, diag_add, t, mean, var, cov, status);
-}
-
-int lfm_mbatch_fit_f64(lfm_ctx* ctx, lfm_mbatch* batch, const lfm_adam* opt, int negative,
-                       int64_t step0, int64_t nsteps, double* raw, double* mu, double* nu,
-                       double* history, int* status) {
-  if (!ctx) return LFM_E_ARG;
-  if (!batch) return set_err(ctx, LFM_E_ARG, "lfm_mbatch_fit_f64: batch is NULL");
-  if (!opt) return set_err(ctx, LFM_E_ARG, "lfm_mbatch_fit_f64: opt is NULL");
-  if (!raw || !mu || !nu) return set_err(ctx, LFM_E_ARG, "lfm_mbatch_fit_f64: raw / mu / nu is NULL");
-  if (nsteps > 0 && !history) return set_err(ctx, LFM_E_ARG, "lfm_mbatch_fit_f64: history is NULL");
-  if (step0 < 0 || nsteps < 0)
-    return set_err(ctx, LFM_E_ARG, "lfm_mbatch_fit_f64: step0 and nsteps must be >= 0");
-  if (opt->num_steps_per_epoch < 1)
-    return set_err(ctx, LFM_E_ARG, "lfm_mbatch_fit_f64: num_steps_per_epoch must be >= 1");
-  if (batch->device != ctx->device) return set_err(ctx, LFM_E_ARG, "batch of another device");
-  if (nsteps == 0) return LFM_OK;
-  const MidFitPlan F = plan_mid_fit(batch->shapes, nsteps);
-  if (F.reject) return set_err(ctx, LFM_E_ARG, F.why);
-  return mid_fit_call(ctx, batch, F, opt, negative, step0, raw, mu, nu, history, status);
-}
-
-int lfm_mbatch_predictive_f64(lfm_ctx* ctx, lfm_mbatch* batch, const double* hyp,
-                              const double* diag_vec, const double* diag_add, const int64_t* m,
-                              const double* t, const double* cov_add, const double* ystar,
-                              double* logp, const uint64_t* seeds, int64_t sample0, int64_t nsamp,
-                              double* mean, double* samples, int* status) {
-  if (!ctx) return LFM_E_ARG;
-  const std::string who = "lfm_mbatch_predictive_f64: ";
-  if (!batch || !hyp || !diag_add || !m || !t)
-    return set_err(ctx, LFM_E_ARG, who + "batch / hyp / diag_add / m / t is NULL");
-  if ((ystar != nullptr) != (logp != nullptr))
-    return set_err(ctx, LFM_E_ARG, who + "ystar and logp must be given together");
-  if (nsamp > 0 && !seeds) return set_err(ctx, LFM_E_ARG, who + "seeds is NULL with nsamp > 0");
-  if ((nsamp > 0) != (samples != nullptr))
-    return set_err(ctx, LFM_E_ARG, who + "samples must be given exactly when nsamp > 0");
-  if (batch->device != ctx->device)
-    return set_err(ctx, LFM_E_ARG, who + "batch of another device");
-  const MidDrawPlan D =
-      plan_mid_draw(batch->shapes, m, cov_add != nullptr, ystar != nullptr, nsamp, sample0);
-  if (D.reject) return set_err(ctx, LFM_E_ARG, D.why);
-  const MidPostPlan Q = plan_mid_post(batch->shapes, m, diag_vec != nullptr, true);
-  if (Q.reject) return set_err(ctx, LFM_E_ARG, Q.why);
-  return mid_draw_call(ctx, batch, Q, D, hyp, diag_vec, diag_add, t, cov_add, ystar, logp, seeds,
-                       mean, samples, status);
-}
-
-}  // extern "C"

@@ -1,8 +1,9 @@
 // lfm_mid_plan.h — layout and launch plan of the resident batch of mid-size problems
 // (lfm_mbatch_*, 1 <= n <= MID_MAX_N): every problem's regions in the handle's device arena, the
 // grids and the launch list of a value call and of a value-and-gradient call. Plain C++ (part of
-// lfm_host.h): lfm_mid.hip only reads it, and tests/native/mid_plan_check.cpp checks it by
-// enumeration under the sanitizers.
+// lfm_host.h): lfm_mbatch.hip (the handle and its calls) and lfm_mid.hip (the kernels and their
+// launcher) only read it, and tests/native/mid_plan_check.cpp checks it by enumeration under the
+// sanitizers.
 //
 // Per problem the arena holds x [n x 3], y [n] and, with Mp = 64 ceil((n + 1) / 64) and
 // nb = Mp / 64 block rows, three Mp x Mp row-major matrices:
@@ -85,7 +86,8 @@ struct MidProb {
 enum MidKind {
   MID_FILL = 0, MID_COLUMN, MID_VALUE, MID_INVERT, MID_SINV, MID_PAIRS, MID_GRAD,
   MID_POST_FILL, MID_SOLVE, MID_COV, MID_CONSTRAIN, MID_ADAM,
-  MID_DRAW_SCALE, MID_DRAW_RANDN, MID_DRAW_PRODUCT
+  MID_DRAW_SCALE, MID_DRAW_RANDN, MID_DRAW_PRODUCT,
+  MID_KINDS  // their number: launch_mid's table has a row for each
 };
 struct MidLaunch {
   int kind, k;

@@ -1,5 +1,5 @@
 // mid_draw_plan_check.cpp — plan_mid_draw (dis_project_amd/csrc/lfm_host.cpp), the fourth arena,
-// the second problem table and the launch list of lfm_mbatch_predictive_f64 (lfm_mid.hip issues
+// the second problem table and the launch list of lfm_mbatch_predictive_f64 (lfm_mbatch.hip issues
 // exactly what it says), under AddressSanitizer + UBSan: built and run by
 // tests/test_mid_draw_host.py with the flags of tests/test_sample_host.py. Over n in {1, 64, 129,
 // 1024}, m in {G, 63, 64, 65, 128, 129, 130, 320, 1023, 1024}, nsamp in {0, 1, 3, 64, 65, 130,
@@ -106,6 +106,7 @@ static void check_regions(const MidDrawPlan& P, const std::vector<MidShape>& sha
 // every unit of every problem has exactly one owner in the launch, by the kernels' mapping
 static void check_launch(const MidDrawPlan& P, const MidLaunch& l, bool enumerate_pairs) {
   CHECK(l.gx == (unsigned)P.nprob && l.gx >= 1, "grid.x %u", l.gx);
+  CHECK(l.kind >= 0 && l.kind < MID_KINDS, "launch kind %d", l.kind);
   CHECK(l.gy >= 1 && l.gy <= 65535u, "grid.y %u", l.gy);
   for (size_t q = 0; q < P.probs.size(); ++q) {
     const int nq = P.probs[q].nb, cb = P.dp[q].cb, sb = P.dp[q].sb;

@@ -1,5 +1,5 @@
 // mid_fit_plan_check.cpp — plan_mid_fit (dis_project_amd/csrc/lfm_host.cpp), the third arena and
-// the launch list of lfm_mbatch_fit_f64 (lfm_mid.hip issues exactly what it says), under
+// the launch list of lfm_mbatch_fit_f64 (lfm_mbatch.hip issues exactly what it says), under
 // AddressSanitizer + UBSan: built and run by tests/test_mid_fit_host.py with the flags of
 // tests/native/Makefile. Over single problems at the tile edges, mixed batches and
 // nsteps = 1 .. 12, 150 and the cap:
@@ -86,6 +86,7 @@ static void check_fit(const std::vector<MidShape>& shapes, int64_t nsteps) {
   CHECK(F.per_step == per, "per_step");
   CHECK(F.launches.size() == 1 + (size_t)nsteps * per, "launch count %zu", F.launches.size());
   if (F.launches.size() != 1 + (size_t)nsteps * per) return;
+  for (const MidLaunch& l : F.launches) CHECK(l.kind >= 0 && l.kind < MID_KINDS, "launch kind %d", l.kind);
   const MidLaunch& c = F.launches[0];
   CHECK(c.kind == MID_CONSTRAIN && c.gx == (unsigned)F.nprob && c.gy == 1u, "the constrain");
   for (int64_t s = 0; s < nsteps; ++s) {

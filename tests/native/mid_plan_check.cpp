@@ -1,5 +1,5 @@
 // mid_plan_check.cpp — plan_mid (dis_project_amd/csrc/lfm_host.cpp), the arena layout and launch
-// plan of the mid-size resident batch (lfm_mid.hip issues exactly what it says), under
+// plan of the mid-size resident batch (lfm_mbatch.hip issues exactly what it says), under
 // AddressSanitizer + UBSan: built and run by tests/test_mid_host.py with the flags of
 // tests/native/Makefile. Over an empty batch, n = 1, 63 / 64 / 65, 1024, every n in a sweep and
 // mixed batches:
@@ -80,6 +80,7 @@ static void check_regions(const MidPlan& P) {
 // owners[(I, J)] of problem m in launch l, by the kernels' unit -> tile mapping
 static void check_launch(const MidPlan& P, const MidLaunch& l) {
   CHECK(l.gx == (unsigned)P.nprob && l.gx >= 1 && l.gx <= 2147483647u, "grid.x %u", l.gx);
+  CHECK(l.kind >= 0 && l.kind < MID_KINDS, "launch kind %d", l.kind);
   CHECK(l.gy >= 1 && l.gy <= 65535u, "grid.y %u", l.gy);
   CHECK((uint64_t)l.gx * 256 < ((uint64_t)1 << 32), "threads along x");
   for (const MidProb& m : P.probs) {

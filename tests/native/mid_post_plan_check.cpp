@@ -1,5 +1,5 @@
 // mid_post_plan_check.cpp — plan_mid_post (dis_project_amd/csrc/lfm_host.cpp), the second arena
-// and the launch list of lfm_mbatch_posterior_f64 (lfm_mid.hip issues exactly what it says),
+// and the launch list of lfm_mbatch_posterior_f64 (lfm_mbatch.hip issues exactly what it says),
 // under AddressSanitizer + UBSan: built and run by tests/test_mid_predict_host.py with the flags
 // of tests/test_mid_host.py. Over n in {1, 63, 64, 127, 128, 129, 192, 193, 1023, 1024}, m in
 // {G, 60, 64, 68, 130, 4096}, with and without diag_vec / cov, and mixed batches:
@@ -92,6 +92,7 @@ static void check_regions(const MidPostPlan& P, const std::vector<MidShape>& sha
 static void check_launch(const MidPostPlan& P, const std::vector<MidShape>& shapes,
                          const MidLaunch& l) {
   CHECK(l.gx == (unsigned)P.nprob && l.gx >= 1, "grid.x %u", l.gx);
+  CHECK(l.kind >= 0 && l.kind < MID_KINDS, "launch kind %d", l.kind);
   CHECK(l.gy >= 1 && l.gy <= 65535u, "grid.y %u", l.gy);
   for (size_t q = 0; q < shapes.size(); ++q) {
     const int nb = mid_blocks((int)shapes[q].n), mb = P.pp[q].mb;
