@@ -67,6 +67,58 @@ hipError_t alloc_fixed(lfm_ctx* ctx);
 
 inline int64_t round_up(int64_t a, int64_t b) { return (a + b - 1) / b * b; }
 
+// A call's copies on ctx->stream, in the order given; after the first that fails the rest do
+// nothing. e may start as an earlier step's error: the copies then do nothing at all.
+struct Copies {
+  lfm_ctx* ctx;
+  hipError_t e = hipSuccess;
+  void up(void* dst, const void* src, size_t n) { copy(dst, src, n, hipMemcpyHostToDevice); }
+  void down(void* dst, const void* src, size_t n) { copy(dst, src, n, hipMemcpyDeviceToHost); }
+  // the first failure as `what`, or LFM_OK
+  int done(const char* what) { return hip_fail(ctx, e, what); }
+  // the end of a call's downloads: done(what), then the stream synchronised
+  int landed(const char* what) {
+    if (int r = done(what)) return r;
+    return finish(ctx);
+  }
+
+ private:
+  void copy(void* dst, const void* src, size_t bytes, hipMemcpyKind kind) {
+    if (e == hipSuccess) e = hipMemcpyAsync(dst, src, bytes, kind, ctx->stream);
+  }
+};
+
+// ------------------------------------------- the on-device fits' host half (both batches)
+// The kernels' optimiser from the caller's and the count of the steps already taken
+inline AdamOpt adam_opt(const lfm_adam* opt, int64_t step0) {
+  return {opt->learning_rate, opt->b1, opt->b2, opt->eps, opt->eps_root, step0,
+          opt->num_steps_per_epoch, opt->fix_params != 0};
+}
+// A fit call's staging, raw | mu | nu | bias as its arena lays them out (offsets in doubles from
+// the arena's start, the bias table last; gaps are 0): one upload of all of it before the
+// launches, one download of [0, bias) after them.
+struct FitStaging {
+  std::vector<double> par;
+  size_t nh, raw, mu, nu, bias;
+  FitStaging(const lfm_adam* opt, int64_t step0, int64_t nsteps, int64_t nhyp, size_t raw_at,
+             size_t mu_at, size_t nu_at, size_t bias_at, const double* r, const double* m1,
+             const double* m2)
+      : par(bias_at + 2 * (size_t)nsteps, 0.0), nh((size_t)nhyp), raw(raw_at), mu(mu_at),
+        nu(nu_at), bias(bias_at) {
+    std::copy(r, r + nh, par.begin() + raw);
+    std::copy(m1, m1 + nh, par.begin() + mu);
+    std::copy(m2, m2 + nh, par.begin() + nu);
+    adam_bias(opt, step0, nsteps, par.data() + bias);
+  }
+  // the downloaded parameters and moments to the caller; the packed layout's jitter slots pass
+  // through unchanged (a static field, model.py:64)
+  void back(double* r, double* m1, double* m2) const {
+    std::copy(par.begin() + raw, par.begin() + raw + nh, r);
+    std::copy(par.begin() + mu, par.begin() + mu + nh, m1);
+    std::copy(par.begin() + nu, par.begin() + nu + nh, m2);
+  }
+};
+
 inline int validate_x(lfm_ctx* ctx, const void* x, int64_t n) {
   if (!ctx) return LFM_E_ARG;
   if (!x) return set_err(ctx, LFM_E_ARG, "x is NULL");
@@ -103,6 +155,10 @@ int batch_launch(lfm_ctx* ctx, lfm_batch* batch, const double* hyp, int negative
 int batch_status(lfm_ctx* ctx, const int* words, int64_t np, int* status,
                  const char* msg = "Cholesky failed: non-positive pivot in a batch problem",
                  bool raw = false);
+// msg of both on-device fits (their words are raw: 1 + the first step whose factor failed)
+constexpr const char* FIT_FAILED =
+    "Cholesky failed during the fit of a batch problem (its loss and parameters are NaN from "
+    "that step on, as JAX's)";
 
 // the status words of the batch's pinned buffer
 inline int* batch_words(const lfm_batch* batch) {

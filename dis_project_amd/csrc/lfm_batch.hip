@@ -128,18 +128,17 @@ int small_batch(lfm_ctx* ctx, int64_t np, const lfm_problem* probs, const int64_
   for (int64_t q = 0; q < np; ++q)
     pack_small(probs[idx[q]], shapes[q], lays[q], pack.at[q], hd, dd, nullptr, nullptr, hp[q]);
   const size_t up = round_up(bytes_d, 16) + bytes_p;
-  hipError_t e = hipMemcpyAsync(db, hb, up, hipMemcpyHostToDevice, ctx->stream);
-  if (e != hipSuccess) return hip_fail(ctx, e, "upload small batch");
+  Copies cp{ctx};
+  cp.up(db, hb, up);
+  if ((r = cp.done("upload small batch"))) return r;
   double* d_out = reinterpret_cast<double*>(db + round_up(bytes_d, 16) + round_up(bytes_p, 16));
   int* d_st = reinterpret_cast<int*>(d_out + np);
   r = launch_small_batch(ctx, reinterpret_cast<const SmallProb*>(db + round_up(bytes_d, 16)),
                          (int)np, plan_small_mll(small_dims(shapes)), negative, d_out, d_st);
   if (r) return r;
   double* h_out = reinterpret_cast<double*>(hb + round_up(bytes_d, 16) + round_up(bytes_p, 16));
-  e = hipMemcpyAsync(h_out, d_out, np * 12, hipMemcpyDeviceToHost, ctx->stream);
-  if (e != hipSuccess) return hip_fail(ctx, e, "download small batch");
-  r = finish(ctx);
-  if (r) return r;
+  cp.down(h_out, d_out, np * 12);
+  if ((r = cp.landed("download small batch"))) return r;
   const int* h_st = reinterpret_cast<const int*>(h_out + np);
   for (int64_t q = 0; q < np; ++q) {
     out[idx[q]] = h_out[q];
@@ -258,17 +257,15 @@ int lfm_batch_create(lfm_ctx* ctx, int64_t nprob, const lfm_problem* probs, lfm_
   b->lds_fit = small_grad_lds(shapes, 1);
   std::vector<int> offs(b->dsb_off);
   offs.insert(offs.end(), b->sc_off.begin(), b->sc_off.end());
-  e = hipMemcpyAsync(b->dmem, hd.data(), nd * 8, hipMemcpyHostToDevice, ctx->stream);
-  if (e == hipSuccess)
-    e = hipMemcpyAsync(b->dprobs, table.data(), (size_t)nprob * sizeof(SmallProb),
-                       hipMemcpyHostToDevice, ctx->stream);
-  if (e == hipSuccess)
-    e = hipMemcpyAsync(b->doffs, offs.data(), bytes_o, hipMemcpyHostToDevice, ctx->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-  if (e != hipSuccess) {
+  Copies cp{ctx};
+  cp.up(b->dmem, hd.data(), nd * 8);
+  cp.up(b->dprobs, table.data(), (size_t)nprob * sizeof(SmallProb));
+  cp.up(b->doffs, offs.data(), bytes_o);
+  if (cp.e == hipSuccess) cp.e = hipStreamSynchronize(ctx->stream);
+  if (int r = cp.done("lfm_batch_create: upload")) {
     hipFree(b->dmem);
     hipHostFree(b->hbuf);
-    return hip_fail(ctx, e, "lfm_batch_create: upload");
+    return r;
   }
   *out = b.release();
   return LFM_OK;
@@ -379,23 +376,11 @@ int lfm_batch_fit_f64(lfm_ctx* ctx, lfm_batch* batch, const lfm_adam* opt, int n
     batch->fit_bytes = L.bytes;
   }
   double* d_fit = reinterpret_cast<double*>(batch->fitbuf);  // raw first
-  const size_t b_par = L.bias * 8, b_bias = (L.hist - L.bias) * 8;
-  const size_t b_hist = (L.status - L.hist) * 8, b_st = (size_t)np * sizeof(int);
-  // optax's bias corrections 1 - b^count, count = step0 + s + 1, with the host's pow (the
-  // restatement's numbers: dis_project_amd/trainer.py adam)
-  std::vector<double> bias((size_t)2 * nsteps), par((size_t)3 * nh);
-  for (int64_t s = 0; s < nsteps; ++s) {
-    const double count = (double)(step0 + s + 1);
-    bias[2 * s] = 1.0 - std::pow(opt->b1, count);
-    bias[2 * s + 1] = 1.0 - std::pow(opt->b2, count);
-  }
-  std::memcpy(par.data(), raw, nh * 8);
-  std::memcpy(par.data() + L.mu, mu, nh * 8);
-  std::memcpy(par.data() + L.nu, nu, nh * 8);
-  hipError_t e = hipMemcpyAsync(d_fit, par.data(), b_par, hipMemcpyHostToDevice, ctx->stream);
-  if (e == hipSuccess)
-    e = hipMemcpyAsync(d_fit + L.bias, bias.data(), b_bias, hipMemcpyHostToDevice, ctx->stream);
-  if (e != hipSuccess) return hip_fail(ctx, e, "lfm_batch_fit_f64: upload");
+  // raw | mu | nu | bias are adjacent in the buffer (raw at its start): one upload
+  FitStaging stage(opt, step0, nsteps, nh, 0, L.mu, L.nu, L.bias, raw, mu, nu);
+  Copies cp{ctx};
+  cp.up(d_fit, stage.par.data(), stage.par.size() * 8);
+  if (int r = cp.done("lfm_batch_fit_f64: upload")) return r;
   SmallFitLaunch f{};
   f.probs = batch->dprobs;
   f.offs = batch->doffs;
@@ -406,36 +391,18 @@ int lfm_batch_fit_f64(lfm_ctx* ctx, lfm_batch* batch, const lfm_adam* opt, int n
   f.history = d_fit + L.hist;
   f.bias = d_fit + L.bias;
   f.status = reinterpret_cast<int*>(d_fit + L.status);
-  f.lr = opt->learning_rate;
-  f.b1 = opt->b1;
-  f.b2 = opt->b2;
-  f.eps = opt->eps;
-  f.eps_root = opt->eps_root;
-  f.step0 = step0;
+  f.opt = adam_opt(opt, step0);
   f.nsteps = nsteps;
-  f.spe = opt->num_steps_per_epoch;
-  f.fix = opt->fix_params != 0;
   f.negative = negative;
-  int r = launch_small_fit(ctx, f, batch->lds_fit);
-  if (r) return r;
+  if (int r = launch_small_fit(ctx, f, batch->lds_fit)) return r;
   hipEventRecord(batch->done, ctx->stream);
   std::vector<int> st((size_t)np);
-  e = hipMemcpyAsync(par.data(), d_fit, b_par, hipMemcpyDeviceToHost, ctx->stream);
-  if (e == hipSuccess)
-    e = hipMemcpyAsync(history, f.history, b_hist, hipMemcpyDeviceToHost, ctx->stream);
-  if (e == hipSuccess)
-    e = hipMemcpyAsync(st.data(), f.status, b_st, hipMemcpyDeviceToHost, ctx->stream);
-  if (e != hipSuccess) return hip_fail(ctx, e, "lfm_batch_fit_f64: download");
-  r = finish(ctx);
-  if (r) return r;
-  // the packed layout's jitter slots pass through unchanged (a static field, model.py:64)
-  std::memcpy(raw, par.data(), nh * 8);
-  std::memcpy(mu, par.data() + L.mu, nh * 8);
-  std::memcpy(nu, par.data() + L.nu, nh * 8);
-  return batch_status(ctx, st.data(), np, status,
-                      "Cholesky failed during the fit of a batch problem (its loss "
-                      "and parameters are NaN from that step on, as JAX's)",
-                      true);
+  cp.down(stage.par.data(), d_fit, L.bias * 8);
+  cp.down(history, f.history, (L.status - L.hist) * 8);
+  cp.down(st.data(), f.status, (size_t)np * sizeof(int));
+  if (int r = cp.landed("lfm_batch_fit_f64: download")) return r;
+  stage.back(raw, mu, nu);
+  return batch_status(ctx, st.data(), np, status, FIT_FAILED, true);
 }
 
 int lfm_batch_posterior_f64(lfm_ctx* ctx, lfm_batch* batch, const double* hyp,
@@ -477,8 +444,9 @@ int lfm_batch_posterior_f64(lfm_ctx* ctx, lfm_batch* batch, const double* hyp,
   std::memcpy(hp + P.t, t, 3 * P.sm * 8);
   std::memcpy(hp + P.table, P.pp.data(), (size_t)np * sizeof(PostProb));
   double* d = ctx->xin;
-  hipError_t e = hipMemcpyAsync(d, hp, P.in_bytes, hipMemcpyHostToDevice, ctx->stream);
-  if (e != hipSuccess) return hip_fail(ctx, e, "lfm_batch_posterior_f64: upload");
+  Copies cp{ctx};
+  cp.up(d, hp, P.in_bytes);
+  if ((r = cp.done("lfm_batch_posterior_f64: upload"))) return r;
   SmallPostLaunch f{};
   f.probs = batch->dprobs;
   f.offs = batch->doffs;
@@ -500,16 +468,11 @@ int lfm_batch_posterior_f64(lfm_ctx* ctx, lfm_batch* batch, const double* hyp,
   if (r) return r;
   hipEventRecord(batch->done, ctx->stream);
   std::vector<int> st((size_t)np);
-  e = hipMemcpyAsync(mean, f.mean, P.sm * 8, hipMemcpyDeviceToHost, ctx->stream);
-  if (e == hipSuccess && var)
-    e = hipMemcpyAsync(var, f.var, P.sm * 8, hipMemcpyDeviceToHost, ctx->stream);
-  if (e == hipSuccess && cov)
-    e = hipMemcpyAsync(cov, f.cov, P.sc * 8, hipMemcpyDeviceToHost, ctx->stream);
-  if (e == hipSuccess)
-    e = hipMemcpyAsync(st.data(), f.status, np * sizeof(int), hipMemcpyDeviceToHost, ctx->stream);
-  if (e != hipSuccess) return hip_fail(ctx, e, "lfm_batch_posterior_f64: download");
-  r = finish(ctx);
-  if (r) return r;
+  cp.down(mean, f.mean, P.sm * 8);
+  if (var) cp.down(var, f.var, P.sm * 8);
+  if (cov) cp.down(cov, f.cov, P.sc * 8);
+  cp.down(st.data(), f.status, np * sizeof(int));
+  if ((r = cp.landed("lfm_batch_posterior_f64: download"))) return r;
   return batch_status(ctx, st.data(), np, status);
 }
 

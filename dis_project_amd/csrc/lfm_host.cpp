@@ -353,6 +353,14 @@ FitLayout fit_layout(int64_t nhyp, int64_t nprob, int64_t nsteps) {
   return L;
 }
 
+void adam_bias(const lfm_adam* opt, int64_t step0, int64_t nsteps, double* out) {
+  for (int64_t s = 0; s < nsteps; ++s) {
+    const double count = (double)(step0 + s + 1);
+    out[2 * s] = 1.0 - std::pow(opt->b1, count);
+    out[2 * s + 1] = 1.0 - std::pow(opt->b2, count);
+  }
+}
+
 PostPlan plan_small_post(const std::vector<SmallShape>& shapes, int64_t nhyp, const int64_t* m,
                          bool has_dv, bool has_cov) {
   auto rejected = [](PostPlan::Reject why) {

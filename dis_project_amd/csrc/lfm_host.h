@@ -22,10 +22,17 @@
 #include <utility>
 #include <vector>
 
+#include "../../include/lfm.h"  // lfm_adam
 #include "lfm_mid_plan.h"    // the mid-size resident batch's layout and plan (plan_mid)
 #include "lfm_small_plan.h"  // LFM_HD; the small-problem path's layout and plans
 
 namespace lfm {
+
+// optax's bias corrections of the nsteps steps of an on-device fit that follow step0 earlier ones
+// (lfm_batch_fit_f64, lfm_mbatch_fit_f64): out[2 s] = 1 - b1^count, out[2 s + 1] = 1 - b2^count,
+// count = step0 + s + 1, with the host's pow (the restatement's numbers:
+// dis_project_amd/trainer.py adam). out: 2 nsteps doubles.
+void adam_bias(const lfm_adam* opt, int64_t step0, int64_t nsteps, double* out);
 
 // JAX gather semantics for a gene index stored as a float: trunc toward zero, negative wraps
 // by +G, clamp to [0, G - 1] (NaN -> 0).
@@ -261,6 +268,22 @@ LFM_HD inline void sample_uniforms(uint64_t seed, uint64_t s, uint64_t p, double
   *u1 = (double)(a + 1) * 0x1p-53;
   *u2 = (double)(b + 1) * 0x1p-53;
 }
+#if defined(__HIPCC__)
+// The two standard normals of pair p of sample s (elements 2 p and 2 p + 1): Box-Muller on the
+// pair's uniforms. Every generator kernel calls it and keeps its own indexing. The contraction
+// setting is the function's own, whatever its caller's is: a fused multiply-add changes the bits.
+__device__ __forceinline__ void sample_normals(uint64_t seed, uint64_t s, uint64_t p, double* z0,
+                                               double* z1) {
+  #pragma clang fp contract(off)
+  double u1, u2;
+  sample_uniforms(seed, s, p, &u1, &u2);
+  const double rad = sqrt(-2.0 * log(u1));
+  double sn, cs;
+  sincos(6.283185307179586 * u2, &sn, &cs);
+  *z0 = rad * cs;
+  *z1 = rad * sn;
+}
+#endif
 
 // One draw of nsamp joint samples from N(loc, scale), scale n x n (lfm_mvn_sample_f64,
 // lfm_post_sample_f64): scale's lower triangle sits in an Mp x Mp matrix (Mp = round_up(n + 1,

@@ -356,6 +356,14 @@ static_assert(sizeof(SmallArgs) <= 4096, "kernel argument block");
 // [nprob, 2 nprob) in the packed layout, hyperparameters read through SmallProb::dsb / sc)
 int launch_small_grad(lfm_ctx* ctx, SmallArgs* a, const SmallProb* d_probs, const int* d_offs,
                       int nprob, size_t lds, int negative, double* out, double* grad, int* status);
+// The optimiser of an on-device fit (lfm_batch_fit_f64, lfm_mbatch_fit_f64), as both fit kernels
+// take it (fit_update, lfm_bijectors.h): optax.adam's constants, the count of the steps taken
+// before this call, and after_epoch's period (num_steps_per_epoch) and switch (fix_params).
+struct AdamOpt {
+  double lr, b1, b2, eps, eps_root;
+  int64_t step0, spe;
+  int fix;
+};
 // the fit kernel's arguments: every problem's Adam steps on the device (small_fit_kernel)
 struct SmallFitLaunch {
   const SmallProb* probs;
@@ -365,9 +373,9 @@ struct SmallFitLaunch {
   double* history;        // [nsteps][nprob]
   const double* bias;     // [nsteps][2]
   int* status;            // [nprob]: 1 + the first step whose factor failed, or 0
-  double lr, b1, b2, eps, eps_root;
-  int64_t step0, nsteps, spe;
-  int fix, negative;
+  AdamOpt opt;
+  int64_t nsteps;
+  int negative;
 };
 int launch_small_fit(lfm_ctx* ctx, const SmallFitLaunch& f, size_t lds);
 // the MLL of a batch of small problems (plan: plan_small_mll of the batch's SmallDims), the
@@ -416,9 +424,9 @@ struct MidFitArgs {
   double* base;
   int64_t raw, mu, nu, bias, hist;  // doubles from base
   int* first_bad;                   // [nprob]: 1 + the first step whose factor failed, or 0
-  double lr, b1, b2, eps, eps_root;
-  int64_t step0, spe, s;
-  int nprob, fix;
+  AdamOpt opt;
+  int64_t s;
+  int nprob;
 };
 // The predictive call's fourth arena (plan_mid_draw) and its table. The launches on it take a
 // MidArgs whose table is the second one (n = m_p, offsets into this arena) and whose status words

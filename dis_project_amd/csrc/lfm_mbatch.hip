@@ -80,27 +80,6 @@ int mid_launches(lfm_ctx* ctx, const std::vector<MidLaunch>& list, MidCall& c) {
   return LFM_OK;
 }
 
-// A call's copies on ctx->stream, in the order given; after the first that fails the rest do
-// nothing.
-struct MidCopies {
-  lfm_ctx* ctx;
-  hipError_t e = hipSuccess;
-  void up(void* dst, const void* src, size_t n) { copy(dst, src, n, hipMemcpyHostToDevice); }
-  void down(void* dst, const void* src, size_t n) { copy(dst, src, n, hipMemcpyDeviceToHost); }
-  // the first failure as `what`, or LFM_OK
-  int done(const char* what) { return hip_fail(ctx, e, what); }
-  // the end of a call's downloads: done(what), then the stream synchronised
-  int landed(const char* what) {
-    if (int r = done(what)) return r;
-    return finish(ctx);
-  }
-
- private:
-  void copy(void* dst, const void* src, size_t bytes, hipMemcpyKind kind) {
-    if (e == hipSuccess) e = hipMemcpyAsync(dst, src, bytes, kind, ctx->stream);
-  }
-};
-
 // One call: the hyperparameters up, the plan's launches, the results and status words down.
 int mid_call(lfm_ctx* ctx, lfm_mbatch* b, const double* hyp, int negative, bool want_grad,
              double* value, double* grad, int* status) {
@@ -108,7 +87,7 @@ int mid_call(lfm_ctx* ctx, lfm_mbatch* b, const double* hyp, int negative, bool 
   DeviceTenancy tenancy(ctx, false);  // shared
   const MidPlan& P = b->plan;
   const int64_t np = P.nprob, nh = P.nhyp;
-  MidCopies cp{ctx};
+  Copies cp{ctx};
   std::memcpy(b->hbuf, hyp, (size_t)nh * 8);
   cp.up(b->base() + P.hyp, b->hbuf, (size_t)nh * 8);
   if (int r = cp.done("lfm_mbatch: upload")) return r;
@@ -136,7 +115,7 @@ int mid_post_enqueue(lfm_ctx* ctx, lfm_mbatch* b, const MidPostPlan& Q, const do
   MidArena& A = b->arena[lfm_mbatch::POST];
   if (int r = A.grow(ctx, Q.bytes, who)) return r;
   double* pbase = A.doubles();
-  MidCopies cp{ctx};
+  Copies cp{ctx};
   std::memcpy(b->hbuf, hyp, (size_t)nh * 8);
   cp.up(b->base() + P.hyp, b->hbuf, (size_t)nh * 8);
   cp.up(pbase + Q.dadd, diag_add, (size_t)np * 8);
@@ -163,7 +142,7 @@ int mid_post_call(lfm_ctx* ctx, lfm_mbatch* b, const MidPostPlan& Q, const doubl
     return r;
   const int64_t np = Q.nprob;
   const double* pbase = b->arena[lfm_mbatch::POST].doubles();
-  MidCopies cp{ctx};
+  Copies cp{ctx};
   cp.down(mean, pbase + Q.mean, (size_t)Q.sm * 8);
   if (var) cp.down(var, pbase + Q.var, (size_t)Q.sm * 8);
   if (cov) cp.down(cov, pbase + Q.cov, (size_t)Q.sc * 8);
@@ -190,7 +169,7 @@ int mid_draw_call(lfm_ctx* ctx, lfm_mbatch* b, const MidPostPlan& Q, const MidDr
   if (int r = mid_post_enqueue(ctx, b, Q, hyp, diag_vec, diag_add, t, who)) return r;
   const double* pbase = b->arena[lfm_mbatch::POST].doubles();
   double* qbase = A.doubles();
-  MidCopies cp{ctx};
+  Copies cp{ctx};
   cp.up(qbase + D.cadd, cov_add, (size_t)np * 8);
   if (ystar) cp.up(qbase + D.ystar, ystar, (size_t)D.sm * 8);
   if (D.nsamp > 0) cp.up(A.p + D.seeds, seeds, (size_t)np * sizeof(uint64_t));
@@ -243,20 +222,11 @@ int mid_fit_call(lfm_ctx* ctx, lfm_mbatch* b, const MidFitPlan& F, const lfm_ada
   MidArena& A = b->arena[lfm_mbatch::FIT];
   if (int r = A.grow(ctx, F.bytes, "lfm_mbatch_fit_f64")) return r;
   double* fbase = A.doubles();
-  // raw | mu | nu | bias are adjacent in the arena: one upload. optax's bias corrections
-  // 1 - b^count, count = step0 + s + 1, with the host's pow (the restatement's numbers:
-  // dis_project_amd/trainer.py adam)
-  std::vector<double> par((size_t)F.hist, 0.0);
-  std::memcpy(par.data() + F.raw, raw, (size_t)nh * 8);
-  std::memcpy(par.data() + F.mu, mu, (size_t)nh * 8);
-  std::memcpy(par.data() + F.nu, nu, (size_t)nh * 8);
-  for (int64_t s = 0; s < ns; ++s) {
-    const double count = (double)(step0 + s + 1);
-    par[(size_t)(F.bias + 2 * s)] = 1.0 - std::pow(opt->b1, count);
-    par[(size_t)(F.bias + 2 * s + 1)] = 1.0 - std::pow(opt->b2, count);
-  }
-  MidCopies cp{ctx};
-  cp.up(fbase, par.data(), (size_t)F.hist * 8);
+  // raw | mu | nu | bias are adjacent in the arena (raw at its start): one upload
+  FitStaging stage(opt, step0, ns, nh, (size_t)F.raw, (size_t)F.mu, (size_t)F.nu, (size_t)F.bias,
+                   raw, mu, nu);
+  Copies cp{ctx};
+  cp.up(fbase, stage.par.data(), stage.par.size() * 8);
   if (int r = cp.done("lfm_mbatch_fit_f64: upload")) return r;
   MidCall c{};
   c.a = mid_args(b, negative);
@@ -268,30 +238,17 @@ int mid_fit_call(lfm_ctx* ctx, lfm_mbatch* b, const MidFitPlan& F, const lfm_ada
   f.bias = F.bias;
   f.hist = F.hist;
   f.first_bad = reinterpret_cast<int*>(A.p + F.first_bad);
-  f.lr = opt->learning_rate;
-  f.b1 = opt->b1;
-  f.b2 = opt->b2;
-  f.eps = opt->eps;
-  f.eps_root = opt->eps_root;
-  f.step0 = step0;
-  f.spe = opt->num_steps_per_epoch;
+  f.opt = adam_opt(opt, step0);
   f.nprob = (int)np;
-  f.fix = opt->fix_params != 0;
   c.has = MID_HAS_FIT;
   if (int r = mid_launches(ctx, F.launches, c)) return r;
   std::vector<int> st((size_t)np);
-  cp.down(par.data(), fbase, (size_t)F.bias * 8);
+  cp.down(stage.par.data(), fbase, (size_t)F.bias * 8);
   cp.down(history, fbase + F.hist, (size_t)(ns * np) * 8);
   cp.down(st.data(), f.first_bad, (size_t)np * sizeof(int));
   if (int r = cp.landed("lfm_mbatch_fit_f64: download")) return r;
-  // the packed layout's jitter slots pass through unchanged (a static field, model.py:64)
-  std::memcpy(raw, par.data() + F.raw, (size_t)nh * 8);
-  std::memcpy(mu, par.data() + F.mu, (size_t)nh * 8);
-  std::memcpy(nu, par.data() + F.nu, (size_t)nh * 8);
-  return batch_status(ctx, st.data(), np, status,
-                      "Cholesky failed during the fit of a batch problem (its loss "
-                      "and parameters are NaN from that step on, as JAX's)",
-                      true);
+  stage.back(raw, mu, nu);
+  return batch_status(ctx, st.data(), np, status, FIT_FAILED, true);
 }
 
 }  // namespace
@@ -331,7 +288,7 @@ int lfm_mbatch_create(lfm_ctx* ctx, int64_t nprob, const lfm_problem* probs, lfm
   if (e == hipSuccess) e = hipMemsetAsync(b->dmem, 0, P.bytes, ctx->stream);
   // x / y of every problem (adjacent in the arena), then the table; the staging outlives the copies
   std::vector<std::vector<double>> stagings((size_t)nprob);
-  MidCopies cp{ctx, e};
+  Copies cp{ctx, e};
   for (int64_t q = 0; q < nprob; ++q) {
     const MidProb& m = P.probs[q];
     std::vector<double>& s = stagings[q];

@@ -701,10 +701,9 @@ __global__ __launch_bounds__(256) void mid_draw_scale_kernel(MidArgs a, MidDrawA
 }
 
 // The problem's normals Z [64 sb x 64 cb], row r sample sample0 + r: sample_randn_kernel's
-// arithmetic (lfm_sample.hip) on the problem's own seed, so element (r, j) is lfm_randn_f64's
+// sample_normals (lfm_host.h) on the problem's own seed, so element (r, j) is lfm_randn_f64's
 // (seeds[p], sample0 + r, j) bit for bit; the padding rows and columns are generated too.
 __global__ __launch_bounds__(256) void mid_draw_randn_kernel(MidArgs a, MidDrawArgs d) {
-  #pragma clang fp contract(off)
   const int p = blockIdx.x;
   if (a.status[p] != 0) return;
   const MidDrawProb D = d.dp[p];
@@ -714,14 +713,8 @@ __global__ __launch_bounds__(256) void mid_draw_randn_kernel(MidArgs a, MidDrawA
   for (int64_t q = (int64_t)blockIdx.y * 256 + threadIdx.x; q < pairs;
        q += (int64_t)gridDim.y * 256) {
     const int64_t r = q / half, pp = q - r * half;
-    double u1, u2;
-    sample_uniforms(seed, d.sample0 + (uint64_t)r, (uint64_t)pp, &u1, &u2);
-    const double rad = sqrt(-2.0 * log(u1));
-    double sn, cs;
-    sincos(6.283185307179586 * u2, &sn, &cs);
     double2 v;
-    v.x = rad * cs;
-    v.y = rad * sn;
+    sample_normals(seed, d.sample0 + (uint64_t)r, (uint64_t)pp, &v.x, &v.y);
     *reinterpret_cast<double2*>(&Z[r * ld + 2 * pp]) = v;
   }
 }
@@ -766,30 +759,23 @@ __global__ __launch_bounds__(256) void mid_draw_product_kernel(MidArgs a, MidDra
 
 // ------------------------------------------------------------------ the fit's update
 // JaxTrainer.step's tail (trainer.py:105-132) and after_epoch (trainer.py:133-160, 205-210) of
-// every problem after step s's value-and-gradient launches, as small_fit_kernel's update in the
-// same arithmetic order: history[s] = the value; the first-bad-step word latched from the
-// problem's status word (a failed step's value and gradient are NaN, and so are the parameters
-// from there on); per trainable parameter (3 G + 2 of them, any number of passes of 256) the
-// bijector's chain rule, optax.adam in optax's order with the host's bias corrections,
-// after_epoch on the unconstrained leaves, and the next step's constrained value into the first
-// arena's packed hyperparameters, where mid_fill_kernel reads it. s < 0: the constrain alone, of
-// all 3 G + 3 slots (the jitter slot passes through: a static field). A thread touches its own
-// parameter's slots alone; thread 0 the problem's history and first-bad words.
+// every problem after step s's value-and-gradient launches: history[s] = the value; the
+// first-bad-step word latched from the problem's status word (a failed step's value and gradient
+// are NaN, and so are the parameters from there on); per trainable parameter (3 G + 2 of them,
+// any number of passes of 256) small_fit_kernel's step (fit_update, lfm_bijectors.h) with the
+// host's bias corrections, and the next step's constrained value into the first arena's packed
+// hyperparameters, where mid_fill_kernel reads it. s < 0: the constrain alone, of all 3 G + 3
+// slots (the jitter slot passes through: a static field). A thread touches its own parameter's
+// slots alone; thread 0 the problem's history and first-bad words.
 __global__ __launch_bounds__(256) void mid_adam_kernel(MidArgs a, MidFitArgs f) {
-  #pragma clang fp contract(off)
   const int p = blockIdx.x, tid = threadIdx.x;
   const MidProb P = a.probs[p];
   const int G = P.G, nh = 3 * G + 3;
   double* raw = f.base + f.raw;
   double* hyp = a.base;  // MidPlan::hyp = 0
   auto slot = [&](int i) { return i < 3 * G ? P.hv + i : P.hs + (i - 3 * G); };
-  // model.constrain() (trainer.py:103): D, S, B, obs_stddev = softplus, l = 0.5 + 3 sigmoid; the
-  // jitter slot holds the static jitter itself
-  auto constrain = [&](int i, double x) {
-    return i == 3 * G ? 0.5 + 3.0 * sigmoid_d(x) : i == 3 * G + 2 ? x : softplus_d(x);
-  };
   if (f.s < 0) {
-    for (int i = tid; i < nh; i += 256) hyp[slot(i)] = constrain(i, raw[slot(i)]);
+    for (int i = tid; i < nh; i += 256) hyp[slot(i)] = fit_constrain(i, G, raw[slot(i)]);
     if (tid == 0) f.first_bad[p] = 0;
     return;
   }
@@ -804,24 +790,11 @@ __global__ __launch_bounds__(256) void mid_adam_kernel(MidArgs a, MidFitArgs f) 
   const double c1 = f.base[f.bias + 2 * s], c2 = f.base[f.bias + 2 * s + 1];
   for (int i = tid; i < nh - 1; i += 256) {
     const int64_t gi = slot(i);
-    const double x = raw[gi], g = grad[gi];
-    const double sg = sigmoid_d(x);
-    const double gr = i == 3 * G ? g * 3.0 * sg * (1.0 - sg) : g * sg;
-    const double mu = f.b1 * mom1[gi] + (1.0 - f.b1) * gr;
-    const double nu = f.b2 * mom2[gi] + (1.0 - f.b2) * (gr * gr);
-    // optax's order: scale_by_adam's mu_hat / (sqrt(nu_hat + eps_root) + eps), then
-    // scale(-learning_rate)
-    const double u = (mu / c1) / (sqrt(nu / c2 + f.eps_root) + f.eps);
-    const double upd = -f.lr * u;
-    mom1[gi] = mu;
-    mom2[gi] = nu;
-    double xn = x + upd;
-    if (f.fix && (f.step0 + s) % f.spe == 0 && G > 3) {
-      if (i == G + 3) xn = 1.0;  // true_s[3]
-      if (i == 3) xn = 0.8;      // true_d[3]
-    }
-    raw[gi] = xn;
-    hyp[gi] = constrain(i, xn);
+    const FitSlot u = fit_update(f.opt, i, G, s, raw[gi], grad[gi], mom1[gi], mom2[gi], c1, c2);
+    mom1[gi] = u.mu;
+    mom2[gi] = u.nu;
+    raw[gi] = u.x;
+    hyp[gi] = fit_constrain(i, G, u.x);
   }
 }
 

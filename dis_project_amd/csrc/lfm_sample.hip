@@ -29,19 +29,12 @@ namespace {
 __global__ __launch_bounds__(256) void sample_randn_kernel(double* __restrict__ Z, int64_t ld,
                                                            int64_t pairs, uint64_t seed,
                                                            uint64_t s0) {
-  #pragma clang fp contract(off)
   const int64_t half = ld >> 1;
   for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < pairs;
        q += (int64_t)gridDim.x * blockDim.x) {
     const int64_t r = q / half, p = q - r * half;
-    double u1, u2;
-    sample_uniforms(seed, s0 + (uint64_t)r, (uint64_t)p, &u1, &u2);
-    const double rad = sqrt(-2.0 * log(u1));
-    double sn, cs;
-    sincos(6.283185307179586 * u2, &sn, &cs);
     double2 v;
-    v.x = rad * cs;
-    v.y = rad * sn;
+    sample_normals(seed, s0 + (uint64_t)r, (uint64_t)p, &v.x, &v.y);
     *reinterpret_cast<double2*>(&Z[r * ld + 2 * p]) = v;
   }
 }

@@ -1277,20 +1277,13 @@ __global__ __launch_bounds__(256) void small_grad_kernel_args(SmallArgs a) {
 // JaxTrainer.fit (trainer.py:162-228) of every problem of a batch, each workgroup stepping its
 // problem through nsteps Adam steps without leaving the kernel. Per step, as trainer.py:105-132
 // and the host restatement (dis_project_amd/trainer.py, which the tests hold it to):
-//   constrain (model.py:66-121): D, S, B, obs_stddev = softplus(raw), l = 0.5 + 3 sigmoid(raw)
+//   constrain (fit_constrain, lfm_bijectors.h)
 //   value and gradient (small_value_grad), history[s] = the value
-//   chain rule: g_raw = g softplus'(raw) = g sigmoid(raw); l: g 3 sigmoid (1 - sigmoid)
-//   optax.adam: mu = b1 mu + (1 - b1) g, nu = b2 nu + (1 - b2) g^2,
-//               raw += -lr ((mu / c1) / (sqrt(nu / c2 + eps_root) + eps))  (optax's order)
-//     with c1 = 1 - b1^count, c2 = 1 - b2^count from the host (bias[2 s], bias[2 s + 1]: the
-//     host's pow, as the restatement's)
-//   after_epoch (trainer.py:133-160, 205-210): every num_steps_per_epoch steps (step 0
-//     included), if fix_params, raw true_s[3] = 1.0 and raw true_d[3] = 0.8 (the unconstrained
-//     leaves: the reference's quirk; no-op for G <= 3, as JAX drops out-of-bounds updates)
-// The jitter slot holds the static jitter (constrained) and is never updated. softplus_d and
-// sigmoid_d: lfm_bijectors.h.
+//   the chain rule, optax.adam and after_epoch of every trainable parameter (fit_update,
+//     lfm_bijectors.h) with c1 = 1 - b1^count, c2 = 1 - b2^count from the host (bias[2 s],
+//     bias[2 s + 1]: adam_bias, lfm_host.cpp)
+// The jitter slot holds the static jitter (constrained) and is never updated.
 __global__ __launch_bounds__(256) void small_fit_kernel(SmallFitLaunch a) {
-  #pragma clang fp contract(off)
   extern __shared__ __attribute__((aligned(16))) double sm[];
   const int b = blockIdx.x, tid = threadIdx.x;
   const SmallProb P = a.probs[b];
@@ -1306,42 +1299,30 @@ __global__ __launch_bounds__(256) void small_fit_kernel(SmallFitLaunch a) {
   }
   small_stage(P, m);
   __syncthreads();
-  // model.constrain() (trainer.py:103): D, S, B, obs_stddev = softplus, l = 0.5 + 3 sigmoid; the
-  // jitter slot holds the static jitter itself
-  auto constrain = [&](int i, double x) {
-    return i == 3 * G ? 0.5 + 3.0 * sigmoid_d(x) : i == 3 * G + 2 ? x : softplus_d(x);
-  };
-  for (int i = tid; i < nh; i += 256) m.hyp[i] = constrain(i, m.raw[i]);
+  for (int i = tid; i < nh; i += 256) m.hyp[i] = fit_constrain(i, G, m.raw[i]);
   __syncthreads();
   int first_bad = 0;
+  // The loop's scalars read from the arguments once: left to itself the compiler re-reads the
+  // argument block inside the step loop, several scalar loads and their waits a step.
+  AdamOpt opt = a.opt;
+  int negative = a.negative;
+  asm volatile("" : "+s"(opt.lr), "+s"(opt.b1), "+s"(opt.b2), "+s"(opt.eps), "+s"(opt.eps_root),
+                    "+s"(opt.step0), "+s"(opt.spe), "+s"(opt.fix), "+s"(negative));
   for (int64_t s = 0; s < a.nsteps; ++s) {
     int bad;
-    const double v = small_value_grad_step(n, G, P.T, P.dt, a.negative, &bad);
+    const double v = small_value_grad_step(n, G, P.T, P.dt, negative, &bad);
     if (bad && !first_bad) first_bad = (int)s + 1;
     if (tid == 0) a.history[s * a.nprob + b] = v;
     // the update, after_epoch on the unconstrained leaves, and the next step's constrained model,
     // each parameter by its own thread (one barrier a step); 3G + 2 > 256 parameters (G >= 85)
     // take a second pass
     auto update = [&](int i) {
-      const double x = m.raw[i], g = m.gout[i];
-      const double sg = sigmoid_d(x);
-      const double gr = i == 3 * G ? g * 3.0 * sg * (1.0 - sg) : g * sg;
-      const double c1 = a.bias[2 * s], c2 = a.bias[2 * s + 1];
-      const double mu = a.b1 * m.mu[i] + (1.0 - a.b1) * gr;
-      const double nu = a.b2 * m.nu[i] + (1.0 - a.b2) * (gr * gr);
-      // optax's order: scale_by_adam's mu_hat / (sqrt(nu_hat + eps_root) + eps), then
-      // scale(-learning_rate)
-      const double u = (mu / c1) / (sqrt(nu / c2 + a.eps_root) + a.eps);
-      const double upd = -a.lr * u;
-      m.mu[i] = mu;
-      m.nu[i] = nu;
-      double xn = x + upd;
-      if (a.fix && (a.step0 + s) % a.spe == 0 && G > 3) {
-        if (i == G + 3) xn = 1.0;  // true_s[3]
-        if (i == 3) xn = 0.8;      // true_d[3]
-      }
-      m.raw[i] = xn;
-      m.hyp[i] = constrain(i, xn);
+      const FitSlot u = fit_update(opt, i, G, s, m.raw[i], m.gout[i], m.mu[i], m.nu[i],
+                                   a.bias[2 * s], a.bias[2 * s + 1]);
+      m.mu[i] = u.mu;
+      m.nu[i] = u.nu;
+      m.raw[i] = u.x;
+      m.hyp[i] = fit_constrain(i, G, u.x);
     };
     if (tid < nh - 1) update(tid);
     if (nh - 1 > 256 && tid + 256 < nh - 1) update(tid + 256);

@@ -152,10 +152,13 @@ _chain = itertools.chain.from_iterable
 
 
 def unpack_grads(packed: np.ndarray, genes) -> list:
-    """A packed gradient (lfm_batch_mll_grad_f64's layout: dD dS dB of each problem, then d l,
-    d obs_stddev, 0 of each) as one ``CustomConjMLL.value_and_grad`` dict per problem."""
+    """A packed array (one slot per hyperparameter: the true_d / true_s / true_b slots of each
+    problem, then each problem's l, obs_stddev and jitter slots) as one dict per problem, the
+    jitter slot dropped: a gradient (lfm_batch_mll_grad_f64's layout: dD dS dB, then d l,
+    d obs_stddev, 0) as ``CustomConjMLL.value_and_grad``'s dicts, or unconstrained parameters
+    (``trainer.pack_raw``'s inverse, ``trainer.unpack_raw``)."""
     out, off = [], 0
-    nvec = 3 * sum(genes)
+    nvec = 3 * int(sum(genes))
     for p, G in enumerate(genes):
         v = packed[off:off + 3 * G]
         sc = packed[nvec + 3 * p: nvec + 3 * p + 3]
@@ -165,29 +168,28 @@ def unpack_grads(packed: np.ndarray, genes) -> list:
     return out
 
 
-class BatchEvaluator:
-    """MLL evaluations of many small problems (n <= 128 each: the C5 ablations) in one batched
-    launch per call, on a device-resident batch (``lfm_batch_create``: every problem's x / y in
-    HBM once). A call packs every model's current hyperparameters into one array
-    (``lfm_batch_mll_f64``'s layout: the true_d / true_s / true_b vectors of each problem, then
-    each problem's l, obs_stddev, jitter), which the kernel reads straight from pinned host
-    memory: one memcpy, one launch, one synchronise. Not PD -> NaN."""
+class _ResidentBatch:
+    """What the evaluators of a device-resident batch share (``PREFIX`` names the entry points:
+    ``lfm_batch_*`` / ``lfm_mbatch_*``, whose arguments are the same word for word): the
+    ``LfmProblem`` table over the datasets' x / y, the handle registered per gene layout, the
+    packed hyperparameter buffer (``lfm_batch_mll_f64``'s layout: the true_d / true_s / true_b
+    vectors of each problem, then each problem's l, obs_stddev, jitter) and the calls on it. A
+    subclass checks its datasets in ``_xy`` and a new gene layout in ``_new_layout``; ``_VEC``
+    gives one model's three vectors as ``_pack`` concatenates them."""
 
-    def __init__(self, ctx: _lib.Context, datasets, negative: bool = False):
+    PREFIX = None
+    _VEC = _VECS
+
+    def __init__(self, ctx, datasets, negative: bool = False):
         self.ctx, self.negative = ctx, bool(negative)
         self.datasets = list(datasets)  # held: the cache key of gpu_evaluator compares them
         self.batch = None
         probs = (_lib.LfmProblem * len(self.datasets))()
         keep = []
         for i, d in enumerate(self.datasets):
-            x = np.ascontiguousarray(d.X, dtype=np.float64).reshape(-1, 3)
-            y = np.ascontiguousarray(d.y, dtype=np.float64).reshape(-1)
-            if y.size != x.shape[0]:
-                raise ValueError("dataset x / y lengths differ")
+            x, y = self._xy(i, d)
             keep.append((x, y))
-            probs[i].x = x.ctypes.data
-            probs[i].y = y.ctypes.data
-            probs[i].n = x.shape[0]
+            probs[i].x, probs[i].y, probs[i].n = x.ctypes.data, y.ctypes.data, x.shape[0]
         self._probs, self._keep = probs, keep  # x / y kept: a new gene layout re-registers
         self._genes = None
         self.status = np.zeros(len(self.datasets), dtype=np.int32)
@@ -195,42 +197,108 @@ class BatchEvaluator:
         # raw addresses of the call's own buffers, taken once (``.ctypes.data`` costs ~1 µs each)
         self._st_ptr, self._out_ptr = self.status.ctypes.data, self._out.ctypes.data
 
-    def _create(self, genes):
-        for i, g in enumerate(genes):
-            self._probs[i].hyp.num_genes = g
-        h = _lib.c_void_p()
-        self.ctx.check(self.ctx.lib.lfm_batch_create(self.ctx.handle, len(genes), self._probs,
-                                                     _lib.ctypes.byref(h)))
-        self.batch, self._genes = h, genes
-        nvec = 3 * sum(genes)
-        self._buf = np.empty(nvec + 3 * len(genes))
-        self._vec, self._sc = self._buf[:nvec], self._buf[nvec:]
-        self._buf_ptr = self._buf.ctypes.data
-
-    def registered(self, genes) -> int:
-        """The batch registered for this gene layout (re-registered if it changed): its handle."""
+    def registered(self, genes):
+        """The handle registered for this gene layout (re-registered if it changed)."""
         genes = tuple(int(g) for g in genes)
         if genes != self._genes:
-            if self.batch is not None:
-                self.close()
-            self._create(genes)
+            self._new_layout(genes)
+            self.close()
+            for i, g in enumerate(genes):
+                self._probs[i].hyp.num_genes = g
+            h = _lib.c_void_p()
+            lib, pre = self.ctx.lib, self.PREFIX
+            self.ctx.check(getattr(lib, pre + "_create")(self.ctx.handle, len(genes), self._probs,
+                                                         _lib.ctypes.byref(h)))
+            self.batch, self._genes = h, genes
+            # the calls' entry points, looked up once (a stand-in library may lack some)
+            self._mll, self._mll_grad, self._fit = (
+                getattr(lib, pre + s, None) for s in ("_mll_f64", "_mll_grad_f64", "_fit_f64"))
+            nvec = 3 * sum(genes)
+            self._buf = np.empty(nvec + 3 * len(genes))
+            self._vec, self._sc = self._buf[:nvec], self._buf[nvec:]
+            self._buf_ptr = self._buf.ctypes.data
         return self.batch
+
+    def _new_layout(self, genes):
+        """Before ``genes`` (a tuple) is registered: a subclass's checks of it."""
 
     def _pack(self, models):
         models = list(models)
         if len(models) != len(self.datasets):
             raise ValueError("one model per registered dataset")
         self.registered(map(_NUM_GENES, models))
-        np.concatenate(list(_chain(map(_VECS, models))), out=self._vec)
+        np.concatenate(list(_chain(map(self._VEC, models))), out=self._vec)
         self._sc[:] = list(_chain(map(_SCALARS, models)))
         return models
 
     def __call__(self, models) -> np.ndarray:
         self._pack(models)
-        rc = self.ctx.lib.lfm_batch_mll_f64(self.ctx.handle, self.batch, self._buf_ptr,
-                                            int(self.negative), self._out_ptr, self._st_ptr)
+        rc = self._mll(self.ctx.handle, self.batch, self._buf_ptr, int(self.negative),
+                       self._out_ptr, self._st_ptr)
         self.ctx.check(rc, allow_not_pd=True)
         return self._out.copy()
+
+    def value_and_grad(self, models):
+        """Every problem's value and gradient (constrained parameters, as
+        ``CustomConjMLL.value_and_grad``) in one call (``lfm_batch_mll_grad_f64``: ONE launch,
+        n <= 127 per problem; ``lfm_mbatch_mll_grad_f64``). Returns (values [P], [grads dict per
+        problem]); NaN where not PD."""
+        self._pack(models)
+        grad = np.empty(self._buf.size)
+        rc = self._mll_grad(self.ctx.handle, self.batch, self._buf_ptr, int(self.negative),
+                            self._out_ptr, _lib.dptr(grad), self._st_ptr)
+        self.ctx.check(rc, allow_not_pd=True)
+        return self._out.copy(), unpack_grads(grad, self._genes)
+
+    def fit_packed(self, raw, mu, nu, optim, fix_params, num_steps_per_epoch, step0, nsteps):
+        """``nsteps`` training steps of every problem on the device in one call
+        (``lfm_batch_fit_f64`` / ``lfm_mbatch_fit_f64``), no host round trip between steps.
+        ``raw`` (the unconstrained parameters, ``trainer.pack_raw``), ``mu`` and ``nu`` (Adam's
+        moments) are float64 arrays of the registered layout (``registered(genes)``) and are
+        updated in place; ``step0`` is the number of steps already taken. Returns (history
+        [nsteps, P], status [P]: 0, or 1 + the first step of this call whose factorisation
+        failed — NaN from there on)."""
+        if self.batch is None:
+            raise ValueError("no registered batch: call registered(genes) first")
+        for a in (raw, mu, nu):
+            if not isinstance(a, np.ndarray) or a.dtype != np.float64 or \
+                    a.size != self._buf.size or not a.flags.c_contiguous:
+                raise ValueError("raw / mu / nu: packed float64 arrays of this batch's layout")
+        nsteps = int(nsteps)
+        hist = np.empty((max(nsteps, 0), len(self.datasets)))
+        st = np.zeros(len(self.datasets), np.int32)
+        opt = _lib.LfmAdam(optim.learning_rate, optim.b1, optim.b2, optim.eps, optim.eps_root,
+                           int(num_steps_per_epoch), int(bool(fix_params)))
+        rc = self._fit(self.ctx.handle, self.batch, _lib.ctypes.byref(opt), int(self.negative),
+                       int(step0), nsteps, _lib.dptr(raw), _lib.dptr(mu), _lib.dptr(nu),
+                       _lib.dptr(hist), _lib.dptr(st))
+        self.ctx.check(rc, allow_not_pd=True)
+        return hist, st
+
+    def close(self):
+        if self.batch is not None:
+            getattr(self.ctx.lib, self.PREFIX + "_destroy")(self.batch)
+            self.batch = None
+            self._genes = None
+
+
+class BatchEvaluator(_ResidentBatch):
+    """MLL evaluations of many small problems (n <= 128 each: the C5 ablations) in one batched
+    launch per call, on a device-resident batch (``lfm_batch_create``: every problem's x / y in
+    HBM once). A call packs every model's current hyperparameters into one array
+    (``lfm_batch_mll_f64``'s layout), which the kernel reads straight from pinned host memory:
+    one memcpy, one launch, one synchronise. Not PD -> NaN. ``fit_packed`` runs a whole Adam
+    loop of every problem inside one launch (``lfm_batch_fit_f64``)."""
+
+    PREFIX = "lfm_batch"
+
+    @staticmethod
+    def _xy(i, d):
+        x = np.ascontiguousarray(d.X, dtype=np.float64).reshape(-1, 3)
+        y = np.ascontiguousarray(d.y, dtype=np.float64).reshape(-1)
+        if y.size != x.shape[0]:
+            raise ValueError("dataset x / y lengths differ")
+        return x, y
 
     def pack(self, models) -> np.ndarray:
         """The models' hyperparameters in the library's packed layout (a copy; the batch is
@@ -276,26 +344,8 @@ class BatchEvaluator:
         self.ctx.check(rc, allow_not_pd=True)
         return recv
 
-    def value_and_grad(self, models):
-        """Every problem's value and gradient (constrained parameters, as
-        ``CustomConjMLL.value_and_grad``) in ONE launch (``lfm_batch_mll_grad_f64``; n <= 127 per
-        problem). Returns (values [P], [grads dict per problem]); NaN where not PD."""
-        models = self._pack(models)
-        grad = np.empty(self._buf.size)
-        rc = self.ctx.lib.lfm_batch_mll_grad_f64(self.ctx.handle, self.batch, self._buf_ptr,
-                                                 int(self.negative), self._out_ptr,
-                                                 _lib.dptr(grad), self._st_ptr)
-        self.ctx.check(rc, allow_not_pd=True)
-        return self._out.copy(), unpack_grads(grad, self._genes)
 
-    def close(self):
-        if self.batch is not None:
-            self.ctx.lib.lfm_batch_destroy(self.batch)
-            self.batch = None
-            self._genes = None
-
-
-class MidBatchEvaluator:
+class MidBatchEvaluator(_ResidentBatch):
     """``BatchEvaluator`` for problems of any size 1 <= n <= 1024 (``lfm_mbatch_*``): pooled
     replicates, larger time grids — the same independent (model, dataset) problems once they
     outgrow one workgroup each. Every problem's x / y go to HBM once; a call packs the models'
@@ -306,37 +356,33 @@ class MidBatchEvaluator:
     (``lfm_mbatch_fit_f64``). ``ctx`` may be None: the calling thread's context is then asked for
     at the first evaluation, after the shapes and ``num_genes`` have been checked."""
 
+    PREFIX = "lfm_mbatch"
     MAX_N = 1024  # LFM_MID_MAX_N
 
     def __init__(self, ctx, datasets, negative: bool = False):
-        self.ctx, self.negative = ctx, bool(negative)
-        self.datasets = list(datasets)
-        self.batch = None
-        if not self.datasets:
+        datasets = list(datasets)
+        if not datasets:
             raise ValueError("at least one dataset")
-        probs = (_lib.LfmProblem * len(self.datasets))()
-        keep = []
-        for i, d in enumerate(self.datasets):
-            x = np.ascontiguousarray(d.X, dtype=np.float64)
-            y = np.ascontiguousarray(d.y, dtype=np.float64).reshape(-1)
-            if x.ndim != 2 or x.shape[1] != 3:
-                raise ValueError(f"dataset {i}: x must be [n, 3]")
-            if y.size != x.shape[0]:
-                raise ValueError(f"dataset {i}: x has {x.shape[0]} rows, y {y.size}")
-            if not 1 <= x.shape[0] <= self.MAX_N:
-                raise ValueError(f"dataset {i}: n = {x.shape[0]} outside [1, {self.MAX_N}]")
-            keep.append((x, y))
-            probs[i].x, probs[i].y, probs[i].n = x.ctypes.data, y.ctypes.data, x.shape[0]
-        self._probs, self._keep = probs, keep
-        self._genes = None
-        self.status = np.zeros(len(self.datasets), dtype=np.int32)
-        self._out = np.empty(len(self.datasets))
+        super().__init__(ctx, datasets, negative)
 
-    def registered(self, genes):
-        """The handle registered for this gene layout (re-registered if it changed)."""
-        genes = tuple(int(g) for g in genes)
-        if genes == self._genes:
-            return self.batch
+    def _xy(self, i, d):
+        x = np.ascontiguousarray(d.X, dtype=np.float64)
+        y = np.ascontiguousarray(d.y, dtype=np.float64).reshape(-1)
+        if x.ndim != 2 or x.shape[1] != 3:
+            raise ValueError(f"dataset {i}: x must be [n, 3]")
+        if y.size != x.shape[0]:
+            raise ValueError(f"dataset {i}: x has {x.shape[0]} rows, y {y.size}")
+        if not 1 <= x.shape[0] <= self.MAX_N:
+            raise ValueError(f"dataset {i}: n = {x.shape[0]} outside [1, {self.MAX_N}]")
+        return x, y
+
+    @staticmethod
+    def _VEC(model) -> list:
+        """A model's vectors, each as a flat float64 array (lists and scalars are taken too)."""
+        return [np.asarray(v, np.float64).reshape(-1) for v in _VECS(model)]
+
+    def _new_layout(self, genes):
+        """The layout against the datasets; then, with ``ctx=None``, the thread's context."""
         if len(genes) != len(self.datasets):
             raise ValueError("one model per registered dataset")
         for i, (g, (x, _)) in enumerate(zip(genes, self._keep)):
@@ -345,78 +391,6 @@ class MidBatchEvaluator:
                                  f"num_genes = {g}")
         if self.ctx is None:
             self.ctx = _lib.get_context()
-        self.close()
-        for i, g in enumerate(genes):
-            self._probs[i].hyp.num_genes = g
-        h = _lib.c_void_p()
-        self.ctx.check(self.ctx.lib.lfm_mbatch_create(self.ctx.handle, len(genes), self._probs,
-                                                      _lib.ctypes.byref(h)))
-        self.batch, self._genes = h, genes
-        nvec = 3 * sum(genes)
-        self._buf = np.empty(nvec + 3 * len(genes))
-        self._vec, self._sc = self._buf[:nvec], self._buf[nvec:]
-        return self.batch
-
-    def _pack(self, models):
-        models = list(models)
-        if len(models) != len(self.datasets):
-            raise ValueError("one model per registered dataset")
-        self.registered(map(_NUM_GENES, models))
-        np.concatenate([np.asarray(v, np.float64).reshape(-1)
-                        for v in _chain(map(_VECS, models))], out=self._vec)
-        self._sc[:] = list(_chain(map(_SCALARS, models)))
-        return models
-
-    def __call__(self, models) -> np.ndarray:
-        self._pack(models)
-        rc = self.ctx.lib.lfm_mbatch_mll_f64(self.ctx.handle, self.batch, _lib.dptr(self._buf),
-                                             int(self.negative), _lib.dptr(self._out),
-                                             _lib.dptr(self.status))
-        self.ctx.check(rc, allow_not_pd=True)
-        return self._out.copy()
-
-    def value_and_grad(self, models):
-        """(values [P], [grad dict per problem]) as ``BatchEvaluator.value_and_grad``
-        (``lfm_mbatch_mll_grad_f64``); NaN where not PD."""
-        self._pack(models)
-        grad = np.empty(self._buf.size)
-        rc = self.ctx.lib.lfm_mbatch_mll_grad_f64(self.ctx.handle, self.batch,
-                                                  _lib.dptr(self._buf), int(self.negative),
-                                                  _lib.dptr(self._out), _lib.dptr(grad),
-                                                  _lib.dptr(self.status))
-        self.ctx.check(rc, allow_not_pd=True)
-        return self._out.copy(), unpack_grads(grad, self._genes)
-
-    def fit_packed(self, raw, mu, nu, optim, fix_params, num_steps_per_epoch, step0, nsteps):
-        """``nsteps`` training steps of every problem on the device in one call
-        (``lfm_mbatch_fit_f64``), no host round trip between steps. ``raw`` (the unconstrained
-        parameters, ``trainer.pack_raw``), ``mu`` and ``nu`` (Adam's moments) are float64 arrays
-        of the registered layout (``registered(genes)``) and are updated in place; ``step0`` is
-        the number of steps already taken. Returns (history [nsteps, P], status [P]: 0, or
-        1 + the first step of this call whose factorisation failed — NaN from there on)."""
-        if self.batch is None:
-            raise ValueError("no registered batch: call registered(genes) first")
-        for a in (raw, mu, nu):
-            if not isinstance(a, np.ndarray) or a.dtype != np.float64 or \
-                    a.size != self._buf.size or not a.flags.c_contiguous:
-                raise ValueError("raw / mu / nu: packed float64 arrays of this batch's layout")
-        nsteps = int(nsteps)
-        hist = np.empty((max(nsteps, 0), len(self.datasets)))
-        st = np.zeros(len(self.datasets), np.int32)
-        opt = _lib.LfmAdam(optim.learning_rate, optim.b1, optim.b2, optim.eps, optim.eps_root,
-                           int(num_steps_per_epoch), int(bool(fix_params)))
-        rc = self.ctx.lib.lfm_mbatch_fit_f64(self.ctx.handle, self.batch, _lib.ctypes.byref(opt),
-                                             int(self.negative), int(step0), nsteps,
-                                             _lib.dptr(raw), _lib.dptr(mu), _lib.dptr(nu),
-                                             _lib.dptr(hist), _lib.dptr(st))
-        self.ctx.check(rc, allow_not_pd=True)
-        return hist, st
-
-    def close(self):
-        if self.batch is not None:
-            self.ctx.lib.lfm_mbatch_destroy(self.batch)
-            self.batch = None
-            self._genes = None
 
 
 def workload(kind: str, genes: int = 64, timepoints: int = 256, restarts: int = 32,

@@ -75,7 +75,38 @@ def unpack_outputs(m, mean, var=None, cov=None):
 class _Assembly:
     """The ``GaussianDistribution``s and marginals of ``ExactLFM.latent_predict`` /
     ``multi_gene_predict`` from a batched posterior: ``_posterior(models, test_inputs, diag_add,
-    want_cov)`` returns per problem (mean, var, cov or None)."""
+    want_cov)`` returns per problem (mean, var, cov or None). ``_ev`` is the evaluator that
+    holds the registered batch (``farm.BatchEvaluator`` / ``farm.MidBatchEvaluator``), ``ENTRY``
+    the posterior entry point on its handle and ``MAX_M`` that entry point's bound on a
+    problem's test rows, if it has one (``TOO_MANY_ROWS``: the message past it)."""
+
+    ENTRY = None
+    MAX_M = TOO_MANY_ROWS = None
+
+    def __len__(self):
+        return len(self._ev.datasets)
+
+    def _posterior(self, models, test_inputs, diag_add, want_cov):
+        models = list(models)
+        if len(models) != len(self):
+            raise ValueError("one model per registered problem")
+        genes = [int(mm.num_genes) for mm in models]
+        t, m = pack_test_inputs(test_inputs, genes)
+        if self.MAX_M is not None and np.any(m > self.MAX_M):
+            raise ValueError(self.TOO_MANY_ROWS)
+        self._ev._pack(models)  # the packed hyperparameters; registers this gene layout
+        self.ctx = self.ctx or self._ev.ctx
+        dadd = as_f64(diag_add).reshape(-1)
+        mean = np.empty(int(m.sum()))
+        var = np.empty_like(mean)
+        cov = np.empty(int((m * m).sum())) if want_cov else None
+        self.status = np.zeros(len(models), np.int32)
+        rc = getattr(self.ctx.lib, self.ENTRY)(
+            self.ctx.handle, self._ev.batch, dptr(self._ev._buf), dptr(self.variances),
+            dptr(dadd), dptr(m), dptr(t), dptr(mean), dptr(var),
+            dptr(cov) if want_cov else None, dptr(self.status))
+        self.ctx.check(rc, allow_not_pd=True)
+        return unpack_outputs(m, mean, var, cov)
 
     def latent_predict(self, models, test_inputs):
         """model.py:420-465 per problem: S = K(x,x) + diag(variances) + jitter I;
@@ -139,6 +170,8 @@ class BatchPredictor(_Assembly):
     problem, e.g. ``BatchTrainer.fit``'s) are read at every call. ``status`` holds the last
     call's per-problem codes (LFM_E_NOT_PD: that problem's outputs are NaN, as under JAX)."""
 
+    ENTRY = "lfm_batch_posterior_f64"
+
     def __init__(self, train_datas, ctx=None):
         from .farm import BatchEvaluator
 
@@ -146,28 +179,6 @@ class BatchPredictor(_Assembly):
         datasets, self.variances = _training_sets(train_datas)
         self._ev = BatchEvaluator(self.ctx, datasets)
         self.status = np.zeros(len(datasets), np.int32)
-
-    def __len__(self):
-        return len(self._ev.datasets)
-
-    def _posterior(self, models, test_inputs, diag_add, want_cov):
-        models = list(models)
-        if len(models) != len(self):
-            raise ValueError("one model per registered problem")
-        genes = [int(mm.num_genes) for mm in models]
-        t, m = pack_test_inputs(test_inputs, genes)
-        hyp = self._ev.pack(models)  # lfm_batch_mll_f64's layout; registers this gene layout
-        batch = self._ev.batch
-        dadd = as_f64(diag_add).reshape(-1)
-        mean = np.empty(int(m.sum()))
-        var = np.empty_like(mean)
-        cov = np.empty(int((m * m).sum())) if want_cov else None
-        self.status = np.zeros(len(models), np.int32)
-        rc = self.ctx.lib.lfm_batch_posterior_f64(
-            self.ctx.handle, batch, dptr(hyp), dptr(self.variances), dptr(dadd), dptr(m), dptr(t),
-            dptr(mean), dptr(var), dptr(cov) if want_cov else None, dptr(self.status))
-        self.ctx.check(rc, allow_not_pd=True)
-        return unpack_outputs(m, mean, var, cov)
 
     def close(self):
         self._ev.close()
@@ -184,7 +195,10 @@ class MidBatchPredictor(_Assembly):
     ``log_prob`` draw from, and score held-out values under, every problem's predictive
     distribution on the same handle (``lfm_mbatch_predictive_f64``, at most 1024 test rows each)."""
 
+    ENTRY = "lfm_mbatch_posterior_f64"
     MAX_M = 4096  # LFM_MID_MAX_M
+    TOO_MANY_ROWS = (f"at most {MAX_M} test rows per problem (LFM_MID_MAX_M); use Posterior for "
+                     "more on one model")
 
     def __init__(self, train_datas, ctx=None, evaluator=None):
         from .farm import MidBatchEvaluator
@@ -205,32 +219,6 @@ class MidBatchPredictor(_Assembly):
         self._ev = evaluator
         self.ctx = ctx or evaluator.ctx
         self.status = np.zeros(len(datasets), np.int32)
-
-    def __len__(self):
-        return len(self._ev.datasets)
-
-    def _posterior(self, models, test_inputs, diag_add, want_cov):
-        models = list(models)
-        if len(models) != len(self):
-            raise ValueError("one model per registered problem")
-        genes = [int(mm.num_genes) for mm in models]
-        t, m = pack_test_inputs(test_inputs, genes)
-        if np.any(m > self.MAX_M):
-            raise ValueError(f"at most {self.MAX_M} test rows per problem (LFM_MID_MAX_M); use "
-                             "Posterior for more on one model")
-        self._ev._pack(models)  # the packed hyperparameters; registers this gene layout
-        self.ctx = self.ctx or self._ev.ctx
-        dadd = as_f64(diag_add).reshape(-1)
-        mean = np.empty(int(m.sum()))
-        var = np.empty_like(mean)
-        cov = np.empty(int((m * m).sum())) if want_cov else None
-        self.status = np.zeros(len(models), np.int32)
-        rc = self.ctx.lib.lfm_mbatch_posterior_f64(
-            self.ctx.handle, self._ev.batch, dptr(self._ev._buf), dptr(self.variances),
-            dptr(dadd), dptr(m), dptr(t), dptr(mean), dptr(var),
-            dptr(cov) if want_cov else None, dptr(self.status))
-        self.ctx.check(rc, allow_not_pd=True)
-        return unpack_outputs(m, mean, var, cov)
 
     MAX_DRAW_M = 1024       # LFM_MID_MAX_N: the covariance goes through the mid factorisation
     MAX_DRAW_SAMPLES = 65536  # per call; sample0 continues a draw

@@ -34,6 +34,7 @@ from typing import Any, Sequence
 import numpy as np
 
 from .dataset import Dataset
+from .farm import unpack_grads as unpack_raw  # noqa: F401 — pack_raw's inverse (jitter dropped)
 from .model import ExactLFM
 
 PARAMS = ("true_d", "true_s", "true_b", "l", "obs_stddev")
@@ -211,17 +212,31 @@ def pack_raw(raws: Sequence[dict], jitters: Sequence[float]) -> np.ndarray:
     return np.concatenate(vec + [np.asarray(sc, np.float64).reshape(-1)])
 
 
-def unpack_raw(packed: np.ndarray, genes: Sequence[int]) -> list:
-    """pack_raw's inverse (the jitter slots dropped)."""
-    out, off = [], 0
-    nvec = 3 * int(sum(genes))
-    for p, G in enumerate(genes):
-        v = packed[off:off + 3 * G]
-        sc = packed[nvec + 3 * p: nvec + 3 * p + 3]
-        out.append({"true_d": v[:G].copy(), "true_s": v[G:2 * G].copy(), "true_b": v[2 * G:].copy(),
-                    "l": float(sc[0]), "obs_stddev": float(sc[1])})
-        off += 3 * G
+def finished_models(raws: Sequence[dict], likes: Sequence[ExactLFM], fix_params: bool) -> list:
+    """The end of a fit (trainer.py:218-222): every problem's constrained model, with
+    ``after_epoch`` once more on the constrained values when ``fix_params``."""
+    out = []
+    for r, like in zip(raws, likes):
+        m = constrain(r, like)
+        if fix_params:
+            c = JaxTrainer.after_epoch({"true_s": m.true_s, "true_d": m.true_d}, True)
+            m = m.replace(true_s=c["true_s"], true_d=c["true_d"])
+        out.append(m)
     return out
+
+
+def fit_on_device(evaluator, raws, likes, optim, fix_params, num_steps_per_epoch, num_iters):
+    """trainer.py:162-228 of every problem in ONE ``evaluator.fit_packed`` call
+    (``farm.BatchEvaluator`` / ``farm.MidBatchEvaluator``) from the unconstrained ``raws``: pack,
+    fit, unpack, finish. Returns (raws, models, histories [P, num_iters], status [P])."""
+    genes = [int(m.num_genes) for m in likes]
+    evaluator.registered(genes)
+    raw = pack_raw(raws, [m.jitter for m in likes])
+    mu, nu = np.zeros_like(raw), np.zeros_like(raw)
+    hist, status = evaluator.fit_packed(raw, mu, nu, optim, fix_params, num_steps_per_epoch, 0,
+                                        num_iters)
+    raws = unpack_raw(raw, genes)
+    return raws, finished_models(raws, likes, fix_params), hist.T.copy(), status
 
 
 @dataclass
@@ -262,33 +277,9 @@ class BatchTrainer:
 
     def fit(self, fix_params: bool = True, num_steps_per_epoch: int = 1000):
         """trainer.py:162-228 for every problem; returns (models, histories [P, num_iters])."""
-        from . import _lib
-
-        genes = [int(m.num_genes) for m in self._like]
-        batch = self._ev.registered(genes)
-        raw = pack_raw(self.raws, [m.jitter for m in self._like])
-        mu, nu = np.zeros_like(raw), np.zeros_like(raw)
-        hist = np.empty((self.num_iters, len(genes)))
-        st = np.zeros(len(genes), np.int32)
-        o = self.optim
-        opt = _lib.LfmAdam(o.learning_rate, o.b1, o.b2, o.eps, o.eps_root,
-                           int(num_steps_per_epoch), int(bool(fix_params)))
-        rc = self.ctx.lib.lfm_batch_fit_f64(self.ctx.handle, batch, _lib.ctypes.byref(opt),
-                                            int(bool(self.objective.negative)), 0, self.num_iters,
-                                            _lib.dptr(raw), _lib.dptr(mu), _lib.dptr(nu),
-                                            _lib.dptr(hist), _lib.dptr(st))
-        self.ctx.check(rc, allow_not_pd=True)
-        self.status = st
-        self.raws = unpack_raw(raw, genes)
-        out = []
-        for r, like in zip(self.raws, self._like):
-            m = constrain(r, like)
-            if fix_params:  # trainer.py:218-222, on the constrained model
-                c = JaxTrainer.after_epoch({"true_s": m.true_s, "true_d": m.true_d}, True)
-                m = m.replace(true_s=c["true_s"], true_d=c["true_d"])
-            out.append(m)
-        self.models = out
-        self.history = hist.T.copy()
+        self.raws, self.models, self.history, self.status = fit_on_device(
+            self._ev, self.raws, self._like, self.optim, fix_params, num_steps_per_epoch,
+            self.num_iters)
         return self.models, self.history
 
     def close(self):
@@ -358,8 +349,11 @@ class MidBatchTrainer:
 
     def fit(self, fix_params: bool = True, num_steps_per_epoch: int = 1000):
         """trainer.py:162-228 for every problem; returns (models, histories [P, num_iters])."""
-        if self.on_device:
-            return self._fit_on_device(fix_params, num_steps_per_epoch)
+        if self.on_device:  # as BatchTrainer.fit
+            self.raws, self.models, self.history, self.status = fit_on_device(
+                self.evaluator, self.raws, self._like, self.optim, fix_params,
+                num_steps_per_epoch, self.num_iters)
+            return self.models, self.history
         raws = list(self.raws)
         states = [self.optim.init(r) for r in raws]
         hist = np.empty((len(raws), self.num_iters))
@@ -372,34 +366,8 @@ class MidBatchTrainer:
                                                                    step_count)
                 if step_count % num_steps_per_epoch == 0:
                     raws[p] = JaxTrainer.after_epoch(raws[p], fix_params)
-        out = []
-        for r, like in zip(raws, self._like):
-            m = constrain(r, like)
-            if fix_params:  # trainer.py:218-222, on the constrained model
-                c = JaxTrainer.after_epoch({"true_s": m.true_s, "true_d": m.true_d}, True)
-                m = m.replace(true_s=c["true_s"], true_d=c["true_d"])
-            out.append(m)
-        self.raws, self.models, self.history = raws, out, hist
-        return self.models, self.history
-
-    def _fit_on_device(self, fix_params, num_steps_per_epoch):
-        """``fit`` in one ``fit_packed`` call; the tail is ``BatchTrainer.fit``'s."""
-        genes = [int(m.num_genes) for m in self._like]
-        self.evaluator.registered(genes)
-        raw = pack_raw(self.raws, [m.jitter for m in self._like])
-        mu, nu = np.zeros_like(raw), np.zeros_like(raw)
-        hist, self.status = self.evaluator.fit_packed(raw, mu, nu, self.optim, fix_params,
-                                                      num_steps_per_epoch, 0, self.num_iters)
-        self.raws = unpack_raw(raw, genes)
-        out = []
-        for r, like in zip(self.raws, self._like):
-            m = constrain(r, like)
-            if fix_params:  # trainer.py:218-222, on the constrained model
-                c = JaxTrainer.after_epoch({"true_s": m.true_s, "true_d": m.true_d}, True)
-                m = m.replace(true_s=c["true_s"], true_d=c["true_d"])
-            out.append(m)
-        self.models = out
-        self.history = hist.T.copy()
+        self.raws, self.history = raws, hist
+        self.models = finished_models(raws, self._like, fix_params)
         return self.models, self.history
 
     def close(self):
@@ -479,14 +447,7 @@ class FarmTrainer:
 
         rec = self.farm.run_records(len(self.models), 3 * self.gmax + 2 + self.num_iters, block)
         self.raws, self.history = unfit_records(rec, self.genes, self.gmax)
-        out = []
-        for r, like in zip(self.raws, self.models):
-            m = constrain(r, like)
-            if fix_params:  # trainer.py:218-222, on the constrained model
-                c = JaxTrainer.after_epoch({"true_s": m.true_s, "true_d": m.true_d}, True)
-                m = m.replace(true_s=c["true_s"], true_d=c["true_d"])
-            out.append(m)
-        return out, self.history
+        return finished_models(self.raws, self.models, fix_params), self.history
 
     def close(self):
         if self._bt is not None:

@@ -9,7 +9,9 @@
 //   one update launch carrying the step, 1 + nsteps (len(value_grad) + 1) in all; every index
 //   the update kernel forms (packed slots, history, bias) stays inside its region; the
 //   rejections come in the documented order with the limit in the message.
+// And adam_bias, the bias table of both on-device fits, against the host's pow entry for entry.
 #include <algorithm>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <vector>
@@ -150,6 +152,18 @@ int main() {
   }
   check_fit({{7, 7}}, MID_FIT_MAX_STEPS);  // the cap itself is taken
   ++plans;
+  // the bias table both fit entry points upload (adam_bias): the host's pow, entry for entry
+  const lfm_adam opt{0.01, 0.9, 0.999, 1e-8, 0.0, 2, 1};
+  for (int64_t step0 : {0, 7}) {
+    std::vector<double> bias(2 * 3);
+    adam_bias(&opt, step0, 3, bias.data());
+    for (int64_t s = 0; s < 3; ++s) {
+      const double count = (double)(step0 + s + 1);
+      CHECK(bias[2 * s] == 1.0 - std::pow(opt.b1, count) &&
+                bias[2 * s + 1] == 1.0 - std::pow(opt.b2, count),
+            "bias of step %lld after %lld", (long long)s, (long long)step0);
+    }
+  }
   if (failures) {
     std::printf("mid_fit_plan_check: %d failures\n", failures);
     return 1;
