@@ -52,10 +52,13 @@ value that is right to fp64 rounding at any hyperparameters:
     entries of the reference formula in mpmath carried in long double (never rounded to fp64),
     a long double Cholesky and forward solves; ``PairCache.scale`` gives the magnitude M of the
     cancellation-free form's terms for any flag pairing (``mtab_scale``'s analogue for xf / ff).
+  * ``predictive_exact``: joint samples and the held-out log density of
+    N(mean, cov + cov_add I) from the same posterior, the covariance never rounded to fp64 before
+    its own long double Cholesky.
 
-mpmath is needed by the generators (tests/golden/make_golden_exact.py, make_golden_exact_grad.py
-and make_golden_exact_posterior.py) and by the CPU tests that regenerate a subsample; nothing here runs
-on a GPU box at test time.
+mpmath is needed by the generators (tests/golden/make_golden_exact.py, make_golden_exact_grad.py,
+make_golden_exact_posterior.py and make_golden_exact_predictive.py) and by the CPU tests that
+regenerate a subsample; nothing here runs on a GPU box at test time.
 """
 
 from __future__ import annotations
@@ -850,13 +853,9 @@ def posterior_entries(x, t, D, S, l, dps=60, diag_only=False, cache=None):
     return pc.matrix(x), pc.matrix(t, x), Ktt
 
 
-def posterior_from_entries(ent, x, y, diag_vec, diag_add, t, D, B, dtype=LD, perm=None):
-    """(mean, cov) of the posterior from the entries ``ent`` of ``posterior_entries`` (cov is the
-    variance vector when ent[2] is K(t,t)'s diagonal): S = K(x,x) + diag(diag_vec) + diag_add I,
-    V = L^{-1} K(x,t), z = L^{-1} (y - m(x)), mean = m(t) + V^T z, cov = K(t,t) - V^T V, in
-    ``dtype`` (long double: the truth, by ``_chol_ld``; fp64: scipy's Cholesky and triangular
-    solves on the entries rounded once). ``perm`` factors the symmetric permutation instead.
-    (None, None) when S is not positive definite."""
+def _posterior_parts(ent, x, y, diag_vec, diag_add, t, D, B, dtype, perm):
+    """(m(t), V = L^{-1} K(x,t), z = L^{-1} (y - m(x)), K(t,t)) in ``dtype`` behind
+    ``posterior_from_entries`` and ``predictive_exact``; None when S is not positive definite."""
     Kxx, Ktx, Ktt = ent
     x, t = np.asarray(x, np.float64), np.asarray(t, np.float64)
     n, m, G = x.shape[0], t.shape[0], len(D)
@@ -873,7 +872,7 @@ def posterior_from_entries(ent, x, y, diag_vec, diag_add, t, D, B, dtype=LD, per
     if dtype == LD:
         Lm = _chol_ld(Sig)
         if Lm is None:
-            return None, None
+            return None
         W = np.concatenate([Kxt, r[:, None]], axis=1)
         for i in range(n):
             W[i] = (W[i] - Lm[i, :i] @ W[:i]) / Lm[i, i]
@@ -883,15 +882,79 @@ def posterior_from_entries(ent, x, y, diag_vec, diag_add, t, D, B, dtype=LD, per
         try:
             Lm = scipy.linalg.cholesky(Sig.astype(dtype), lower=True, check_finite=False)
         except (np.linalg.LinAlgError, scipy.linalg.LinAlgError):
-            return None, None
+            return None
         W = scipy.linalg.solve_triangular(
             Lm, np.concatenate([Kxt, r[:, None]], axis=1).astype(dtype), lower=True,
             check_finite=False)
         mt, Ktt = mt.astype(dtype), np.asarray(Ktt).astype(dtype)
-    V, z = W[:, :m], W[:, m]
+    return mt, W[:, :m], W[:, m], Ktt
+
+
+def posterior_from_entries(ent, x, y, diag_vec, diag_add, t, D, B, dtype=LD, perm=None):
+    """(mean, cov) of the posterior from the entries ``ent`` of ``posterior_entries`` (cov is the
+    variance vector when ent[2] is K(t,t)'s diagonal): S = K(x,x) + diag(diag_vec) + diag_add I,
+    V = L^{-1} K(x,t), z = L^{-1} (y - m(x)), mean = m(t) + V^T z, cov = K(t,t) - V^T V, in
+    ``dtype`` (long double: the truth, by ``_chol_ld``; fp64: scipy's Cholesky and triangular
+    solves on the entries rounded once). ``perm`` factors the symmetric permutation instead.
+    (None, None) when S is not positive definite."""
+    parts = _posterior_parts(ent, x, y, diag_vec, diag_add, t, D, B, dtype, perm)
+    if parts is None:
+        return None, None
+    mt, V, z, Ktt = parts
     mean = mt + V.T @ z
     cov = Ktt - np.sum(V * V, axis=0) if np.ndim(Ktt) == 1 else Ktt - V.T @ V
     return mean.astype(np.float64), cov.astype(np.float64)
+
+
+def predictive_exact(ent, x, y, diag_vec, diag_add, t, D, B, cov_add, ystar, z, dtype=LD,
+                     perm=None):
+    """(mean [m], logp, X [len(z), m]) of the predictive distribution N(mean, cov + cov_add I)
+    behind ``multi_gene_predict(...).log_prob`` / ``.sample``: the posterior as
+    ``posterior_from_entries`` forms it, with the covariance kept in ``dtype`` (long double: it is
+    not rounded to fp64 before ``cov_add`` joins its diagonal), the scale's Cholesky factor L
+    (``_chol_ld``), logp = -(m log 2 pi + 2 sum log L_ii + |L^{-1} (ystar - mean)|^2) / 2 from a
+    forward solve and the factor's diagonal, and X = mean + z L^T for the normals ``z``; rounded
+    to fp64 at the end. ``ent`` holds the full K(t,t). ``ystar`` None: logp is None; ``z`` None:
+    X is None. ``dtype=np.float64``: scipy's Cholesky and triangular solves on the entries rounded
+    once. ``perm`` permutes the training rows. (None, None, None) where S or the scale is not
+    positive definite."""
+    parts = _posterior_parts(ent, x, y, diag_vec, diag_add, t, D, B, dtype, perm)
+    if parts is None:
+        return None, None, None
+    mt, V, zr, Ktt = parts
+    assert np.ndim(Ktt) == 2, "the full K(t,t)"
+    m = mt.shape[0]
+    mean = mt + V.T @ zr
+    scale = Ktt - V.T @ V
+    idx = np.diag_indices(m)
+    scale[idx] = scale[idx] + dtype(float(cov_add))
+    if dtype == LD:
+        Lc = _chol_ld(scale)
+        if Lc is None:
+            return None, None, None
+    else:
+        import scipy.linalg
+
+        try:
+            Lc = scipy.linalg.cholesky(scale, lower=True, check_finite=False)
+        except (np.linalg.LinAlgError, scipy.linalg.LinAlgError):
+            return None, None, None
+    logp = None
+    if ystar is not None:
+        d = np.asarray(ystar, np.float64).reshape(-1).astype(dtype) - mean
+        if dtype == LD:
+            w = np.empty(m, dtype=LD)
+            for i in range(m):
+                w[i] = (d[i] - Lc[i, :i] @ w[:i]) / Lc[i, i]
+        else:
+            w = scipy.linalg.solve_triangular(Lc, d, lower=True, check_finite=False)
+        logdet = 2 * np.sum(np.log(np.diagonal(Lc)))
+        # log(2 pi) from the fp64 pi: m * 1e-17 absolute, as in mll_exact
+        logp = float(-(m * np.log(2 * dtype(np.pi)) + logdet + w @ w) / 2)
+    X = None
+    if z is not None:
+        X = (mean + np.atleast_2d(np.asarray(z, np.float64)).astype(dtype) @ Lc.T).astype(np.float64)
+    return mean.astype(np.float64), logp, X
 
 
 def posterior_exact(x, y, diag_vec, diag_add, t, D, S, B, l, dps=60, perm=None, diag_only=False,

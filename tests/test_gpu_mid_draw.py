@@ -9,6 +9,8 @@ tests/test_gpu_sample.py uses for the resident path. Inputs: tests/mid_draw_inpu
 
   1. log density, 2. samples: every edge problem in one batch and the cap alone, cov_add 1e-4
      and 0.49; 3. bit identities; 4. moments; 5. failures and refusals; 6. the Python shim.
+
+The end-to-end bound against an extended-precision truth: tests/test_gpu_exact_predictive.py.
 """
 
 import ctypes

@@ -12,6 +12,8 @@ GaussianDistribution.sample, predict.Posterior.sample).
   6. the resident path against lfm_mvn_sample_f64 fed the same handle's predict, bit for bit, and
      against numpy within 50 kappa(scale) m eps max|X|; a predict before and after is unchanged;
   7. failures leave the ctx and the handle usable.
+
+The end-to-end bound against an extended-precision truth: tests/test_gpu_exact_predictive.py.
 """
 
 import ctypes
