@@ -209,7 +209,7 @@ __device__ __forceinline__ void small_factor_next(double (&d)[W], int c, SmallFa
 // updated slot 16 crossing to the low lane's slot 15. The same arithmetic as the one-lane LDL^T
 // columns. On return the low lanes' 16 slots are the one-lane window of width 16 at column c.
 __device__ __forceinline__ int small_factor_two(double (&a)[16], SmallFactor& f) {
-  const int hi = (int)(threadIdx.x >> 5), i = (int)(threadIdx.x & 31);
+  const int hi = (int)((threadIdx.x >> 5) & 1), i = (int)(threadIdx.x & 31);  // any wave
   const bool act = i < f.n + 1;
   if (hi) f.colbuf[32 + i] = 0.0;  // entries past the rows (the high half reads up to c + 31)
   int c = 0;
@@ -246,7 +246,7 @@ __device__ __forceinline__ void small_factor_regs(const double* __restrict__ sm,
                                                   double* quad, int* bad_out) {
   SmallFactor f;
   f.n = n;
-  f.r = threadIdx.x;  // wave 0
+  f.r = threadIdx.x & 63;  // one wave, whichever it is
   f.act = f.r < M;
   f.colbuf = colbuf;
   f.mp = f.mz = f.q = 0.0;
@@ -609,10 +609,13 @@ __global__ __launch_bounds__(256) void small_mll_kernel_args(SmallArgs a) {
 //     alpha = S^{-1} r,  W = alpha alpha^T - S^{-1},
 // for n <= 127 (n + 1 <= 128 rows of the augmented matrix in registers):
 //   1. Sigma and r in LDS (small_sigma: the MLL kernel's arithmetic);
-//   2. the sweep operator on [[Sigma, r], [r^T, 0]] (below): -Sigma^{-1}, alpha and the pivots
-//      (logdet) in one pass — on half a wave (n + 1 <= 32, two lanes a row), one wave
+//   2. the sweep operator on [[Sigma, r], [r^T, 0]] (below): -Sigma^{-1} and alpha in one pass
+//      — on half a wave (n + 1 <= 32, two lanes a row), one wave
 //      (n + 1 <= 64; waves 1-3 meanwhile build the grid layout's derivative tables,
 //      grad_table_entry) or four waves (n + 1 <= 128, one barrier a step);
+//      Its pivots and last entry would give the MLL too, through other roundings than the MLL
+//      kernel's: the value comes from that kernel's own factor instead (wave 1 beside a one-wave
+//      sweep, every wave before the four-wave one), so that it is lfm_batch_mll_f64's bit for bit;
 //   3. W = alpha alpha^T - Sigma^{-1} written by the sweep's last pass (small_sweep_w*): into wb
 //      (one wave) or A's lower triangle (four waves), diag(W) into wd;
 //   4. 1/2 tr(W dS/d{D, S, l}): grid problems one wave per gene-block pair (its rows share gene
@@ -981,21 +984,27 @@ __device__ __forceinline__ double small_value_grad(const SmallProb P, const Smal
       for (int q = tid; q < ngg; q += 256) m.gg[q] = grad_table_entry(h, P.T, P.dt, m.tms, q);
     }
     __syncthreads();  // Sigma and r are read by every wave
-    // the four-wave sweep: logdet, the quadratic form, alpha and -Sigma^{-1}; W from its rows
+    // the value: the MLL kernel's own two-wave factor and sums on the same Sigma (A is only
+    // read), so that value[p] is lfm_batch_mll_f64's out[p] bit for bit (include/lfm.h); the
+    // sweep's pivots give the same number through other roundings. Its column buffers are the
+    // sweep's, which is past a barrier from here
+    double fmll;
+    int fbad;
+    {
+      double pr, zr;
+      small_factor_regs2(A, ld, n, M, m.colbuf, &pr, &zr, &fbad);
+      fmll = small_mll_2wave(pr, zr, fbad, n, negative, m.red);
+    }
+    __syncthreads();  // every thread has read the sums in red and is past the column buffers
+    // the four-wave sweep: alpha and -Sigma^{-1}; W from its rows
     double a[64];
     double logdet;
     int bad;
     small_sweep4(A, ld, n, m.colbuf, a, &logdet, &bad);
-    // -r^T Sigma^{-1} r: row n's slot 0 (thread n: the h = 0 threads are rows 0..127)
-    if (tid == n) m.red[2] = -a[0];
     small_sweep4_w(a, n, A, ld, m.al, m.wd);
     if (tid == 0) {
-      const double two_pi = 6.283185307179586476925;
-      double mll = -0.5 * ((double)n * log(two_pi) + logdet + m.red[2]);
-      mll *= negative ? -1.0 : 1.0;
-      if (bad) mll = __builtin_nan("");
-      m.red[0] = mll;
-      m.red[1] = (double)bad;
+      m.red[0] = bad ? __builtin_nan("") : fmll;
+      m.red[1] = (double)(bad ? bad : fbad);
     }
   } else if (wv == 0) {
     // one wave: the sweep (small_sweep_regs) gives the MLL's logdet and quadratic form, alpha
@@ -1004,16 +1013,8 @@ __device__ __forceinline__ double small_value_grad(const SmallProb P, const Smal
       double logdet;
       int bad;
       small_sweep_regs(A, ld, n, m.colbuf, a, &logdet, &bad);
-      const double quad = -__shfl(a[0], n);  // lane n: -r^T Sigma^{-1} r
       small_sweep_w(a, n, m.wb, m.colbuf, m.al, m.wd);
-      if (lane == 0) {
-        const double two_pi = 6.283185307179586476925;
-        double mll = -0.5 * ((double)n * log(two_pi) + logdet + quad);
-        mll *= negative ? -1.0 : 1.0;
-        if (bad) mll = __builtin_nan("");
-        m.red[0] = mll;
-        m.red[1] = (double)bad;
-      }
+      if (lane == 0) m.red[1] = (double)bad;
     };
     if (M <= 32) {
       // each row on two lanes (small_sweep_half)
@@ -1021,25 +1022,48 @@ __device__ __forceinline__ double small_value_grad(const SmallProb P, const Smal
       double logdet;
       int bad;
       small_sweep_half(A, ld, n, m.colbuf, a, &logdet, &bad);
-      const double quad = -__shfl(a[0], n);  // lane n: -r^T Sigma^{-1} r
       small_sweep_w_half(a, n, m.wb, m.colbuf, m.al, m.wd);
-      if (lane == 0) {
-        const double two_pi = 6.283185307179586476925;
-        double mll = -0.5 * ((double)n * log(two_pi) + logdet + quad);
-        mll *= negative ? -1.0 : 1.0;
-        if (bad) mll = __builtin_nan("");
-        m.red[0] = mll;
-        m.red[1] = (double)bad;
-      }
+      if (lane == 0) m.red[1] = (double)bad;
     } else {
       double a[64];
       sweep(a);
     }
-  } else if (P.T > 0) {
-    const int ngg = (int)grad_tables_doubles(G, P.T);
-    for (int q = tid - 64; q < ngg; q += 192) m.gg[q] = grad_table_entry(h, P.T, P.dt, m.tms, q);
+  } else {
+    if (wv == 1) {
+      // The value, beside wave 0's sweep: the MLL kernel's own one-wave factor (small_body's
+      // operations on the same Sigma, which both waves only read; a column buffer of its own,
+      // m.fcol), so that value[p] is lfm_batch_mll_f64's out[p] bit for bit (include/lfm.h). The
+      // sweep's pivots give the same number through other roundings.
+      double pr, qp;
+      int fbad;
+      m.fcol[64 + lane] = 0.0;
+      if (M <= 32)
+        small_factor_regs<32>(A, ld, n, M, m.fcol, &pr, &qp, &fbad);
+      else
+        small_factor_regs<64>(A, ld, n, M, m.fcol, &pr, &qp, &fbad);
+      double ldp = lane < n ? log(pr) : 0.0;
+      for (int o = 32; o > 0; o >>= 1) ldp += __shfl_xor(ldp, o);
+      if (lane == 0) {
+        const double two_pi = 6.283185307179586476925;
+        double mll = -0.5 * ((double)n * log(two_pi) + ldp + qp);
+        mll *= negative ? -1.0 : 1.0;
+        if (fbad) mll = __builtin_nan("");
+        m.red[0] = mll;
+        m.red[3] = (double)fbad;
+      }
+    }
+    if (P.T > 0) {
+      const int ngg = (int)grad_tables_doubles(G, P.T);
+      for (int q = tid - 64; q < ngg; q += 192)
+        m.gg[q] = grad_table_entry(h, P.T, P.dt, m.tms, q);
+    }
   }
   __syncthreads();
+  // one wave: a failure seen by either the sweep or the factor fails the problem
+  if (M <= 64 && tid == 0) {
+    if (m.red[1] != 0.0) m.red[0] = __builtin_nan("");
+    else if (m.red[3] != 0.0) m.red[1] = m.red[3];
+  }
   // (W was written by the sweep: small_sweep_w / _half on one wave, small_sweep4_w on four)
   const int np = n * (n + 1) / 2;
   __syncthreads();

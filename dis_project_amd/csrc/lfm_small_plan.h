@@ -51,14 +51,14 @@ LFM_HD inline size_t tables_doubles(int G, int T) {
 //   accw   [4][2G + 1]      the waves' partial sums of 1/2 tr(W dSigma / d{D, S, l})
 //   wb     [(n + 1) x ldw]  one wave: W's rows as the sweep leaves them (small_sweep_w)
 //   gout   [3G + 3]         the gradient in the packed layout (dD dS dB, dl, d obs_stddev, 0)
+//   fcol   [128]            one wave: the column buffer of the value's factor, which wave 1 runs
+//                           beside wave 0's sweep (four waves factor first, in colbuf)
 // and the fit (FIT): raw, mu, nu [3G + 3 each] (the unconstrained parameters, Adam's moments).
 // The regions are disjoint and inside the returned size for every shape the kernels take:
 // host_check's check_small_map enumerates them.
-// (`spare` is never set or read: without the member the compiler allocates the gradient kernels'
-// registers differently, 22 AGPRs instead of 14, so it stays until that is measured)
 struct SmallMap {
   double *A, *red, *hyp, *ktab, *colbuf, *xs, *ys, *gt;
-  double *gg, *al, *wd, *accw, *gout, *raw, *mu, *nu, *tms, *spare, *wb;
+  double *gg, *al, *wd, *accw, *gout, *raw, *mu, *nu, *tms, *fcol, *wb;
   int* bgs;
   int n, ld, G;
 };
@@ -105,6 +105,7 @@ LFM_HD inline size_t small_map(double* sm, int n, int G, int T, int tabs, int gr
     q.wb = take(n + 1 <= 64 ? (size_t)(n + 1) * small_wb_ld(n) : 0);
     q.accw = take(4 * (2 * (size_t)G + 1));
     q.gout = take(3 * (size_t)G + 3);
+    q.fcol = take(n + 1 <= 64 ? 128 : 0);
   }
   if (fit) {
     q.raw = take(3 * (size_t)G + 3);
