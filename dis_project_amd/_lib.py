@@ -166,6 +166,8 @@ PRODUCT_SIGNATURES = [
      [_c_ctx, _dptr, _dptr, c_int64, c_int64, c_uint64, c_int64, c_int64, _dptr]),
     ("lfm_post_sample_f64", c_int,
      [_c_ctx, c_void_p, _dptr, c_int64, c_double, c_uint64, c_int64, c_int64, _dptr, _dptr]),
+    ("lfm_post_log_prob_f64", c_int,
+     [_c_ctx, c_void_p, _dptr, c_int64, c_double, _dptr, c_int64, _dptr, _dptr]),
     ("lfm_h_f64", c_int,
      [_c_ctx, POINTER(LfmHyp), POINTER(c_int64), POINTER(c_int64), _dptr, _dptr, c_int64, _dptr]),
     ("lfm_dev_alloc", c_int, [_c_ctx, c_size_t, POINTER(c_void_p)]),

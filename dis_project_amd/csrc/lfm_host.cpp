@@ -614,6 +614,41 @@ SamplePlan plan_sample(int64_t n, int64_t nsamp, int64_t sample0) {
   return P;
 }
 
+// ------------------------- held-out log density on the resident posterior (lfm_post.hip)
+PostLogpPlan plan_post_logp(int64_t n, int64_t G, int64_t m, int64_t k, int64_t chunk) {
+  PostLogpPlan P;
+  P.m = m;
+  P.k = k;
+  auto rejected = [&](int code, const std::string& why) {
+    P.reject = code;
+    P.why = why;
+    P.pred = ResidentPlan();
+    return P;
+  };
+  P.pred = plan_post(n, G, m, chunk, true);
+  if (P.pred.reject) return rejected(P.pred.reject, P.pred.why);  // the codes are plan_post's
+  if (k < 1) return rejected(PostLogpPlan::BAD_K, "k must be >= 1 held-out vector");
+  if (k > LOGP_MAX_K)
+    return rejected(PostLogpPlan::TOO_MANY,
+                    "k = " + std::to_string(k) + " is above the limit of " +
+                        std::to_string(LOGP_MAX_K) +
+                        " held-out vectors a call (split the rows of ystar over calls)");
+  P.Np = (m + 127) / 128 * 128;
+  P.Mp = (m + 1 + 127) / 128 * 128;
+  P.pass = std::min(P.pred.chunk, post_default_chunk(P.Np));
+  P.rows = plan_post(m, 1, k, P.pass, false);
+  P.mat_bytes = (size_t)P.Mp * P.Mp * sizeof(double);
+  P.dinv_bytes = (size_t)(P.Np / 128) * 128 * 16 * sizeof(double);
+  P.zero_bytes = (size_t)P.Np * sizeof(double);
+  P.vt_bytes = std::max(P.pred.vt_bytes, P.rows.vt_bytes);
+  P.acc_bytes = std::max(P.pred.acc_bytes, P.rows.acc_bytes);
+  P.logp_bytes = (size_t)P.rows.vt_rows * sizeof(double);
+  P.dinv_grid = (int)(P.Np / 128);
+  P.z_grid = (int)((P.Np + 255) / 256);
+  P.resid_grid = (int)((P.Np / 2 + 255) / 256);
+  return P;
+}
+
 // ------------------- mid-size resident batch (lfm_mbatch.hip; its kernels: lfm_mid.hip)
 namespace {
 // a region's size rounded up to 16 bytes: in doubles, and in bytes

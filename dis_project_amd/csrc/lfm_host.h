@@ -4,7 +4,8 @@
 // device-counter target and profiling figure of a call, which lfm_chol_sched.hip only reads);
 // with lfm_small_plan.h the small-problem path's LDS map, staging and buffer layouts and its
 // launch plans (plan_small_*, which lfm_small.hip and lfm_batch.hip only read); and the resident
-// posterior's predict plan (plan_post, which lfm_post.hip only reads); with lfm_mid_plan.h the
+// posterior's predict plan and its held-out log density's (plan_post, plan_post_logp, which
+// lfm_post.hip only reads); with lfm_mid_plan.h the
 // mid-size resident batch's arenas and launch plans (plan_mid, plan_mid_post, plan_mid_fit,
 // plan_mid_draw, which lfm_mbatch.hip and lfm_mid.hip only read); and
 // the joint samples' generator and launch plan (plan_sample, which lfm_sample.hip only reads).
@@ -313,6 +314,38 @@ inline int64_t sample_depth(int tj) { return 128 * ((int64_t)tj + 1); }
 // Rejections in order: n < 1 or above 2^30; nsamp < 1; sample0 < 0; sample0 + nsamp above
 // 2^63 - 1; nsamp above SAMPLE_MAX_NSAMP.
 SamplePlan plan_sample(int64_t n, int64_t nsamp, int64_t sample0);
+
+// ------------------------- held-out log density on the resident posterior (lfm_post.hip)
+// lfm_post_log_prob_f64: k held-out vectors scored under N(mean(t), cov(t) + diag_add I). The
+// predict with the covariance is plan_post's (`pred`); the covariance is factored in the sample
+// call's matrix (stride Mp = round_up(m + 1, 128), mat_bytes as plan_sample's); the residual rows
+// R (stride Np = round_up(m, 128)) go through the predict's own sweep against that factor in
+// passes of `pass` rows: `rows` is plan_post for a factor of m columns and k test rows in chunks
+// of `pass`, whose chunks are the passes and whose panels are the sweep's launches. pass is the
+// handle's chunk, capped at post_default_chunk(Np), so that R stays within POST_VT_BUDGET.
+constexpr int64_t LOGP_MAX_K = (int64_t)1 << 24;  // held-out vectors per call
+struct PostLogpPlan {
+  enum Reject { OK = 0, BAD_M, COV_CHUNK, BAD_CHUNK, BAD_K, TOO_MANY };
+  int reject = OK;
+  std::string why;           // the message of a rejection
+  int64_t m = 0, k = 0;
+  int64_t Np = 0, Mp = 0;    // round_up(m, 128), round_up(m + 1, 128)
+  int64_t pass = 0;          // held-out rows per pass, a multiple of 128
+  ResidentPlan pred;         // the predict with the covariance: plan_post(n, G, m, chunk, true)
+  ResidentPlan rows;         // the sweep over cov's factor: plan_post(m, 1, k, pass, false)
+  size_t mat_bytes = 0;      // Mp x Mp: the covariance's factor
+  size_t dinv_bytes = 0;     // Np / 128 x 8 inverses of its 16 x 16 diagonal blocks
+  size_t zero_bytes = 0;     // the sweep's z: Np zeros
+  size_t vt_bytes = 0;       // the larger of the predict's Vt and R (rows.vt_rows x Np)
+  size_t acc_bytes = 0;      // the larger of the two sweeps' row accumulators
+  size_t logp_bytes = 0;     // one pass's results: rows.vt_rows doubles
+  int dinv_grid = 0;         // post_dinv_kernel: one workgroup per 128-block of the factor
+  int z_grid = 0;            // post_z_kernel: workgroups of 256 over Np columns
+  int resid_grid = 0;        // post_resid_kernel: grid (resid_grid, pad_rows), 256 pairs each
+};
+// Rejections in order: plan_post's with the covariance (m < 1 or m % G != 0; m above the chunk; a
+// bad chunk); k < 1; k above LOGP_MAX_K.
+PostLogpPlan plan_post_logp(int64_t n, int64_t G, int64_t m, int64_t k, int64_t chunk);
 
 // Readers-writer lock over one GPU's library work (lfm_ctx.hip DeviceTenancy: a schedule-3
 // factorisation exclusive, all other GPU work shared). In-process a std::shared_mutex; across

@@ -325,6 +325,12 @@ bool chol_fuses_gram(const lfm_ctx* ctx, int mode, const GridLayout& lay, int64_
 // sizes). Nothing is downloaded and nothing synchronised.
 int sample_enqueue(lfm_ctx* ctx, const SamplePlan& P, double* A, const double* d_loc,
                    uint64_t seed, double* Z, double* X);
+// Its two halves, for a caller that reads the factor itself (lfm_post.hip). scale_factor: the
+// augmented row with residual 0 and the factorisation of A (stride Mp, scale n x n) in place, so
+// that ctx->result[0] = -1/2 logdet - (n / 2) log 2 pi. sample_draw: everything after it.
+int scale_factor(lfm_ctx* ctx, double* A, int64_t n, int64_t Mp, const double* d_loc);
+int sample_draw(lfm_ctx* ctx, const SamplePlan& P, double* A, const double* d_loc, uint64_t seed,
+                double* Z, double* X);
 // The end of a sampling call: X and the factorisation's status to the host, synchronised. Not
 // positive definite: out (and mean, if given) NaN and LFM_E_NOT_PD.
 int sample_finish(lfm_ctx* ctx, const SamplePlan& P, const double* X, double* out, double* mean);

@@ -25,7 +25,16 @@
 // lfm_post_sample_f64 draws joint samples from such a predict without the covariance leaving the
 // device: the predict with the covariance, cov copied into an Mp' = round_up(m + 1, 128)-stride
 // matrix of the handle's, diag_add on its diagonal, then lfm_sample.hip's factor, generator and
-// product (sample_enqueue). The handle's L, z and dinv are only read.
+// product (sample_draw). The handle's L, z and dinv are only read.
+// lfm_post_log_prob_f64 scores k held-out vectors under the same distribution: the sample's first
+// steps (post_scale_factor, written once for both), whose factorisation at residual 0 reduces to
+// base = -1/2 logdet - (m / 2) log 2 pi; the factor made readable by the sweep above (row m an
+// identity row, post_dinv_kernel on its diagonal blocks); then per pass of held-out rows
+//   post_resid_kernel   R = ystar - mean in place in Vt's memory, zero padded, 16-byte accesses;
+//   the same panel / update launches against the covariance's factor with z = 0, after which the
+//                       accumulator s2 is ||L^{-1} (ystar_r - mean)||^2;
+//   post_logp_kernel    logp[r] = base - 0.5 * s2[r].
+// Every size, grid and pass is plan_post_logp's (lfm_host.cpp).
 #include "lfm_api_internal.h"
 #include "lfm_chol_dev.h"
 
@@ -49,6 +58,10 @@ struct lfm_post {
   // grown by the samples (SamplePlan's byte counts): the covariance's factor, Z and X
   double *smat = nullptr, *sz = nullptr, *sx = nullptr;
   size_t smat_cap = 0, sz_cap = 0, sx_cap = 0;
+  // grown by the log densities (PostLogpPlan's byte counts): the inverses of the covariance
+  // factor's diagonal blocks, the sweep's zero z and one pass's results
+  double *sdinv = nullptr, *szero = nullptr, *lp = nullptr;
+  size_t sdinv_cap = 0, szero_cap = 0, lp_cap = 0;
 };
 
 namespace lfm {
@@ -343,7 +356,7 @@ int grow(lfm_ctx* ctx, double** p, size_t* cap, size_t bytes, const char* what) 
 
 void release(lfm_post* q) {
   for (double* p : {q->L, q->dinv, q->z, q->x, q->par, q->vt, q->acc, q->t, q->out, q->cov,
-                    q->smat, q->sz, q->sx})
+                    q->smat, q->sz, q->sx, q->sdinv, q->szero, q->lp})
     if (p) hipFree(p);
   delete q;
 }
@@ -398,6 +411,29 @@ int post_fit(lfm_ctx* ctx, lfm_post* q, const double* x, const double* y, const 
   return status_code(ctx, hres[3], hres[4]);
 }
 
+// The right-looking sweep of one chunk's rows (g.Vt) against a factor (g.L, g.dinv, g.z): the
+// plan's panel and update launches in order
+void post_sweep(lfm_ctx* ctx, PostArgs g, const ResidentPlan& P, const PostChunk& c) {
+  hipStream_t st = ctx->stream;
+  const double prow = (double)c.panel_grid * 64;
+  for (const PostPanel& s : P.panels) {
+    g.K0 = s.K0;
+    g.w = s.w;
+    g.tj0 = s.tj0;
+    hipEvent_t ev;
+    prof_begin(ctx, K_POST_PANEL, &ev);
+    hipLaunchKernelGGL(post_panel_kernel, dim3((unsigned)c.panel_grid), dim3(256), 0, st, g);
+    prof_end(ctx, K_POST_PANEL, ev, prow * NB * NB * s.w * s.w, 2.0 * prow * NB * s.w * 8);
+    if (s.ntj > 0) {
+      prof_begin(ctx, K_POST_UPDATE, &ev);
+      hipLaunchKernelGGL(post_update_kernel, dim3((unsigned)c.tiles, (unsigned)s.ntj), dim3(256),
+                         0, st, g);
+      prof_end(ctx, K_POST_UPDATE, ev, 2.0 * c.pad_rows * NB * s.ntj * NB * s.w,
+               2.0 * c.pad_rows * NB * s.ntj * 8);
+    }
+  }
+}
+
 // The launches of one chunk, exactly as the plan lists them
 int post_chunk(lfm_ctx* ctx, lfm_post* q, const ResidentPlan& P, const PostChunk& c,
                const HypDev& h) {
@@ -417,23 +453,7 @@ int post_chunk(lfm_ctx* ctx, lfm_post* q, const ResidentPlan& P, const PostChunk
   g.z = q->z;
   g.s2 = q->acc;
   g.sz = q->acc + P.vt_rows;
-  const double prow = (double)c.panel_grid * 64;
-  for (const PostPanel& s : P.panels) {
-    g.K0 = s.K0;
-    g.w = s.w;
-    g.tj0 = s.tj0;
-    hipEvent_t ev;
-    prof_begin(ctx, K_POST_PANEL, &ev);
-    hipLaunchKernelGGL(post_panel_kernel, dim3((unsigned)c.panel_grid), dim3(256), 0, st, g);
-    prof_end(ctx, K_POST_PANEL, ev, prow * NB * NB * s.w * s.w, 2.0 * prow * NB * s.w * 8);
-    if (s.ntj > 0) {
-      prof_begin(ctx, K_POST_UPDATE, &ev);
-      hipLaunchKernelGGL(post_update_kernel, dim3((unsigned)c.tiles, (unsigned)s.ntj), dim3(256),
-                         0, st, g);
-      prof_end(ctx, K_POST_UPDATE, ev, 2.0 * c.pad_rows * NB * s.ntj * NB * s.w,
-               2.0 * c.pad_rows * NB * s.ntj * 8);
-    }
-  }
+  post_sweep(ctx, g, P, c);
   hipLaunchKernelGGL(post_finish_kernel, dim3((unsigned)((c.rows + 255) / 256)), dim3(256), 0, st,
                      h, q->t, c.q0, c.rows, P.m, g.s2, g.sz, q->out, q->out + P.m);
   return hip_fail(ctx, hipGetLastError(), "resident posterior: chunk launches");
@@ -472,6 +492,66 @@ int post_enqueue(lfm_ctx* ctx, lfm_post* q, const ResidentPlan& P, const double*
 __global__ void post_shift_kernel(double* __restrict__ A, int64_t lda, double d, int64_t n) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) A[i * lda + i] += d;
+}
+
+// The first steps of a sample and of a log density, in stream order: the predict with the
+// covariance (mean in q->out, cov in q->cov), cov into the Mp-stride matrix q->smat, diag_add on
+// its diagonal in one addition, the augmented row with residual 0 and the factorisation, which
+// leaves L in q->smat's lower triangle, the status in ctx->result[3] and
+// ctx->result[0] = -1/2 logdet - (m / 2) log 2 pi. q->smat holds Mp x Mp doubles.
+int post_scale_factor(lfm_ctx* ctx, lfm_post* q, const ResidentPlan& P, int64_t Mp, const double* t,
+                      double diag_add) {
+  int r = post_enqueue(ctx, q, P, t);
+  if (r) return r;
+  hipStream_t st = ctx->stream;
+  const int64_t m = P.m;
+  hipError_t e = hipMemcpy2DAsync(q->smat, Mp * 8, q->cov, m * 8, m * 8, m,
+                                  hipMemcpyDeviceToDevice, st);
+  if (e != hipSuccess) return hip_fail(ctx, e, "the covariance into the factor's stride");
+  hipLaunchKernelGGL(post_shift_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st,
+                     q->smat, Mp, diag_add, m);
+  return scale_factor(ctx, q->smat, m, Mp, q->out);
+}
+
+// ------------------------------------------------------- held-out log density
+// The residual rows in place: R (pad_rows x ldr, ldr = round_up(m, 128)) holds ystar's rows
+// [0, rows) in its columns [0, m); R[r, j] -= mean[j] there, zero in columns [m, ldr) and in the
+// padding rows. One thread per pair of columns: every row starts 16-byte aligned, so each access
+// of R is one 16-byte load or store; mean (the handle's out) is 16-byte aligned too.
+__global__ __launch_bounds__(256) void post_resid_kernel(double* __restrict__ R, int64_t ldr,
+                                                         const double* __restrict__ mean, int64_t m,
+                                                         int64_t rows) {
+  const int64_t row = blockIdx.y;
+  const int64_t j = 2 * ((int64_t)blockIdx.x * 256 + threadIdx.x);
+  if (j >= ldr) return;
+  double2* p = reinterpret_cast<double2*>(R + row * ldr + j);
+  double2 v = {0.0, 0.0};
+  if (row < rows && j < m) {
+    v = *p;
+    if (j + 1 < m) {
+      const double2 mu = *reinterpret_cast<const double2*>(mean + j);
+      v.x -= mu.x;
+      v.y -= mu.y;
+    } else {
+      v.x -= mean[j];
+      v.y = 0.0;
+    }
+  }
+  *p = v;
+}
+
+// logp[r] = base - 0.5 * s2[r]: one multiplication (exact) and one subtraction; base = res[0] is
+// the factorisation's own reduction at residual 0, -1/2 logdet - (m / 2) log 2 pi. NaN when the
+// status word res[3] says a pivot failed, and when the row's s2 is not finite: an Inf in ystar
+// need not meet a zero of the factor on its way through the sweep, and would end as -Inf.
+__global__ void post_logp_kernel(const double* __restrict__ res, const double* __restrict__ s2,
+                                 int64_t rows, double* __restrict__ logp) {
+  #pragma clang fp contract(off)
+  const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= rows) return;
+  const double half = 0.5 * s2[r];
+  const bool ok = res[3] == (double)STATUS_NONE && half < __builtin_inf();
+  logp[r] = ok ? res[0] - half : __builtin_nan("");
 }
 
 }  // namespace
@@ -575,18 +655,82 @@ int lfm_post_sample_f64(lfm_ctx* ctx, lfm_post* post, const double* t, int64_t m
   if (!r) r = grow(ctx, &q->sx, &q->sx_cap, S.x_bytes, "the samples");
   if (!r) r = ctx->hpin.reserve(ctx, 1 << 16);
   if (r) return r;
-  r = post_enqueue(ctx, q, P, t);  // mean in q->out, cov (m x m, dense) in q->cov
+  r = post_scale_factor(ctx, q, P, S.Mp, t, diag_add);
   if (r) return r;
   hipStream_t st = ctx->stream;
-  hipError_t e = hipMemcpy2DAsync(q->smat, S.Mp * 8, q->cov, m * 8, m * 8, m,
-                                  hipMemcpyDeviceToDevice, st);
-  if (e != hipSuccess) return hip_fail(ctx, e, "the covariance into the factor's stride");
-  hipLaunchKernelGGL(post_shift_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st,
-                     q->smat, S.Mp, diag_add, m);
-  r = sample_enqueue(ctx, S, q->smat, q->out, seed, q->sz, q->sx);
+  r = sample_draw(ctx, S, q->smat, q->out, seed, q->sz, q->sx);
   if (r) return r;
   if (mean) hipMemcpyAsync(mean, q->out, (size_t)m * 8, hipMemcpyDeviceToHost, st);
   return sample_finish(ctx, S, q->sx, out, mean);
+}
+
+int lfm_post_log_prob_f64(lfm_ctx* ctx, lfm_post* post, const double* t, int64_t m, double diag_add,
+                          const double* ystar, int64_t k, double* mean, double* logp) {
+  if (!ctx) return LFM_E_ARG;
+  if (!post) return set_err(ctx, LFM_E_ARG, "post is NULL");
+  if (ctx->device != post->device)
+    return set_err(ctx, LFM_E_ARG, "the handle belongs to another device than this ctx");
+  if (!t || !ystar || !logp) return set_err(ctx, LFM_E_ARG, "t / ystar / logp is NULL");
+  lfm_post* q = post;
+  const PostLogpPlan P = plan_post_logp(q->n, q->G, m, k, q->chunk);
+  if (P.reject) return set_err(ctx, LFM_E_ARG, P.why);
+  DeviceGuard g(ctx->device);
+  DeviceTenancy tenancy(ctx, false);  // CHOL_RESIDENT is schedule 1: shared
+  // the predict's Vt and accumulators serve the residual rows once the covariance is formed:
+  // grown to the larger of the two uses before the predict, which then finds them large enough
+  int r = grow(ctx, &q->vt, &q->vt_cap, P.vt_bytes, "the solve workspace");
+  if (!r) r = grow(ctx, &q->acc, &q->acc_cap, P.acc_bytes, "the row accumulators");
+  if (!r) r = grow(ctx, &q->smat, &q->smat_cap, P.mat_bytes, "the covariance's factor");
+  if (!r) r = grow(ctx, &q->sdinv, &q->sdinv_cap, P.dinv_bytes, "its diagonal inverses");
+  if (!r) r = grow(ctx, &q->szero, &q->szero_cap, P.zero_bytes, "the zero z");
+  if (!r) r = grow(ctx, &q->lp, &q->lp_cap, P.logp_bytes, "the log densities");
+  if (!r) r = ctx->hpin.reserve(ctx, 1 << 16);
+  if (r) return r;
+  r = post_scale_factor(ctx, q, P.pred, P.Mp, t, diag_add);
+  if (r) return r;
+  hipStream_t st = ctx->stream;
+  // the factor as the sweep reads it: row m, which holds L^{-1} 0, becomes the identity row its
+  // neighbours are and its zeros become the sweep's z; then the diagonal blocks' inverses. The
+  // sweep reads the factor's 16 x 16 diagonal blocks through these inverses alone (built from
+  // their lower triangles) and everything else strictly below them, so the input entries the
+  // factorisation leaves above the diagonal are never read.
+  hipLaunchKernelGGL(post_z_kernel, dim3((unsigned)P.z_grid), dim3(256), 0, st, q->smat, P.Mp, m,
+                     P.Np, q->szero);
+  hipLaunchKernelGGL(post_dinv_kernel, dim3((unsigned)P.dinv_grid), dim3(128), 0, st, q->smat, P.Mp,
+                     q->sdinv);
+  PostArgs a{};
+  a.Vt = q->vt;
+  a.ldv = P.Np;
+  a.L = q->smat;
+  a.ldl = P.Mp;
+  a.dinv = q->sdinv;
+  a.z = q->szero;
+  a.s2 = q->acc;
+  a.sz = q->acc + P.rows.vt_rows;
+  for (const PostChunk& c : P.rows.chunks) {
+    hipError_t e = hipMemcpy2DAsync(q->vt, P.Np * 8, ystar + c.q0 * m, m * 8, m * 8, c.rows,
+                                    hipMemcpyHostToDevice, st);
+    if (e != hipSuccess) return hip_fail(ctx, e, "upload ystar");
+    hipLaunchKernelGGL(post_resid_kernel, dim3((unsigned)P.resid_grid, (unsigned)c.pad_rows),
+                       dim3(256), 0, st, q->vt, P.Np, q->out, m, c.rows);
+    post_sweep(ctx, a, P.rows, c);
+    hipLaunchKernelGGL(post_logp_kernel, dim3((unsigned)((c.rows + 255) / 256)), dim3(256), 0, st,
+                       ctx->result, a.s2, c.rows, q->lp);
+    r = hip_fail(ctx, hipGetLastError(), "held-out log density: pass launches");
+    if (r) return r;
+    hipMemcpyAsync(logp + c.q0, q->lp, (size_t)c.rows * 8, hipMemcpyDeviceToHost, st);
+  }
+  if (mean) hipMemcpyAsync(mean, q->out, (size_t)m * 8, hipMemcpyDeviceToHost, st);
+  double* hres = ctx->hpin;
+  hipMemcpyAsync(hres, ctx->result, 5 * sizeof(double), hipMemcpyDeviceToHost, st);
+  r = finish(ctx);
+  if (r) return r;
+  r = status_code(ctx, hres[3], hres[4]);
+  if (r == LFM_E_NOT_PD) {
+    std::fill(logp, logp + k, std::nan(""));
+    if (mean) std::fill(mean, mean + m, std::nan(""));
+  }
+  return r;
 }
 
 }  // extern "C"

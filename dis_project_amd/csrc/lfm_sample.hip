@@ -92,15 +92,24 @@ void launch_randn(lfm_ctx* ctx, double* Z, int64_t ld, int64_t rows, int64_t pai
 
 }  // namespace
 
+int scale_factor(lfm_ctx* ctx, double* A, int64_t n, int64_t Mp, const double* d_loc) {
+  // the augmented row: y = loc, residual 0, so the MLL the factorisation also produces is
+  // -1/2 logdet - (n / 2) log 2 pi (a draw does not use it; lfm_post_log_prob_f64 does)
+  const HypDev h{nullptr, nullptr, nullptr, 1, 1.0};
+  int r = launch_augment(ctx, h, nullptr, d_loc, d_loc, n, A, Mp, Mp);
+  if (r) return r;
+  return chol_factor_solve(ctx, A, Mp, n, Mp, 0, ctx->result, CHOL_RESIDENT);
+}
+
 int sample_enqueue(lfm_ctx* ctx, const SamplePlan& P, double* A, const double* d_loc,
                    uint64_t seed, double* Z, double* X) {
+  int r = scale_factor(ctx, A, P.n, P.Mp, d_loc);
+  return r ? r : sample_draw(ctx, P, A, d_loc, seed, Z, X);
+}
+
+int sample_draw(lfm_ctx* ctx, const SamplePlan& P, double* A, const double* d_loc, uint64_t seed,
+                double* Z, double* X) {
   hipStream_t st = ctx->stream;
-  // the augmented row: y = loc, residual 0 (the MLL the factorisation also produces is not used)
-  const HypDev h{nullptr, nullptr, nullptr, 1, 1.0};
-  int r = launch_augment(ctx, h, nullptr, d_loc, d_loc, P.n, A, P.Mp, P.Mp);
-  if (r) return r;
-  r = chol_factor_solve(ctx, A, P.Mp, P.n, P.Mp, 0, ctx->result, CHOL_RESIDENT);
-  if (r) return r;
   hipLaunchKernelGGL(sample_tril_kernel, dim3((unsigned)P.tiles_j), dim3(256), 0, st, A, P.Mp);
   launch_randn(ctx, Z, P.ldz, P.zrows, P.pairs, P.randn_grid, seed, P.sample0);
   SampleArgs g{Z, P.ldz, A, P.Mp, d_loc, X, P.n, P.nsamp, P.tiles_j};

@@ -465,6 +465,38 @@ class Posterior:
             self.ctx.check(rc, allow_not_pd=True)
         return mean, out
 
+    def log_prob(self, test_inputs, y_star, cov_add=None):
+        """log N(y_star; mean(t), cov(t) + cov_add I), one ``lfm_post_log_prob_f64``: the
+        covariance is formed and factored on the device and the held-out vectors are solved
+        against its factor there; only the log densities come back. ``y_star`` is ``[m]`` (returns
+        a float) or ``[k, m]`` (returns ``[k]``: k vectors scored under the one factorisation).
+        ``cov_add`` defaults to the model's jitter, as in ``sample``; a caller scoring noisy
+        replicates passes ``obs_stddev**2 + jitter``. Both kinds use the DENSE covariance. For
+        ``kind="gene"`` with the default ``cov_add`` that is ``predict(t).log_prob(y_star)``. For
+        ``kind="latent"`` it is the joint posterior, which the reference's ``latent_predict``
+        discards by diagonalising (model.py:420-465); ``predict(t).log_prob(...)`` still
+        reproduces the reference's diagonal distribution exactly. Gene rows (flag 1) can be
+        scored jointly under either kind. Latent rows (flag 0) cannot: their joint covariance is
+        indefinite, and the result is NaN with ``LFM_E_NOT_PD``
+        swallowed, as JAX's Cholesky would return NaN. A row of ``y_star`` with a NaN or Inf is
+        NaN alone. m must fit one chunk (``set_chunk``). After a failed fit: NaN, as
+        ``predict``."""
+        t = self._test(test_inputs)
+        m = t.shape[0]
+        y = as_f64(y_star)
+        if y.ndim not in (1, 2) or y.shape[-1] != m or y.shape[0] < 1:
+            raise ValueError(f"y_star must be [m] or [k, m] with m = {m} test rows and k >= 1")
+        single = y.ndim == 1
+        y = np.ascontiguousarray(y.reshape(-1, m))
+        k = y.shape[0]
+        cadd = self.jitter if cov_add is None else float(cov_add)
+        logp = np.full(k, np.nan)
+        if self._handle:
+            rc = self.ctx.lib.lfm_post_log_prob_f64(
+                self.ctx.handle, self._handle, dptr(t), m, cadd, dptr(y), k, None, dptr(logp))
+            self.ctx.check(rc, allow_not_pd=True)
+        return float(logp[0]) if single else logp
+
     def close(self):
         if self._final is not None:
             self._final()  # runs lfm_post_destroy once

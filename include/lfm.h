@@ -634,6 +634,70 @@ int lfm_post_sample_f64(lfm_ctx* ctx, lfm_post* post, const double* t, int64_t m
                         uint64_t seed, int64_t sample0, int64_t nsamp,
                         double* mean /* [m], may be NULL */, double* out /* [nsamp x m] */);
 
+/* ------------- held-out log density on the resident posterior */
+/* gpjax 0.8.2 GaussianDistribution.log_prob (called at objectives.py:78) of the distribution
+ * multi_gene_predict returns (model.py:467-514), for k held-out vectors at once and without the
+ * covariance leaving the device: the other half of lfm_post_sample_f64.
+ *   logp[r] = log N(ystar_r; mean(t), cov(t) + diag_add I)
+ *           = -1/2 ||w_r||^2 - sum_i log L_ii - (m / 2) log 2 pi,   r < k,
+ *   L L^T = cov(t) + diag_add I,   w_r = L^{-1} (ystar_r - mean),
+ * mean and cov as lfm_post_predict_f64 defines them; diag_add joins each diagonal entry of cov in
+ * one addition, exactly as in lfm_post_sample_f64. t [m x 3], ystar [k x m] row-major, mean [m]
+ * (may be NULL) and logp [k] are host pointers.
+ *
+ * The route, on the ctx's stream: the predict with the covariance; cov into the handle's matrix of
+ * stride Mp' = 128 ceil((m + 1) / 128), diag_add on its diagonal, the augmented row with residual
+ * 0 and the factorisation on schedule 1 (these are lfm_post_sample_f64's first steps, one piece of
+ * code), whose own reduction then is base = -1/2 logdet - (m / 2) log 2 pi; the 16 x 16 inverses
+ * of the factor's diagonal blocks; then, in passes of at most `pass` held-out rows, the residual
+ * rows R[r, j] = ystar[r, j] - mean[j] (stride Np' = 128 ceil(m / 128), zero padded) through the
+ * predict's own multi-right-hand-side sweep on the fp64 MFMA against this factor, whose per-row
+ * accumulator ends as ||w_r||^2, and
+ *   logp[r] = base - 0.5 * ||w_r||^2:   one multiplication, which is exact, and one subtraction.
+ * pass is the handle's chunk, at most the largest multiple of 128 rows, up to 16384, whose
+ * pass x Np' doubles fit 1 GiB. m has lfm_post_predict_f64's rules with the covariance. On top of
+ * a predict with the covariance the handle grows by
+ *   8 (Mp'^2 + 17 Np' + max(0, P Np' - V) + max(0, 2 P - A) + P) bytes,
+ *   P = 128 ceil(min(k, pass) / 128),  V = 128 ceil(m / 128) 128 ceil(n / 128) and A = 2 x 128
+ *   ceil(m / 128): the doubles of the predict's solve workspace and row accumulators, which are
+ *   free again once the covariance is formed and serve the residual rows;
+ * Mp'^2 of it is the matrix a sample on the same handle uses. Nothing is placed in the ctx
+ * workspace; lfm_post_destroy frees it.
+ *
+ * Promises:
+ *   logp[r] depends on the handle, t, diag_add and row r of ystar alone: not on k, not on the pass
+ *     size, not on lfm_post_set_chunk. Rows [0, j) of a k-vector call are the j-vector call's, bit
+ *     for bit, and the same call twice gives the same bits.
+ *   A NaN or Inf in one row of ystar (any row whose ||w_r||^2 is not finite) makes that row's logp
+ *     NaN and leaves every other row's bits alone; the return is still LFM_OK.
+ *   mean is lfm_post_predict_f64's mean, bit for bit.
+ *   The handle's factor, z, inverses and predict results are only read: a predict or a sample
+ *     after the call returns the bits it returned before.
+ *   No atomics, no device-side waits, no cooperative launch, no graph capture. Synchronous; holds
+ *     the device's lock shared (the factorisation runs schedule 1).
+ *   Not positive definite, a failed pivot of cov + diag_add I (latent rows: see the note on
+ *     validity above): every logp and the mean are NaN, the return is LFM_E_NOT_PD, and the handle
+ *     and the ctx stay usable. A failed allocation is LFM_E_OOM, and both stay usable.
+ *   LFM_E_ARG with a message naming the cause, no caller buffer touched, checked in this order:
+ *     a NULL ctx (no message); a NULL post; a handle of another device; a NULL t / ystar / logp;
+ *     m < 1 or m % num_genes != 0; m above the chunk; k < 1; k above 2^24 (split the rows of
+ *     ystar over calls).
+ *
+ * Measured on an MI355X (scripts/post_logp_rate.py, profiles/post_logp.json, DESIGN.md section
+ * 4.10.1; a resident N = 16384 model, gene rows, diag_add = obs_stddev^2, medians of synchronous
+ * calls): the call takes 15.2 ms at m = 384, 48 ms at m = 4096 and 237 / 237 / 241 ms at
+ * m = 16384 for 1 / 16 / 1024 vectors: the sample call's predict (109 ms of solve, both sweeps)
+ * and factorisation (76 ms), whatever k. The host route, lfm_post_predict_f64 with the covariance,
+ * one addition on the diagonal and lfm_log_prob_f64 per vector, takes 11.6 / 16.1 / 315 ms at
+ * m = 384 (0.76x / 1.06x / 21x), 44.5 / 110 / 4560 ms at m = 4096 (0.93x / 2.3x / 94x) and
+ * 289 / 1360 / 69900 ms at m = 16384 (1.2x / 5.7x / 290x; the figures for more than 16 vectors at
+ * m = 4096 and more than 2 at m = 16384 are its predict plus k times the median timed vector,
+ * 4.4 ms and 68 ms), uploading 2.1 GB per vector at m = 16384 where this call uploads 0.5 to
+ * 135 MB. For one held-out vector at m <= 4096 the host route is the faster one. */
+int lfm_post_log_prob_f64(lfm_ctx* ctx, lfm_post* post, const double* t, int64_t m, double diag_add,
+                          const double* ystar /* [k x m] row-major, host */, int64_t k,
+                          double* mean /* [m], may be NULL */, double* logp /* [k] */);
+
 /* ----------------------- device-resident variants (inputs already in HBM) */
 int lfm_dev_alloc(lfm_ctx* ctx, size_t bytes, void** out);
 int lfm_dev_free(lfm_ctx* ctx, void* p);
