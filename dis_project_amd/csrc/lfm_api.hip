@@ -1,6 +1,6 @@
 // lfm_api.hip — the large-N entry points of include/lfm.h: input staging, x-layout detection,
-// mean / h / cross-covariance / gram / MLL / gradient / posterior / log_prob, resident data, the
-// C3 restart pipeline and the dispatch of lfm_mll_batch_f64.
+// mean / h / cross-covariance / gram / MLL / gradient / posterior / log_prob / joint samples,
+// resident data, the C3 restart pipeline and the dispatch of lfm_mll_batch_f64.
 //
 // Every entry point binds the ctx's device, enqueues on the ctx's stream and is
 // synchronous at return (one hipStreamSynchronize per call).
@@ -38,15 +38,6 @@ struct Staged {
   const int* d_bg = nullptr;
 };
 
-int check_hyp(lfm_ctx* ctx, const lfm_hyp* hyp) {
-  if (!hyp) return set_err(ctx, LFM_E_ARG, "hyp is NULL");
-  if (hyp->num_genes < 1 || hyp->num_genes > (1 << 20))
-    return set_err(ctx, LFM_E_ARG, "num_genes must be in [1, 2^20]");
-  if (!hyp->true_d || !hyp->true_s || !hyp->true_b)
-    return set_err(ctx, LFM_E_ARG, "hyp true_d / true_s / true_b must not be NULL");
-  return LFM_OK;
-}
-
 // The common preamble of the entry points, in the order their argument errors are reported: x
 // and n, the call's other pointers (ptrs: all of them non-NULL, else `what`), hyp, and n against
 // num_genes.
@@ -64,9 +55,16 @@ int check_problem(lfm_ctx* ctx, const double* x, int64_t n, bool ptrs, const cha
 int read_back(lfm_ctx* ctx, const double* d_ptr, size_t count, std::vector<double>& out,
               const char* what) {
   out.resize(count);
-  hipError_t e = hipMemcpyAsync(out.data(), d_ptr, count * 8, hipMemcpyDeviceToHost, ctx->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-  return hip_fail(ctx, e, what);
+  Copies c{ctx};
+  c.down(out.data(), d_ptr, count * 8);
+  if (c.e == hipSuccess) c.e = hipStreamSynchronize(ctx->stream);
+  return c.done(what);
+}
+
+// A problem's x | y into ctx->xin (reserved by the caller): x at 0, y at 3 n
+void up_xy(Copies& c, const double* x, const double* y, int64_t n) {
+  c.up(c.ctx->xin, x, n * 3 * 8);
+  c.up(c.ctx->xin + 3 * n, y, n * 8);
 }
 
 // Uploads D, S, B (and, for a grid layout, the time vector and block genes) into ctx->par.
@@ -92,8 +90,10 @@ int stage_hyp(lfm_ctx* ctx, const lfm_hyp* hyp, const double* x_host, int64_t n,
   std::memcpy(hp + 2 * G, hyp->true_b, G * 8);
   if (T) std::memcpy(hp + 3 * G, st->lay.times.data(), T * 8);
   if (nblk) std::memcpy(reinterpret_cast<char*>(hp) + nd * 8, st->lay.block_gene.data(), nblk * 4);
-  hipError_t e = hipMemcpyAsync(ctx->par, hp, bytes, hipMemcpyHostToDevice, ctx->stream);
-  if (e != hipSuccess) return hip_fail(ctx, e, "upload hyperparameters");
+  Copies c{ctx};
+  c.up(ctx->par, hp, bytes);
+  r = c.done("upload hyperparameters");
+  if (r) return r;
   st->h = HypDev{ctx->par, ctx->par + G, ctx->par + 2 * G, (int)G, hyp->l};
   st->d_times = ctx->par + 3 * G;
   st->d_bg = reinterpret_cast<const int*>(reinterpret_cast<const char*>(ctx->par.p) + nd * 8);
@@ -148,13 +148,9 @@ int mll_enqueue(lfm_ctx* ctx, const Staged& st, const double* d_x, const double*
 // The scalar result of the factorisation just enqueued, to the host (synchronous): NaN with the
 // status word's error.
 int read_result(lfm_ctx* ctx, double* out) {
-  double* hres = ctx->hpin + (ctx->hpin.bytes / 8 - 8);
-  hipMemcpyAsync(hres, ctx->result, 5 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream);
-  int r = finish(ctx);
-  if (r) return r;
-  *out = hres[0];
-  r = status_code(ctx, hres[3], hres[4]);
-  if (r) *out = std::nan("");
+  Copies c{ctx};
+  int r = result_tail(c, "download the result", out);
+  if (status_failed(r)) *out = std::nan("");
   return r;
 }
 
@@ -200,14 +196,14 @@ int gram_host(lfm_ctx* ctx, const double* x, int64_t n, const lfm_hyp* hyp, doub
   r = ctx->A.reserve(ctx, (size_t)n * n * sizeof(OutT));
   if (r) return r;
   OutT* dA = reinterpret_cast<OutT*>(ctx->A.p);
-  hipMemcpyAsync(ctx->xin, x, n * 3 * 8, hipMemcpyHostToDevice, ctx->stream);
-  if (uplo == LFM_UPLO_LOWER) hipMemsetAsync(dA, 0, (size_t)n * n * sizeof(OutT), ctx->stream);
-  r = gram_impl<OutT>(ctx, x, ctx->xin, n, hyp, diag_add, uplo, dA, n);
+  Copies c{ctx};
+  c.up(ctx->xin, x, n * 3 * 8);
+  if (uplo == LFM_UPLO_LOWER) c.zero(dA, (size_t)n * n * sizeof(OutT));
+  r = c.done("upload x");
+  if (!r) r = gram_impl<OutT>(ctx, x, ctx->xin, n, hyp, diag_add, uplo, dA, n);
   if (r) return r;
-  hipError_t e = hipMemcpy2DAsync(out, ldo * sizeof(OutT), dA, n * sizeof(OutT),
-                                  n * sizeof(OutT), n, hipMemcpyDeviceToHost, ctx->stream);
-  if (e != hipSuccess) return hip_fail(ctx, e, "download gram");
-  return finish(ctx);
+  c.down2d(out, ldo * sizeof(OutT), dA, n * sizeof(OutT), n * sizeof(OutT), n);
+  return c.landed("download gram");
 }
 
 template <typename OutT>
@@ -287,6 +283,17 @@ void twins_drop(lfm_ctx* ctx) {
   ctx->ovl_stream = nullptr;
 }
 
+int sample_finish(lfm_ctx* ctx, const SamplePlan& P, const double* X, double* out, double* mean) {
+  Copies c{ctx};
+  c.down(out, X, P.x_bytes);
+  int r = result_tail(c, "download the samples");
+  if (r == LFM_E_NOT_PD) {
+    std::fill(out, out + P.nsamp * P.n, std::nan(""));
+    if (mean) std::fill(mean, mean + P.n, std::nan(""));
+  }
+  return r;
+}
+
 }  // namespace lfm
 
 // =================================================================== C ABI
@@ -305,11 +312,13 @@ int lfm_mean_function_f64(lfm_ctx* ctx, const double* x, int64_t n, const lfm_hy
   if (r) return r;
   r = ctx->xin.reserve(ctx, (size_t)n * 4 * 8);
   if (r) return r;
-  hipMemcpyAsync(ctx->xin, x, n * 3 * 8, hipMemcpyHostToDevice, ctx->stream);
-  r = launch_mean(ctx, st.h, ctx->xin, n, ctx->xin + 3 * n);
+  Copies c{ctx};
+  c.up(ctx->xin, x, n * 3 * 8);
+  r = c.done("upload x");
+  if (!r) r = launch_mean(ctx, st.h, ctx->xin, n, ctx->xin + 3 * n);
   if (r) return r;
-  hipMemcpyAsync(out, ctx->xin + 3 * n, n * 8, hipMemcpyDeviceToHost, ctx->stream);
-  return finish(ctx);
+  c.down(out, ctx->xin + 3 * n, n * 8);
+  return c.landed("download the mean");
 }
 
 int lfm_h_f64(lfm_ctx* ctx, const lfm_hyp* hyp, const int64_t* j, const int64_t* k,
@@ -327,14 +336,16 @@ int lfm_h_f64(lfm_ctx* ctx, const lfm_hyp* hyp, const int64_t* j, const int64_t*
   double* dt1 = ctx->xin + 2 * n;
   double* dt2 = ctx->xin + 3 * n;
   double* dout = ctx->xin + 4 * n;
-  hipMemcpyAsync(dj, j, n * 8, hipMemcpyHostToDevice, ctx->stream);
-  hipMemcpyAsync(dk, k, n * 8, hipMemcpyHostToDevice, ctx->stream);
-  hipMemcpyAsync(dt1, t1, n * 8, hipMemcpyHostToDevice, ctx->stream);
-  hipMemcpyAsync(dt2, t2, n * 8, hipMemcpyHostToDevice, ctx->stream);
-  r = launch_h(ctx, st.h, dj, dk, dt1, dt2, n, dout);
+  Copies c{ctx};
+  c.up(dj, j, n * 8);
+  c.up(dk, k, n * 8);
+  c.up(dt1, t1, n * 8);
+  c.up(dt2, t2, n * 8);
+  r = c.done("upload j / k / t1 / t2");
+  if (!r) r = launch_h(ctx, st.h, dj, dk, dt1, dt2, n, dout);
   if (r) return r;
-  hipMemcpyAsync(out, dout, n * 8, hipMemcpyDeviceToHost, ctx->stream);
-  return finish(ctx);
+  c.down(out, dout, n * 8);
+  return c.landed("download h");
 }
 
 int lfm_cross_covariance_f64(lfm_ctx* ctx, const double* x, int64_t n, const double* x2,
@@ -353,15 +364,15 @@ int lfm_cross_covariance_f64(lfm_ctx* ctx, const double* x, int64_t n, const dou
   if (r) return r;
   r = ctx->A.reserve(ctx, (size_t)n * m * 8);
   if (r) return r;
-  hipMemcpyAsync(ctx->xin, x, n * 3 * 8, hipMemcpyHostToDevice, ctx->stream);
-  hipMemcpyAsync(ctx->xin + 3 * n, x2, m * 3 * 8, hipMemcpyHostToDevice, ctx->stream);
-  r = launch_gram_direct<double>(ctx, st.h, ctx->xin, n, ctx->xin + 3 * n, m, 0.0, 0.0,
+  Copies c{ctx};
+  c.up(ctx->xin, x, n * 3 * 8);
+  c.up(ctx->xin + 3 * n, x2, m * 3 * 8);
+  r = c.done("upload x / x2");
+  if (!r) r = launch_gram_direct<double>(ctx, st.h, ctx->xin, n, ctx->xin + 3 * n, m, 0.0, 0.0,
                                  LFM_UPLO_FULL, ctx->A, m);
   if (r) return r;
-  hipError_t e = hipMemcpy2DAsync(out, ldo * 8, ctx->A, m * 8, m * 8, n, hipMemcpyDeviceToHost,
-                                  ctx->stream);
-  if (e != hipSuccess) return hip_fail(ctx, e, "download cross-covariance");
-  return finish(ctx);
+  c.down2d(out, ldo * 8, ctx->A, m * 8, m * 8, n);
+  return c.landed("download cross-covariance");
 }
 
 int lfm_gram_f64(lfm_ctx* ctx, const double* x, int64_t n, const lfm_hyp* hyp, double diag_add,
@@ -403,9 +414,10 @@ int lfm_mll_f64(lfm_ctx* ctx, const double* x, const double* y, int64_t n, const
   if (r) return r;
   r = ctx->xin.reserve(ctx, (size_t)n * 4 * 8);
   if (r) return r;
-  hipMemcpyAsync(ctx->xin, x, n * 3 * 8, hipMemcpyHostToDevice, ctx->stream);
-  hipMemcpyAsync(ctx->xin + 3 * n, y, n * 8, hipMemcpyHostToDevice, ctx->stream);
-  return mll_blocked(ctx, st, ctx->xin, ctx->xin + 3 * n, nullptr, n, hyp, negative, out);
+  Copies c{ctx};
+  up_xy(c, x, y, n);
+  r = c.done("upload x / y");
+  return r ? r : mll_blocked(ctx, st, ctx->xin, ctx->xin + 3 * n, nullptr, n, hyp, negative, out);
 }
 
 int lfm_mll_grad_f64(lfm_ctx* ctx, const double* x, const double* y, int64_t n,
@@ -420,14 +432,14 @@ int lfm_mll_grad_f64(lfm_ctx* ctx, const double* x, const double* y, int64_t n,
   if (r) return r;
   const double* d_x = ctx->xin;
   const double* d_y = ctx->xin + 3 * n;
-  hipMemcpyAsync(ctx->xin, x, n * 3 * 8, hipMemcpyHostToDevice, ctx->stream);
-  hipMemcpyAsync(ctx->xin + 3 * n, y, n * 8, hipMemcpyHostToDevice, ctx->stream);
+  Copies up{ctx};
+  up_xy(up, x, y, n);
+  r = up.done("upload x / y");
   // bordered 2Mp x 2Mp matrix [[S_aug, .], [I, 0]] (lfm_grad.hip)
   const int64_t Mp = round_up(n + 1, 128), M2 = 2 * Mp;
-  r = ctx->A.reserve(ctx, (size_t)M2 * M2 * sizeof(double));
-  if (r) return r;
+  if (!r) r = ctx->A.reserve(ctx, (size_t)M2 * M2 * sizeof(double));
   const int64_t G = hyp->num_genes;
-  r = ctx->gacc.reserve(ctx, (size_t)(5 * G + 3) * sizeof(double));
+  if (!r) r = ctx->gacc.reserve(ctx, (size_t)(5 * G + 3) * sizeof(double));
   if (r) return r;
   DeviceTenancy tenancy(ctx, s3_on(ctx));  // held to the final synchronise (finish)
   return with_s3_fallback(ctx, [&]() -> int {
@@ -440,15 +452,12 @@ int lfm_mll_grad_f64(lfm_ctx* ctx, const double* x, const double* y, int64_t n,
     const size_t ng = (size_t)(3 * G + 2);
     r = ctx->hpin.reserve(ctx, (ng + 16) * sizeof(double));
     if (r) return r;
-    double* hres = ctx->hpin;
-    hipMemcpyAsync(hres, ctx->result, 5 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream);
-    hipMemcpyAsync(hres + 8, d_out, ng * sizeof(double), hipMemcpyDeviceToHost, ctx->stream);
-    r = finish(ctx);
-    if (r) return r;
-    *value = hres[0];
-    std::memcpy(grad, hres + 8, ng * sizeof(double));
-    r = status_code(ctx, hres[3], hres[4]);
-    if (r) {
+    Copies c{ctx};
+    c.down(ctx->hpin, d_out, ng * sizeof(double));
+    r = result_tail(c, "download the gradient", value);
+    if (r == LFM_OK) {
+      std::memcpy(grad, ctx->hpin, ng * sizeof(double));
+    } else if (status_failed(r)) {
       *value = std::nan("");
       for (size_t i = 0; i < ng; ++i) grad[i] = std::nan("");
     }
@@ -482,23 +491,18 @@ int lfm_posterior_f64(lfm_ctx* ctx, const double* x, const double* y, int64_t n,
   double* d_t = d_v + n;
   double* d_mean = d_t + 3 * m;
   double* d_cov = d_mean + m;
-  hipMemcpyAsync(d_x, x, n * 3 * 8, hipMemcpyHostToDevice, ctx->stream);
-  hipMemcpyAsync(d_y, y, n * 8, hipMemcpyHostToDevice, ctx->stream);
-  if (diag_vec) hipMemcpyAsync(d_v, diag_vec, n * 8, hipMemcpyHostToDevice, ctx->stream);
-  hipMemcpyAsync(d_t, t, m * 3 * 8, hipMemcpyHostToDevice, ctx->stream);
-  r = posterior_blocked(ctx, st.h, d_x, d_y, n, diag_vec ? d_v : nullptr, diag_add, d_t, m,
+  Copies c{ctx};
+  up_xy(c, x, y, n);
+  if (diag_vec) c.up(d_v, diag_vec, n * 8);
+  c.up(d_t, t, m * 3 * 8);
+  r = c.done("upload x / y / diag_vec / t");
+  if (!r) r = posterior_blocked(ctx, st.h, d_x, d_y, n, diag_vec ? d_v : nullptr, diag_add, d_t, m,
                         d_mean, d_cov);
   if (r) return r;
-  r = ctx->hpin.reserve(ctx, 64 * sizeof(double));
-  if (r) return r;
-  double* hres = ctx->hpin;
-  hipMemcpyAsync(hres, ctx->result, 5 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream);
-  hipMemcpyAsync(mean, d_mean, m * 8, hipMemcpyDeviceToHost, ctx->stream);
-  hipMemcpyAsync(cov, d_cov, (size_t)m * m * 8, hipMemcpyDeviceToHost, ctx->stream);
-  r = finish(ctx);
-  if (r) return r;
-  r = status_code(ctx, hres[3], hres[4]);
-  if (r) {
+  c.down(mean, d_mean, m * 8);
+  c.down(cov, d_cov, (size_t)m * m * 8);
+  r = result_tail(c, "download mean / cov");
+  if (status_failed(r)) {
     const double nan = std::nan("");
     for (int64_t i = 0; i < m; ++i) mean[i] = nan;
     for (int64_t i = 0; i < m * m; ++i) cov[i] = nan;
@@ -630,7 +634,6 @@ int lfm_mll_multi_f64(lfm_ctx* ctx, lfm_data* data, int64_t nsets, const lfm_hyp
       return r;
     }
   }
-  auto hres = [&](lfm_ctx* t) { return t->hpin + (t->hpin.bytes / 8 - 8); };
   // enqueue set k on workspace k % 2, its prologue gated on set k - 1's tail
   auto enqueue = [&](int64_t k) -> int {
     lfm_ctx* t = tw[k & 1];
@@ -642,9 +645,11 @@ int lfm_mll_multi_f64(lfm_ctx* ctx, lfm_data* data, int64_t nsets, const lfm_hyp
     if (!r) r = mll_enqueue(t, st, data->d_x, data->d_y, nullptr, n, &hyps[k], negative);
     if (!r) {
       hipStreamWaitEvent(ctx->stream, t->ovl_done, 0);
-      hipMemcpyAsync(hres(t), t->result, 5 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream);
+      Copies c{ctx};  // the workspace's result on the primary's stream
+      c.down(result_words(t), t->result, 5 * sizeof(double));
       hipEventRecord(t->ovl_res, ctx->stream);
-      r = hip_fail(ctx, hipGetLastError(), "restart pipeline enqueue");
+      r = c.done("restart pipeline result copy");
+      if (!r) r = hip_fail(ctx, hipGetLastError(), "restart pipeline enqueue");
     } else {
       ctx->err = t->err;
     }
@@ -655,7 +660,7 @@ int lfm_mll_multi_f64(lfm_ctx* ctx, lfm_data* data, int64_t nsets, const lfm_hyp
     lfm_ctx* t = tw[k & 1];
     hipError_t e = hipEventSynchronize(t->ovl_res);
     if (e != hipSuccess) return hip_fail(ctx, e, "restart pipeline result");
-    const double* h = hres(t);
+    const double* h = result_words(t);
     out[k] = h[0];
     int r = status_code(t, h[3], h[4]);
     if (status) status[k] = r;
@@ -734,22 +739,70 @@ int lfm_log_prob_f64(lfm_ctx* ctx, const double* loc, const double* scale, int64
   if (r) return r;
   r = ctx->xin.reserve(ctx, (size_t)n * 2 * 8);
   if (r) return r;
-  hipMemcpyAsync(ctx->xin, loc, n * 8, hipMemcpyHostToDevice, ctx->stream);
-  hipMemcpyAsync(ctx->xin + n, y, n * 8, hipMemcpyHostToDevice, ctx->stream);
-  r = ctx->hpin.reserve(ctx, 1 << 16);
+  Copies c{ctx};
+  c.up(ctx->xin, loc, n * 8);
+  c.up(ctx->xin + n, y, n * 8);
+  r = c.done("upload loc / y");
+  if (!r) r = ctx->hpin.reserve(ctx, 1 << 16);
   if (r) return r;
   DeviceTenancy tenancy(ctx, s3_on(ctx));  // held to the final synchronise (finish)
   return with_s3_fallback(ctx, [&]() -> int {
     // the factorisation overwrites A: a fallback re-run uploads scale again
-    hipError_t e = hipMemcpy2DAsync(ctx->A, Mp * 8, scale, lds * 8, n * 8, n,
-                                    hipMemcpyHostToDevice, ctx->stream);
-    if (e != hipSuccess) return hip_fail(ctx, e, "upload scale");
+    Copies c{ctx};
+    c.up2d(ctx->A, Mp * 8, scale, lds * 8, n * 8, n);
+    int r = c.done("upload scale");
+    if (r) return r;
     HypDev h{nullptr, nullptr, nullptr, 1, 1.0};
-    int r = launch_augment(ctx, h, nullptr, ctx->xin + n, ctx->xin, n, ctx->A, Mp, Mp);
+    r = launch_augment(ctx, h, nullptr, ctx->xin + n, ctx->xin, n, ctx->A, Mp, Mp);
     if (r) return r;
     r = chol_factor_solve(ctx, ctx->A, Mp, n, Mp, 0, ctx->result);
     return r ? r : read_result(ctx, out);
   });
+}
+
+int lfm_randn_f64(lfm_ctx* ctx, uint64_t seed, int64_t sample0, int64_t nsamp, int64_t n,
+                  double* out) {
+  if (!ctx) return LFM_E_ARG;
+  if (!out) return set_err(ctx, LFM_E_ARG, "out is NULL");
+  const SamplePlan P = plan_sample(n, nsamp, sample0);
+  if (P.reject) return set_err(ctx, LFM_E_ARG, P.why);
+  DeviceGuard g(ctx->device);
+  DeviceTenancy tenancy(ctx, false);  // no factorisation: shared
+  // the generator alone: nsamp rows of ld = n rounded up to a pair
+  const int64_t ld = (n + 1) / 2 * 2, pairs = nsamp * (ld / 2);
+  int r = ctx->smp_z.reserve(ctx, (size_t)nsamp * ld * sizeof(double));
+  if (r) return r;
+  launch_randn(ctx, ctx->smp_z, ld, nsamp, pairs,
+               (int)std::min<int64_t>((pairs + 255) / 256, SAMPLE_RANDN_GRID), seed, sample0);
+  r = hip_fail(ctx, hipGetLastError(), "sample_randn_kernel");
+  if (r) return r;
+  Copies c{ctx};
+  c.down2d(out, n * 8, ctx->smp_z, ld * 8, n * 8, nsamp);
+  return c.landed("download the normals");
+}
+
+int lfm_mvn_sample_f64(lfm_ctx* ctx, const double* loc, const double* scale, int64_t n,
+                       int64_t lds, uint64_t seed, int64_t sample0, int64_t nsamp, double* out) {
+  if (!ctx) return LFM_E_ARG;
+  if (!loc || !scale || !out) return set_err(ctx, LFM_E_ARG, "loc / scale / out is NULL");
+  const SamplePlan P = plan_sample(n, nsamp, sample0);
+  if (P.reject) return set_err(ctx, LFM_E_ARG, P.why);
+  if (lds < n) return set_err(ctx, LFM_E_ARG, "lds must be >= n");
+  DeviceGuard g(ctx->device);
+  int r = ctx->A.reserve(ctx, P.mat_bytes);
+  if (!r) r = ctx->smp_z.reserve(ctx, P.z_bytes);
+  if (!r) r = ctx->smp_x.reserve(ctx, P.x_bytes);
+  if (!r) r = ctx->xin.reserve(ctx, (size_t)n * sizeof(double));
+  if (!r) r = ctx->hpin.reserve(ctx, 1 << 16);
+  if (r) return r;
+  DeviceTenancy tenancy(ctx, false);  // CHOL_RESIDENT is schedule 1: shared
+  Copies c{ctx};
+  c.up(ctx->xin, loc, n * 8);
+  c.up2d(ctx->A, P.Mp * 8, scale, lds * 8, n * 8, n);
+  r = c.done("upload loc / scale");
+  if (!r) r = sample_enqueue(ctx, P, ctx->A, ctx->xin, seed, ctx->smp_z, ctx->smp_x);
+  if (r) return r;
+  return sample_finish(ctx, P, ctx->smp_x, out, nullptr);
 }
 
 }  // extern "C"

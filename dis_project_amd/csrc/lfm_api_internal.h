@@ -1,5 +1,6 @@
 // lfm_api_internal.h — what the units of the extern "C" boundary share (lfm_ctx.hip, lfm_api.hip,
-// lfm_batch.hip, lfm_mbatch.hip, lfm_farm.hip). The kernel units see lfm_internal.h only.
+// lfm_post_api.hip, lfm_batch.hip, lfm_mbatch.hip, lfm_farm.hip). The kernel units see
+// lfm_internal.h only.
 #pragma once
 
 #include <algorithm>
@@ -68,12 +69,25 @@ hipError_t alloc_fixed(lfm_ctx* ctx);
 inline int64_t round_up(int64_t a, int64_t b) { return (a + b - 1) / b * b; }
 
 // A call's copies on ctx->stream, in the order given; after the first that fails the rest do
-// nothing. e may start as an earlier step's error: the copies then do nothing at all.
+// nothing. e may start as an earlier step's error: the copies then do nothing at all. The strided
+// forms move `rows` rows of `width` bytes between pitches dp and sp (bytes).
 struct Copies {
   lfm_ctx* ctx;
   hipError_t e = hipSuccess;
   void up(void* dst, const void* src, size_t n) { copy(dst, src, n, hipMemcpyHostToDevice); }
   void down(void* dst, const void* src, size_t n) { copy(dst, src, n, hipMemcpyDeviceToHost); }
+  void up2d(void* dst, size_t dp, const void* src, size_t sp, size_t width, size_t rows) {
+    copy2d(dst, dp, src, sp, width, rows, hipMemcpyHostToDevice);
+  }
+  void down2d(void* dst, size_t dp, const void* src, size_t sp, size_t width, size_t rows) {
+    copy2d(dst, dp, src, sp, width, rows, hipMemcpyDeviceToHost);
+  }
+  void dev2d(void* dst, size_t dp, const void* src, size_t sp, size_t width, size_t rows) {
+    copy2d(dst, dp, src, sp, width, rows, hipMemcpyDeviceToDevice);
+  }
+  void zero(void* dst, size_t n) {
+    if (e == hipSuccess) e = hipMemsetAsync(dst, 0, n, ctx->stream);
+  }
   // the first failure as `what`, or LFM_OK
   int done(const char* what) { return hip_fail(ctx, e, what); }
   // the end of a call's downloads: done(what), then the stream synchronised
@@ -86,7 +100,24 @@ struct Copies {
   void copy(void* dst, const void* src, size_t bytes, hipMemcpyKind kind) {
     if (e == hipSuccess) e = hipMemcpyAsync(dst, src, bytes, kind, ctx->stream);
   }
+  void copy2d(void* dst, size_t dp, const void* src, size_t sp, size_t width, size_t rows,
+              hipMemcpyKind kind) {
+    if (e == hipSuccess) e = hipMemcpy2DAsync(dst, dp, src, sp, width, rows, kind, ctx->stream);
+  }
 };
+
+// Where a factorising call's five result words land: the last 8 doubles of ctx->hpin. stage_hyp
+// stages from hpin's start and leaves 1 KiB beyond what it uploads, and a call's other pinned
+// download (the gradient's ng doubles) starts at hpin[0] in a reservation of ng + 16, so neither
+// reaches them.
+inline double* result_words(lfm_ctx* ctx) { return ctx->hpin + (ctx->hpin.bytes / 8 - 8); }
+// The end of a factorising call: ctx->result's five words to result_words(ctx) after the downloads
+// already queued on c, c.landed(what), then the status word's code (LFM_OK, LFM_E_NOT_PD,
+// LFM_E_TIMEOUT). *value (optional) is word 0 whenever the copies landed. LFM_E_STATE if the
+// caller has not reserved 64 doubles of hpin. What to NaN-fill on which code is the caller's.
+int result_tail(Copies& c, const char* what, double* value = nullptr);
+// r is one of the status word's failures: the copies landed, the results are not valid
+inline bool status_failed(int r) { return r == LFM_E_NOT_PD || r == LFM_E_TIMEOUT; }
 
 // ------------------------------------------- the on-device fits' host half (both batches)
 // The kernels' optimiser from the caller's and the count of the steps already taken
@@ -127,6 +158,15 @@ inline int validate_x(lfm_ctx* ctx, const void* x, int64_t n) {
   return LFM_OK;
 }
 
+inline int check_hyp(lfm_ctx* ctx, const lfm_hyp* hyp) {
+  if (!hyp) return set_err(ctx, LFM_E_ARG, "hyp is NULL");
+  if (hyp->num_genes < 1 || hyp->num_genes > (1 << 20))
+    return set_err(ctx, LFM_E_ARG, "num_genes must be in [1, 2^20]");
+  if (!hyp->true_d || !hyp->true_s || !hyp->true_b)
+    return set_err(ctx, LFM_E_ARG, "hyp true_d / true_s / true_b must not be NULL");
+  return LFM_OK;
+}
+
 inline int check_mean_shape(lfm_ctx* ctx, int64_t n, const lfm_hyp* hyp) {
   // mean_function (model.py:145-149) repeats B/D in blocks of n // num_genes; the
   // reference's broadcast only succeeds when those blocks tile n exactly.
@@ -139,6 +179,9 @@ inline int check_mean_shape(lfm_ctx* ctx, int64_t n, const lfm_hyp* hyp) {
 // ------------------------------------------------------------ lfm_api.hip
 // Drain and free the restart pipeline's workspaces and its overlap stream
 void twins_drop(lfm_ctx* ctx);
+// The end of a sampling call: X (P.x_bytes) and the factorisation's status to the host,
+// synchronised. Not positive definite: out (and mean, if given) NaN and LFM_E_NOT_PD.
+int sample_finish(lfm_ctx* ctx, const SamplePlan& P, const double* X, double* out, double* mean);
 
 // ---------------------------------------------------------- lfm_batch.hip
 // small-N batch through one launch; probs already validated

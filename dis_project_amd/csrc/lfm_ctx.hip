@@ -367,6 +367,17 @@ int finish(lfm_ctx* ctx) {
   return LFM_OK;
 }
 
+int result_tail(Copies& c, const char* what, double* value) {
+  lfm_ctx* ctx = c.ctx;
+  if (ctx->hpin.bytes < 64 * sizeof(double))
+    return set_err(ctx, LFM_E_STATE, "result tail: the pinned staging was not reserved");
+  const double* hres = result_words(ctx);
+  c.down(result_words(ctx), ctx->result, 5 * sizeof(double));
+  if (int r = c.landed(what)) return r;
+  if (value) *value = hres[0];
+  return status_code(ctx, hres[3], hres[4]);
+}
+
 // ------------------------------------------------------ schedule-3 stall fallback
 // A schedule-3 factorisation whose device-side waits ran out (LFM_E_TIMEOUT after the time
 // bound, lfm_chol.hip: another tenant of the GPU starved the chain's co-resident workgroups, or

@@ -5,7 +5,7 @@
 // with lfm_small_plan.h the small-problem path's LDS map, staging and buffer layouts and its
 // launch plans (plan_small_*, which lfm_small.hip and lfm_batch.hip only read); and the resident
 // posterior's predict plan and its held-out log density's (plan_post, plan_post_logp, which
-// lfm_post.hip only reads); with lfm_mid_plan.h the
+// lfm_post.hip and lfm_post_api.hip only read); with lfm_mid_plan.h the
 // mid-size resident batch's arenas and launch plans (plan_mid, plan_mid_post, plan_mid_fit,
 // plan_mid_draw, which lfm_mbatch.hip and lfm_mid.hip only read); and
 // the joint samples' generator and launch plan (plan_sample, which lfm_sample.hip only reads).

@@ -312,7 +312,7 @@ int launch_gram_region(lfm_ctx* ctx, const GramGen& g, int64_t r0, int64_t r1, i
 // the factorisation (lfm_chol_sched.hip; its kernels: lfm_chol.hip, lfm_chol.h)
 // CHOL_RESIDENT: CHOL_MLL's matrix and plan, but always on schedule 1, which leaves L in A's
 // lower triangle and z in row n (schedule 3 keeps its panels in separate buffers); the
-// resident posterior's fit (lfm_post.hip)
+// resident posterior's fit (lfm_post_api.hip)
 enum CholMode { CHOL_MLL = 0, CHOL_INVERSE = 1, CHOL_SCHUR = 2, CHOL_RESIDENT = 3 };
 // gen: the gram to fuse (lfm_api decides with chol_fuses_gram; the full gram is then NOT in A)
 int chol_factor_solve(lfm_ctx* ctx, double* A, int64_t lda, int64_t n, int64_t Mp, int negative,
@@ -325,15 +325,50 @@ bool chol_fuses_gram(const lfm_ctx* ctx, int mode, const GridLayout& lay, int64_
 // sizes). Nothing is downloaded and nothing synchronised.
 int sample_enqueue(lfm_ctx* ctx, const SamplePlan& P, double* A, const double* d_loc,
                    uint64_t seed, double* Z, double* X);
-// Its two halves, for a caller that reads the factor itself (lfm_post.hip). scale_factor: the
+// Its two halves, for a caller that reads the factor itself (lfm_post_api.hip). scale_factor: the
 // augmented row with residual 0 and the factorisation of A (stride Mp, scale n x n) in place, so
 // that ctx->result[0] = -1/2 logdet - (n / 2) log 2 pi. sample_draw: everything after it.
 int scale_factor(lfm_ctx* ctx, double* A, int64_t n, int64_t Mp, const double* d_loc);
 int sample_draw(lfm_ctx* ctx, const SamplePlan& P, double* A, const double* d_loc, uint64_t seed,
                 double* Z, double* X);
-// The end of a sampling call: X and the factorisation's status to the host, synchronised. Not
-// positive definite: out (and mean, if given) NaN and LFM_E_NOT_PD.
-int sample_finish(lfm_ctx* ctx, const SamplePlan& P, const double* X, double* out, double* mean);
+// The generator alone: rows x ld normals (ld even, pairs = rows ld / 2) of samples sample0 ...
+void launch_randn(lfm_ctx* ctx, double* Z, int64_t ld, int64_t rows, int64_t pairs, int grid,
+                  uint64_t seed, int64_t sample0);
+
+// The resident posterior (lfm_post.hip: the kernels and these launches, one per step of a call;
+// lfm_post_api.hip: the handle and its calls). The sweep kernels' arguments:
+struct PostArgs {
+  double* Vt;         // the chunk's rows x Np
+  int64_t ldv;
+  const double* L;
+  int64_t ldl;
+  const double* dinv;
+  const double* z;
+  int64_t K0;         // the super-panel's first column
+  int w;              // its width in block columns
+  int tj0;            // update: first block column to the right
+  double* s2;         // per-row sum v^2 over the columns solved so far
+  double* sz;         // per-row sum v z
+};
+// The fit's matrix in L (stride Mp): S = (K + diag_add I) + diag(d_v) (d_v may be NULL), row n
+int post_sigma(lfm_ctx* ctx, const HypDev& h, const double* x, const double* d_y,
+               const double* d_v, int64_t n, double diag_add, double* L, int64_t Mp);
+// A factor as the sweep reads it: z = its row n, row n an identity row, dinv = the inverses of
+// its 16 x 16 diagonal blocks. The grids are the caller's. Launches only.
+void post_factor_ready(lfm_ctx* ctx, double* L, int64_t ldl, int64_t n, int64_t Np, double* z,
+                       double* dinv, unsigned z_grid, unsigned dinv_grid);
+// One chunk of a predict as the plan lists it: mean into out [m] and var into out + m
+int post_chunk(lfm_ctx* ctx, const PostArgs& g, const ResidentPlan& P, const PostChunk& c,
+               const HypDev& h, const double* x, const double* t, double* out);
+// cov (m x m, dense) = K(t, t) - Vt Vt^T from the single chunk's solved Vt
+int post_cov(lfm_ctx* ctx, const HypDev& h, const ResidentPlan& P, const double* t,
+             const double* Vt, double* cov);
+// diag_add on A's diagonal in one addition, then scale_factor (lfm_sample.hip) on it
+int post_shift_factor(lfm_ctx* ctx, double* A, int64_t m, int64_t Mp, double diag_add,
+                      const double* d_loc);
+// One pass of held-out rows, already in a.Vt: lp[r] = ctx->result[0] - 0.5 s2[r] after the sweep
+int post_logp_pass(lfm_ctx* ctx, const PostArgs& a, const PostLogpPlan& P, const PostChunk& c,
+                   const double* mean, double* lp);
 
 // gradient kernels (lfm_grad.hip)
 int launch_border_init(lfm_ctx* ctx, double* A, int64_t lda, int64_t Mp);

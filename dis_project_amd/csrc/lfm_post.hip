@@ -1,5 +1,6 @@
 // lfm_post.hip — the resident posterior (include/lfm.h lfm_post_*): factor a large model once,
-// predict many times.
+// predict many times. The kernels and the functions that launch them, one per step of a call;
+// the handle and the entry points are lfm_post_api.hip's.
 //
 // Reference: ExactLFM.latent_predict / multi_gene_predict, src/model.py:420-514:
 //     mean = m(t) + K(t,x) S^{-1} (y - m(x)),   cov = K(t,t) - K(t,x) S^{-1} K(x,t),
@@ -35,34 +36,10 @@
 //                       accumulator s2 is ||L^{-1} (ystar_r - mean)||^2;
 //   post_logp_kernel    logp[r] = base - 0.5 * s2[r].
 // Every size, grid and pass is plan_post_logp's (lfm_host.cpp).
-#include "lfm_api_internal.h"
+#include "lfm_internal.h"
 #include "lfm_chol_dev.h"
 
 using namespace lfm;
-
-struct lfm_post {
-  lfm_ctx* owner = nullptr;  // the creating context: takes lfm_post_set_chunk's message
-  int device = 0;
-  int64_t n = 0, Np = 0, Mp = 0, G = 0;
-  int64_t chunk = 0;         // 0: post_default_chunk(Np)
-  double l = 0.0;
-  // fixed at creation
-  double* L = nullptr;       // Mp x Mp, Mp = round_up(n + 1, 128): the factor, lower triangle
-  double* dinv = nullptr;    // Np / 128 x 8 inverses of L's 16 x 16 diagonal blocks
-  double* z = nullptr;       // [Np], zero from n
-  double* x = nullptr;       // [n x 3]
-  double* par = nullptr;     // D, S, B
-  // grown by the predicts (ResidentPlan's byte counts)
-  double *vt = nullptr, *acc = nullptr, *t = nullptr, *out = nullptr, *cov = nullptr;
-  size_t vt_cap = 0, acc_cap = 0, t_cap = 0, out_cap = 0, cov_cap = 0;
-  // grown by the samples (SamplePlan's byte counts): the covariance's factor, Z and X
-  double *smat = nullptr, *sz = nullptr, *sx = nullptr;
-  size_t smat_cap = 0, sz_cap = 0, sx_cap = 0;
-  // grown by the log densities (PostLogpPlan's byte counts): the inverses of the covariance
-  // factor's diagonal blocks, the sweep's zero z and one pass's results
-  double *sdinv = nullptr, *szero = nullptr, *lp = nullptr;
-  size_t sdinv_cap = 0, szero_cap = 0, lp_cap = 0;
-};
 
 namespace lfm {
 namespace {
@@ -106,20 +83,6 @@ __global__ __launch_bounds__(128) void post_dinv_kernel(const double* __restrict
 }
 
 // --------------------------------------------------------------- predict
-struct PostArgs {
-  double* Vt;         // the chunk's rows x Np
-  int64_t ldv;
-  const double* L;
-  int64_t ldl;
-  const double* dinv;
-  const double* z;
-  int64_t K0;         // the super-panel's first column
-  int w;              // its width in block columns
-  int tj0;            // update: first block column to the right
-  double* s2;         // per-row sum v^2 over the columns solved so far
-  double* sz;         // per-row sum v z
-};
-
 // Columns [n, Np) of the chunk's rows and the whole of its padding rows [rows, pad_rows): zero
 __global__ void post_pad_kernel(double* __restrict__ Vt, int64_t ldv, int64_t n, int64_t rows) {
   const int64_t row = blockIdx.y;
@@ -337,180 +300,10 @@ __global__ __launch_bounds__(256, 2) void post_cov_kernel(const double* __restri
     }
 }
 
-// ------------------------------------------------------------------ host
-int grow(lfm_ctx* ctx, double** p, size_t* cap, size_t bytes, const char* what) {
-  if (bytes <= *cap) return LFM_OK;
-  // every call ends synchronised: nothing in flight reads the old allocation
-  if (*p) hipFree(*p);
-  *p = nullptr;
-  *cap = 0;
-  if (hipMalloc((void**)p, bytes) != hipSuccess) {
-    (void)hipGetLastError();
-    *p = nullptr;
-    return set_err(ctx, LFM_E_OOM, std::string("out of device memory: ") + what + " needs " +
-                                       std::to_string(bytes) + " bytes");
-  }
-  *cap = bytes;
-  return LFM_OK;
-}
-
-void release(lfm_post* q) {
-  for (double* p : {q->L, q->dinv, q->z, q->x, q->par, q->vt, q->acc, q->t, q->out, q->cov,
-                    q->smat, q->sz, q->sx, q->sdinv, q->szero, q->lp})
-    if (p) hipFree(p);
-  delete q;
-}
-
-int post_fit(lfm_ctx* ctx, lfm_post* q, const double* x, const double* y, const double* diag_vec,
-             double diag_add, const lfm_hyp* hyp) {
-  const int64_t n = q->n, G = q->G, Np = q->Np, Mp = q->Mp;
-  auto alloc = [&](double** p, size_t count, const char* what) {
-    size_t cap = 0;
-    return grow(ctx, p, &cap, count * sizeof(double), what);
-  };
-  int r = alloc(&q->L, (size_t)Mp * Mp, "the resident factor");
-  if (!r) r = alloc(&q->dinv, (size_t)(Np / NB) * NB * IB, "the diagonal inverses");
-  if (!r) r = alloc(&q->z, (size_t)Np, "z");
-  if (!r) r = alloc(&q->x, (size_t)n * 3, "x");
-  if (!r) r = alloc(&q->par, (size_t)G * 3, "the hyperparameters");
-  // y and the variances are only read while S is built: the ctx's staging
-  if (!r) r = ctx->xin.reserve(ctx, (size_t)n * 2 * sizeof(double));
-  if (!r) r = ctx->hpin.reserve(ctx, 64 * sizeof(double));
-  if (r) return r;
-  hipStream_t st = ctx->stream;
-  double* d_y = ctx->xin;
-  double* d_v = d_y + n;
-  hipMemcpyAsync(q->x, x, n * 3 * 8, hipMemcpyHostToDevice, st);
-  hipMemcpyAsync(d_y, y, n * 8, hipMemcpyHostToDevice, st);
-  if (diag_vec) hipMemcpyAsync(d_v, diag_vec, n * 8, hipMemcpyHostToDevice, st);
-  hipMemcpyAsync(q->par, hyp->true_d, G * 8, hipMemcpyHostToDevice, st);
-  hipMemcpyAsync(q->par + G, hyp->true_s, G * 8, hipMemcpyHostToDevice, st);
-  hipMemcpyAsync(q->par + 2 * G, hyp->true_b, G * 8, hipMemcpyHostToDevice, st);
-  r = hip_fail(ctx, hipGetLastError(), "resident posterior: upload");
-  if (r) return r;
-  const HypDev h{q->par, q->par + G, q->par + 2 * G, (int)G, q->l};
-  r = launch_gram_direct<double>(ctx, h, q->x, n, q->x, n, diag_add, 0.0, LFM_UPLO_LOWER, q->L, Mp);
-  if (r) return r;
-  if (diag_vec)
-    hipLaunchKernelGGL(post_diag_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, q->L,
-                       Mp, d_v, n);
-  r = launch_augment(ctx, h, q->x, d_y, nullptr, n, q->L, Mp, Mp);
-  if (r) return r;
-  r = chol_factor_solve(ctx, q->L, Mp, n, Mp, 0, ctx->result, CHOL_RESIDENT);
-  if (r) return r;
-  hipLaunchKernelGGL(post_z_kernel, dim3((unsigned)((Np + 255) / 256)), dim3(256), 0, st, q->L, Mp,
-                     n, Np, q->z);
-  hipLaunchKernelGGL(post_dinv_kernel, dim3((unsigned)(Np / NB)), dim3(128), 0, st, q->L, Mp,
-                     q->dinv);
-  r = hip_fail(ctx, hipGetLastError(), "post_dinv_kernel");
-  if (r) return r;
-  double* hres = ctx->hpin;
-  hipMemcpyAsync(hres, ctx->result, 5 * sizeof(double), hipMemcpyDeviceToHost, st);
-  r = finish(ctx);
-  if (r) return r;
-  return status_code(ctx, hres[3], hres[4]);
-}
-
-// The right-looking sweep of one chunk's rows (g.Vt) against a factor (g.L, g.dinv, g.z): the
-// plan's panel and update launches in order
-void post_sweep(lfm_ctx* ctx, PostArgs g, const ResidentPlan& P, const PostChunk& c) {
-  hipStream_t st = ctx->stream;
-  const double prow = (double)c.panel_grid * 64;
-  for (const PostPanel& s : P.panels) {
-    g.K0 = s.K0;
-    g.w = s.w;
-    g.tj0 = s.tj0;
-    hipEvent_t ev;
-    prof_begin(ctx, K_POST_PANEL, &ev);
-    hipLaunchKernelGGL(post_panel_kernel, dim3((unsigned)c.panel_grid), dim3(256), 0, st, g);
-    prof_end(ctx, K_POST_PANEL, ev, prow * NB * NB * s.w * s.w, 2.0 * prow * NB * s.w * 8);
-    if (s.ntj > 0) {
-      prof_begin(ctx, K_POST_UPDATE, &ev);
-      hipLaunchKernelGGL(post_update_kernel, dim3((unsigned)c.tiles, (unsigned)s.ntj), dim3(256),
-                         0, st, g);
-      prof_end(ctx, K_POST_UPDATE, ev, 2.0 * c.pad_rows * NB * s.ntj * NB * s.w,
-               2.0 * c.pad_rows * NB * s.ntj * 8);
-    }
-  }
-}
-
-// The launches of one chunk, exactly as the plan lists them
-int post_chunk(lfm_ctx* ctx, lfm_post* q, const ResidentPlan& P, const PostChunk& c,
-               const HypDev& h) {
-  hipStream_t st = ctx->stream;
-  const int64_t Np = P.Np;
-  hipLaunchKernelGGL(post_pad_kernel, dim3(1, (unsigned)c.pad_rows), dim3(256), 0, st, q->vt, Np,
-                     q->n, c.rows);
-  int r = launch_gram_direct<double>(ctx, h, q->t + c.q0 * 3, c.rows, q->x, q->n, 0.0, 0.0,
-                                     LFM_UPLO_FULL, q->vt, Np);
-  if (r) return r;
-  PostArgs g{};
-  g.Vt = q->vt;
-  g.ldv = Np;
-  g.L = q->L;
-  g.ldl = q->Mp;
-  g.dinv = q->dinv;
-  g.z = q->z;
-  g.s2 = q->acc;
-  g.sz = q->acc + P.vt_rows;
-  post_sweep(ctx, g, P, c);
-  hipLaunchKernelGGL(post_finish_kernel, dim3((unsigned)((c.rows + 255) / 256)), dim3(256), 0, st,
-                     h, q->t, c.q0, c.rows, P.m, g.s2, g.sz, q->out, q->out + P.m);
-  return hip_fail(ctx, hipGetLastError(), "resident posterior: chunk launches");
-}
-
-// One predict with the covariance when the plan has it, left on the device: mean in q->out [m],
-// var in q->out + m (marginals only), cov in q->cov (m x m, dense). Nothing is downloaded.
-int post_enqueue(lfm_ctx* ctx, lfm_post* q, const ResidentPlan& P, const double* t) {
-  const bool cov = P.cov_bytes != 0;
-  int r = grow(ctx, &q->vt, &q->vt_cap, P.vt_bytes, "the solve workspace");
-  if (!r) r = grow(ctx, &q->acc, &q->acc_cap, P.acc_bytes, "the row accumulators");
-  if (!r) r = grow(ctx, &q->t, &q->t_cap, P.t_bytes, "the test inputs");
-  if (!r) r = grow(ctx, &q->out, &q->out_cap, P.out_bytes, "mean / var");
-  if (!r && cov) r = grow(ctx, &q->cov, &q->cov_cap, P.cov_bytes, "the covariance");
-  if (r) return r;
-  hipStream_t st = ctx->stream;
-  const int64_t G = q->G, m = P.m;
-  const HypDev h{q->par, q->par + G, q->par + 2 * G, (int)G, q->l};
-  hipMemcpyAsync(q->t, t, P.t_bytes, hipMemcpyHostToDevice, st);
-  for (const PostChunk& c : P.chunks) {
-    r = post_chunk(ctx, q, P, c, h);
-    if (r) return r;
-  }
-  if (cov) {
-    // one chunk (the plan rejected anything else): its Vt is whole
-    r = launch_gram_direct<double>(ctx, h, q->t, m, q->t, m, 0.0, 0.0, LFM_UPLO_LOWER, q->cov, m);
-    if (r) return r;
-    hipLaunchKernelGGL(post_cov_kernel, dim3((unsigned)P.cov_tiles, (unsigned)P.cov_tiles),
-                       dim3(256), 0, st, q->vt, P.Np, q->cov, m);
-    r = hip_fail(ctx, hipGetLastError(), "post_cov_kernel");
-  }
-  return r;
-}
-
 // A[i][i] += d: the caller's diag_add on the sampled covariance, in one addition
 __global__ void post_shift_kernel(double* __restrict__ A, int64_t lda, double d, int64_t n) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) A[i * lda + i] += d;
-}
-
-// The first steps of a sample and of a log density, in stream order: the predict with the
-// covariance (mean in q->out, cov in q->cov), cov into the Mp-stride matrix q->smat, diag_add on
-// its diagonal in one addition, the augmented row with residual 0 and the factorisation, which
-// leaves L in q->smat's lower triangle, the status in ctx->result[3] and
-// ctx->result[0] = -1/2 logdet - (m / 2) log 2 pi. q->smat holds Mp x Mp doubles.
-int post_scale_factor(lfm_ctx* ctx, lfm_post* q, const ResidentPlan& P, int64_t Mp, const double* t,
-                      double diag_add) {
-  int r = post_enqueue(ctx, q, P, t);
-  if (r) return r;
-  hipStream_t st = ctx->stream;
-  const int64_t m = P.m;
-  hipError_t e = hipMemcpy2DAsync(q->smat, Mp * 8, q->cov, m * 8, m * 8, m,
-                                  hipMemcpyDeviceToDevice, st);
-  if (e != hipSuccess) return hip_fail(ctx, e, "the covariance into the factor's stride");
-  hipLaunchKernelGGL(post_shift_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st,
-                     q->smat, Mp, diag_add, m);
-  return scale_factor(ctx, q->smat, m, Mp, q->out);
 }
 
 // ------------------------------------------------------- held-out log density
@@ -554,183 +347,87 @@ __global__ void post_logp_kernel(const double* __restrict__ res, const double* _
   logp[r] = ok ? res[0] - half : __builtin_nan("");
 }
 
+// ------------------------------------------------------------- launches
+// The right-looking sweep of one chunk's rows (g.Vt) against a factor (g.L, g.dinv, g.z): the
+// plan's panel and update launches in order
+void post_sweep(lfm_ctx* ctx, PostArgs g, const ResidentPlan& P, const PostChunk& c) {
+  hipStream_t st = ctx->stream;
+  const double prow = (double)c.panel_grid * 64;
+  for (const PostPanel& s : P.panels) {
+    g.K0 = s.K0;
+    g.w = s.w;
+    g.tj0 = s.tj0;
+    hipEvent_t ev;
+    prof_begin(ctx, K_POST_PANEL, &ev);
+    hipLaunchKernelGGL(post_panel_kernel, dim3((unsigned)c.panel_grid), dim3(256), 0, st, g);
+    prof_end(ctx, K_POST_PANEL, ev, prow * NB * NB * s.w * s.w, 2.0 * prow * NB * s.w * 8);
+    if (s.ntj > 0) {
+      prof_begin(ctx, K_POST_UPDATE, &ev);
+      hipLaunchKernelGGL(post_update_kernel, dim3((unsigned)c.tiles, (unsigned)s.ntj), dim3(256),
+                         0, st, g);
+      prof_end(ctx, K_POST_UPDATE, ev, 2.0 * c.pad_rows * NB * s.ntj * NB * s.w,
+               2.0 * c.pad_rows * NB * s.ntj * 8);
+    }
+  }
+}
+
 }  // namespace
+
+int post_sigma(lfm_ctx* ctx, const HypDev& h, const double* x, const double* d_y,
+               const double* d_v, int64_t n, double diag_add, double* L, int64_t Mp) {
+  int r = launch_gram_direct<double>(ctx, h, x, n, x, n, diag_add, 0.0, LFM_UPLO_LOWER, L, Mp);
+  if (r) return r;
+  if (d_v)
+    hipLaunchKernelGGL(post_diag_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
+                       ctx->stream, L, Mp, d_v, n);
+  return launch_augment(ctx, h, x, d_y, nullptr, n, L, Mp, Mp);
+}
+
+void post_factor_ready(lfm_ctx* ctx, double* L, int64_t ldl, int64_t n, int64_t Np, double* z,
+                       double* dinv, unsigned z_grid, unsigned dinv_grid) {
+  hipLaunchKernelGGL(post_z_kernel, dim3(z_grid), dim3(256), 0, ctx->stream, L, ldl, n, Np, z);
+  hipLaunchKernelGGL(post_dinv_kernel, dim3(dinv_grid), dim3(128), 0, ctx->stream, L, ldl, dinv);
+}
+
+int post_chunk(lfm_ctx* ctx, const PostArgs& g, const ResidentPlan& P, const PostChunk& c,
+               const HypDev& h, const double* x, const double* t, double* out) {
+  hipStream_t st = ctx->stream;
+  hipLaunchKernelGGL(post_pad_kernel, dim3(1, (unsigned)c.pad_rows), dim3(256), 0, st, g.Vt, P.Np,
+                     P.n, c.rows);
+  int r = launch_gram_direct<double>(ctx, h, t + c.q0 * 3, c.rows, x, P.n, 0.0, 0.0,
+                                     LFM_UPLO_FULL, g.Vt, P.Np);
+  if (r) return r;
+  post_sweep(ctx, g, P, c);
+  hipLaunchKernelGGL(post_finish_kernel, dim3((unsigned)((c.rows + 255) / 256)), dim3(256), 0, st,
+                     h, t, c.q0, c.rows, P.m, g.s2, g.sz, out, out + P.m);
+  return hip_fail(ctx, hipGetLastError(), "resident posterior: chunk launches");
+}
+
+int post_cov(lfm_ctx* ctx, const HypDev& h, const ResidentPlan& P, const double* t,
+             const double* Vt, double* cov) {
+  int r = launch_gram_direct<double>(ctx, h, t, P.m, t, P.m, 0.0, 0.0, LFM_UPLO_LOWER, cov, P.m);
+  if (r) return r;
+  hipLaunchKernelGGL(post_cov_kernel, dim3((unsigned)P.cov_tiles, (unsigned)P.cov_tiles),
+                     dim3(256), 0, ctx->stream, Vt, P.Np, cov, P.m);
+  return hip_fail(ctx, hipGetLastError(), "post_cov_kernel");
+}
+
+int post_shift_factor(lfm_ctx* ctx, double* A, int64_t m, int64_t Mp, double diag_add,
+                      const double* d_loc) {
+  hipLaunchKernelGGL(post_shift_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0,
+                     ctx->stream, A, Mp, diag_add, m);
+  return scale_factor(ctx, A, m, Mp, d_loc);
+}
+
+int post_logp_pass(lfm_ctx* ctx, const PostArgs& a, const PostLogpPlan& P, const PostChunk& c,
+                   const double* mean, double* lp) {
+  hipStream_t st = ctx->stream;
+  hipLaunchKernelGGL(post_resid_kernel, dim3((unsigned)P.resid_grid, (unsigned)c.pad_rows),
+                     dim3(256), 0, st, a.Vt, P.Np, mean, P.m, c.rows);
+  post_sweep(ctx, a, P.rows, c);
+  hipLaunchKernelGGL(post_logp_kernel, dim3((unsigned)((c.rows + 255) / 256)), dim3(256), 0, st,
+                     ctx->result, a.s2, c.rows, lp);
+  return hip_fail(ctx, hipGetLastError(), "held-out log density: pass launches");
+}
+
 }  // namespace lfm
-
-extern "C" {
-
-int lfm_post_create(lfm_ctx* ctx, const double* x, const double* y, int64_t n,
-                    const double* diag_vec, double diag_add, const lfm_hyp* hyp, lfm_post** out) {
-  int r = validate_x(ctx, x, n);
-  if (r) return r;
-  if (out) *out = nullptr;
-  if (!y || !out) return set_err(ctx, LFM_E_ARG, "y / out is NULL");
-  if (!hyp) return set_err(ctx, LFM_E_ARG, "hyp is NULL");
-  if (hyp->num_genes < 1 || hyp->num_genes > (1 << 20))
-    return set_err(ctx, LFM_E_ARG, "num_genes must be in [1, 2^20]");
-  if (!hyp->true_d || !hyp->true_s || !hyp->true_b)
-    return set_err(ctx, LFM_E_ARG, "hyp true_d / true_s / true_b must not be NULL");
-  r = check_mean_shape(ctx, n, hyp);
-  if (r) return r;
-  DeviceGuard g(ctx->device);
-  DeviceTenancy tenancy(ctx, false);  // schedule 1, shared
-  lfm_post* q = new lfm_post;
-  q->owner = ctx;
-  q->device = ctx->device;
-  q->n = n;
-  q->G = hyp->num_genes;
-  q->Np = round_up(n, NB);
-  q->Mp = round_up(n + 1, NB);
-  q->l = hyp->l;
-  r = post_fit(ctx, q, x, y, diag_vec, diag_add, hyp);
-  if (r) {
-    hipStreamSynchronize(ctx->stream);
-    release(q);
-    return r;
-  }
-  *out = q;
-  return LFM_OK;
-}
-
-int lfm_post_destroy(lfm_post* post) {
-  if (!post) return LFM_E_ARG;
-  DeviceGuard g(post->device);
-  release(post);
-  return LFM_OK;
-}
-
-int lfm_post_set_chunk(lfm_post* post, int64_t rows) {
-  if (!post) return LFM_E_ARG;
-  if (rows < 0 || rows % 128 != 0)
-    return set_err(post->owner, LFM_E_ARG, "the chunk must be a multiple of 128 rows (0: default)");
-  post->chunk = rows;
-  return LFM_OK;
-}
-
-int lfm_post_predict_f64(lfm_ctx* ctx, lfm_post* post, const double* t, int64_t m, double* mean,
-                         double* var, double* cov) {
-  if (!ctx) return LFM_E_ARG;
-  if (!post) return set_err(ctx, LFM_E_ARG, "post is NULL");
-  if (ctx->device != post->device)
-    return set_err(ctx, LFM_E_ARG, "the handle belongs to another device than this ctx");
-  if (!t || !mean) return set_err(ctx, LFM_E_ARG, "t / mean is NULL");
-  if (!var && !cov) return set_err(ctx, LFM_E_ARG, "one of var / cov must be given");
-  lfm_post* q = post;
-  const ResidentPlan P = plan_post(q->n, q->G, m, q->chunk, cov != nullptr);
-  if (P.reject) return set_err(ctx, LFM_E_ARG, P.why);
-  DeviceGuard g(ctx->device);
-  DeviceTenancy tenancy(ctx, false);  // no factorisation: shared
-  int r = post_enqueue(ctx, q, P, t);
-  if (r) return r;
-  hipStream_t st = ctx->stream;
-  hipMemcpyAsync(mean, q->out, (size_t)m * 8, hipMemcpyDeviceToHost, st);
-  if (cov)
-    hipMemcpyAsync(cov, q->cov, P.cov_bytes, hipMemcpyDeviceToHost, st);
-  else
-    hipMemcpyAsync(var, q->out + m, (size_t)m * 8, hipMemcpyDeviceToHost, st);
-  r = finish(ctx);
-  if (r) return r;
-  if (cov && var)
-    for (int64_t i = 0; i < m; ++i) var[i] = cov[i * m + i];  // diag(cov), bit for bit
-  return LFM_OK;
-}
-
-int lfm_post_sample_f64(lfm_ctx* ctx, lfm_post* post, const double* t, int64_t m, double diag_add,
-                        uint64_t seed, int64_t sample0, int64_t nsamp, double* mean,
-                        double* out) {
-  if (!ctx) return LFM_E_ARG;
-  if (!post) return set_err(ctx, LFM_E_ARG, "post is NULL");
-  if (ctx->device != post->device)
-    return set_err(ctx, LFM_E_ARG, "the handle belongs to another device than this ctx");
-  if (!t || !out) return set_err(ctx, LFM_E_ARG, "t / out is NULL");
-  lfm_post* q = post;
-  const ResidentPlan P = plan_post(q->n, q->G, m, q->chunk, true);
-  if (P.reject) return set_err(ctx, LFM_E_ARG, P.why);
-  const SamplePlan S = plan_sample(m, nsamp, sample0);
-  if (S.reject) return set_err(ctx, LFM_E_ARG, S.why);
-  DeviceGuard g(ctx->device);
-  DeviceTenancy tenancy(ctx, false);  // CHOL_RESIDENT is schedule 1: shared
-  int r = grow(ctx, &q->smat, &q->smat_cap, S.mat_bytes, "the covariance's factor");
-  if (!r) r = grow(ctx, &q->sz, &q->sz_cap, S.z_bytes, "the normals");
-  if (!r) r = grow(ctx, &q->sx, &q->sx_cap, S.x_bytes, "the samples");
-  if (!r) r = ctx->hpin.reserve(ctx, 1 << 16);
-  if (r) return r;
-  r = post_scale_factor(ctx, q, P, S.Mp, t, diag_add);
-  if (r) return r;
-  hipStream_t st = ctx->stream;
-  r = sample_draw(ctx, S, q->smat, q->out, seed, q->sz, q->sx);
-  if (r) return r;
-  if (mean) hipMemcpyAsync(mean, q->out, (size_t)m * 8, hipMemcpyDeviceToHost, st);
-  return sample_finish(ctx, S, q->sx, out, mean);
-}
-
-int lfm_post_log_prob_f64(lfm_ctx* ctx, lfm_post* post, const double* t, int64_t m, double diag_add,
-                          const double* ystar, int64_t k, double* mean, double* logp) {
-  if (!ctx) return LFM_E_ARG;
-  if (!post) return set_err(ctx, LFM_E_ARG, "post is NULL");
-  if (ctx->device != post->device)
-    return set_err(ctx, LFM_E_ARG, "the handle belongs to another device than this ctx");
-  if (!t || !ystar || !logp) return set_err(ctx, LFM_E_ARG, "t / ystar / logp is NULL");
-  lfm_post* q = post;
-  const PostLogpPlan P = plan_post_logp(q->n, q->G, m, k, q->chunk);
-  if (P.reject) return set_err(ctx, LFM_E_ARG, P.why);
-  DeviceGuard g(ctx->device);
-  DeviceTenancy tenancy(ctx, false);  // CHOL_RESIDENT is schedule 1: shared
-  // the predict's Vt and accumulators serve the residual rows once the covariance is formed:
-  // grown to the larger of the two uses before the predict, which then finds them large enough
-  int r = grow(ctx, &q->vt, &q->vt_cap, P.vt_bytes, "the solve workspace");
-  if (!r) r = grow(ctx, &q->acc, &q->acc_cap, P.acc_bytes, "the row accumulators");
-  if (!r) r = grow(ctx, &q->smat, &q->smat_cap, P.mat_bytes, "the covariance's factor");
-  if (!r) r = grow(ctx, &q->sdinv, &q->sdinv_cap, P.dinv_bytes, "its diagonal inverses");
-  if (!r) r = grow(ctx, &q->szero, &q->szero_cap, P.zero_bytes, "the zero z");
-  if (!r) r = grow(ctx, &q->lp, &q->lp_cap, P.logp_bytes, "the log densities");
-  if (!r) r = ctx->hpin.reserve(ctx, 1 << 16);
-  if (r) return r;
-  r = post_scale_factor(ctx, q, P.pred, P.Mp, t, diag_add);
-  if (r) return r;
-  hipStream_t st = ctx->stream;
-  // the factor as the sweep reads it: row m, which holds L^{-1} 0, becomes the identity row its
-  // neighbours are and its zeros become the sweep's z; then the diagonal blocks' inverses. The
-  // sweep reads the factor's 16 x 16 diagonal blocks through these inverses alone (built from
-  // their lower triangles) and everything else strictly below them, so the input entries the
-  // factorisation leaves above the diagonal are never read.
-  hipLaunchKernelGGL(post_z_kernel, dim3((unsigned)P.z_grid), dim3(256), 0, st, q->smat, P.Mp, m,
-                     P.Np, q->szero);
-  hipLaunchKernelGGL(post_dinv_kernel, dim3((unsigned)P.dinv_grid), dim3(128), 0, st, q->smat, P.Mp,
-                     q->sdinv);
-  PostArgs a{};
-  a.Vt = q->vt;
-  a.ldv = P.Np;
-  a.L = q->smat;
-  a.ldl = P.Mp;
-  a.dinv = q->sdinv;
-  a.z = q->szero;
-  a.s2 = q->acc;
-  a.sz = q->acc + P.rows.vt_rows;
-  for (const PostChunk& c : P.rows.chunks) {
-    hipError_t e = hipMemcpy2DAsync(q->vt, P.Np * 8, ystar + c.q0 * m, m * 8, m * 8, c.rows,
-                                    hipMemcpyHostToDevice, st);
-    if (e != hipSuccess) return hip_fail(ctx, e, "upload ystar");
-    hipLaunchKernelGGL(post_resid_kernel, dim3((unsigned)P.resid_grid, (unsigned)c.pad_rows),
-                       dim3(256), 0, st, q->vt, P.Np, q->out, m, c.rows);
-    post_sweep(ctx, a, P.rows, c);
-    hipLaunchKernelGGL(post_logp_kernel, dim3((unsigned)((c.rows + 255) / 256)), dim3(256), 0, st,
-                       ctx->result, a.s2, c.rows, q->lp);
-    r = hip_fail(ctx, hipGetLastError(), "held-out log density: pass launches");
-    if (r) return r;
-    hipMemcpyAsync(logp + c.q0, q->lp, (size_t)c.rows * 8, hipMemcpyDeviceToHost, st);
-  }
-  if (mean) hipMemcpyAsync(mean, q->out, (size_t)m * 8, hipMemcpyDeviceToHost, st);
-  double* hres = ctx->hpin;
-  hipMemcpyAsync(hres, ctx->result, 5 * sizeof(double), hipMemcpyDeviceToHost, st);
-  r = finish(ctx);
-  if (r) return r;
-  r = status_code(ctx, hres[3], hres[4]);
-  if (r == LFM_E_NOT_PD) {
-    std::fill(logp, logp + k, std::nan(""));
-    if (mean) std::fill(mean, mean + m, std::nan(""));
-  }
-  return r;
-}
-
-}  // extern "C"

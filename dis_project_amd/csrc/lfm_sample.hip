@@ -1,5 +1,6 @@
-// lfm_sample.hip — joint samples from a Gaussian (include/lfm.h lfm_randn_f64,
-// lfm_mvn_sample_f64; lfm_post_sample_f64 in lfm_post.hip ends here too).
+// lfm_sample.hip — joint samples from a Gaussian: the kernels and their launches (the entry
+// points lfm_randn_f64 and lfm_mvn_sample_f64 are lfm_api.hip's; lfm_post_sample_f64, in
+// lfm_post_api.hip, ends here too).
 //
 // Reference: gpjax 0.8.2 GaussianDistribution.sample(seed, sample_shape): loc + L z per sample,
 // L L^T = scale, z standard normal. Here, with samples as rows:
@@ -17,7 +18,7 @@
 // Every size and grid is plan_sample's (lfm_host.cpp). The K order and the tile shape depend on
 // neither nsamp nor sample0, rows have one owner and the launches follow each other on one
 // stream: no atomics, no device-side waits, the same bits however a draw is split over calls.
-#include "lfm_api_internal.h"
+#include "lfm_internal.h"
 #include "lfm_chol_dev.h"
 
 using namespace lfm;
@@ -81,6 +82,8 @@ __global__ __launch_bounds__(256, 2) void sample_trmm_kernel(SampleArgs g) {
     }
 }
 
+}  // namespace
+
 void launch_randn(lfm_ctx* ctx, double* Z, int64_t ld, int64_t rows, int64_t pairs, int grid,
                   uint64_t seed, int64_t sample0) {
   hipEvent_t ev;
@@ -89,8 +92,6 @@ void launch_randn(lfm_ctx* ctx, double* Z, int64_t ld, int64_t rows, int64_t pai
                      pairs, seed, (uint64_t)sample0);
   prof_end(ctx, K_SAMPLE_RANDN, ev, 0, (double)rows * ld * 8);
 }
-
-}  // namespace
 
 int scale_factor(lfm_ctx* ctx, double* A, int64_t n, int64_t Mp, const double* d_loc) {
   // the augmented row: y = loc, residual 0, so the MLL the factorisation also produces is
@@ -125,68 +126,4 @@ int sample_draw(lfm_ctx* ctx, const SamplePlan& P, double* A, const double* d_lo
   return hip_fail(ctx, hipGetLastError(), "joint samples: launches");
 }
 
-int sample_finish(lfm_ctx* ctx, const SamplePlan& P, const double* X, double* out, double* mean) {
-  double* hres = ctx->hpin;
-  hipMemcpyAsync(hres, ctx->result, 5 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream);
-  hipMemcpyAsync(out, X, P.x_bytes, hipMemcpyDeviceToHost, ctx->stream);
-  int r = finish(ctx);
-  if (r) return r;
-  r = status_code(ctx, hres[3], hres[4]);
-  if (r == LFM_E_NOT_PD) {
-    std::fill(out, out + P.nsamp * P.n, std::nan(""));
-    if (mean) std::fill(mean, mean + P.n, std::nan(""));
-  }
-  return r;
-}
-
 }  // namespace lfm
-
-extern "C" {
-
-int lfm_randn_f64(lfm_ctx* ctx, uint64_t seed, int64_t sample0, int64_t nsamp, int64_t n,
-                  double* out) {
-  if (!ctx) return LFM_E_ARG;
-  if (!out) return set_err(ctx, LFM_E_ARG, "out is NULL");
-  const SamplePlan P = plan_sample(n, nsamp, sample0);
-  if (P.reject) return set_err(ctx, LFM_E_ARG, P.why);
-  DeviceGuard g(ctx->device);
-  DeviceTenancy tenancy(ctx, false);  // no factorisation: shared
-  // the generator alone: nsamp rows of ld = n rounded up to a pair
-  const int64_t ld = (n + 1) / 2 * 2, pairs = nsamp * (ld / 2);
-  int r = ctx->smp_z.reserve(ctx, (size_t)nsamp * ld * sizeof(double));
-  if (r) return r;
-  launch_randn(ctx, ctx->smp_z, ld, nsamp, pairs,
-               (int)std::min<int64_t>((pairs + 255) / 256, SAMPLE_RANDN_GRID), seed, sample0);
-  r = hip_fail(ctx, hipGetLastError(), "sample_randn_kernel");
-  if (r) return r;
-  hipError_t e = hipMemcpy2DAsync(out, n * 8, ctx->smp_z, ld * 8, n * 8, nsamp,
-                                  hipMemcpyDeviceToHost, ctx->stream);
-  if (e != hipSuccess) return hip_fail(ctx, e, "download the normals");
-  return finish(ctx);
-}
-
-int lfm_mvn_sample_f64(lfm_ctx* ctx, const double* loc, const double* scale, int64_t n,
-                       int64_t lds, uint64_t seed, int64_t sample0, int64_t nsamp, double* out) {
-  if (!ctx) return LFM_E_ARG;
-  if (!loc || !scale || !out) return set_err(ctx, LFM_E_ARG, "loc / scale / out is NULL");
-  const SamplePlan P = plan_sample(n, nsamp, sample0);
-  if (P.reject) return set_err(ctx, LFM_E_ARG, P.why);
-  if (lds < n) return set_err(ctx, LFM_E_ARG, "lds must be >= n");
-  DeviceGuard g(ctx->device);
-  int r = ctx->A.reserve(ctx, P.mat_bytes);
-  if (!r) r = ctx->smp_z.reserve(ctx, P.z_bytes);
-  if (!r) r = ctx->smp_x.reserve(ctx, P.x_bytes);
-  if (!r) r = ctx->xin.reserve(ctx, (size_t)n * sizeof(double));
-  if (!r) r = ctx->hpin.reserve(ctx, 1 << 16);
-  if (r) return r;
-  DeviceTenancy tenancy(ctx, false);  // CHOL_RESIDENT is schedule 1: shared
-  hipMemcpyAsync(ctx->xin, loc, n * 8, hipMemcpyHostToDevice, ctx->stream);
-  hipError_t e = hipMemcpy2DAsync(ctx->A, P.Mp * 8, scale, lds * 8, n * 8, n,
-                                  hipMemcpyHostToDevice, ctx->stream);
-  if (e != hipSuccess) return hip_fail(ctx, e, "upload scale");
-  r = sample_enqueue(ctx, P, ctx->A, ctx->xin, seed, ctx->smp_z, ctx->smp_x);
-  if (r) return r;
-  return sample_finish(ctx, P, ctx->smp_x, out, nullptr);
-}
-
-}  // extern "C"

@@ -1,5 +1,5 @@
 // post_logp_plan_check.cpp — plan_post_logp (dis_project_amd/csrc/lfm_host.cpp), the plan of
-// lfm_post_log_prob_f64 (lfm_post.hip issues exactly what it says), under AddressSanitizer +
+// lfm_post_log_prob_f64 (lfm_post_api.hip issues exactly what it says), under AddressSanitizer +
 // UBSan: built and run by tests/test_post_logp_host.py with the flags of tests/native/Makefile.
 //   the rejections come in the documented order with their messages; Mp' and Np' at the 128-edges
 //   of m; the sweep over the covariance's factor has no update launch up to Np' = 512 and one from

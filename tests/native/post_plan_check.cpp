@@ -1,5 +1,5 @@
 // post_plan_check.cpp — plan_post (dis_project_amd/csrc/lfm_host.cpp), the launch plan of the
-// resident posterior's predicts (lfm_post.hip issues exactly what it says), under
+// resident posterior's predicts (lfm_post_api.hip issues exactly what it says), under
 // AddressSanitizer + UBSan: built and run by tests/test_post_host.py with the flags of
 // tests/native/Makefile. Over n in {1 .. 1400 step 37, 16384}, three gene counts, a range of m,
 // chunk in {128, 256, default} and the covariance on / off:

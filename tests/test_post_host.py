@@ -92,7 +92,7 @@ def test_posterior_argument_checks_need_no_gpu():
 
 @pytest.mark.skipif(not os.path.exists("/opt/rocm/bin/hipcc"), reason="needs hipcc")
 def test_strict_build():
-    """Every unit, lfm_post.hip included, with warnings as errors."""
+    """Every unit, lfm_post.hip and lfm_post_api.hip included, with warnings as errors."""
     r = subprocess.run(["make", "-s", "-C", os.path.join(ROOT, "dis_project_amd", "csrc"),
                         "-j", str(min(16, os.cpu_count() or 4)), "strict"],
                        capture_output=True, text=True, timeout=1800)
