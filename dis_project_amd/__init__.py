@@ -9,12 +9,13 @@ from .dataset import Dataset, SyntheticP53Data, dataset_3d  # noqa: F401
 from .distributions import GaussianDistribution, randn, seed_to_u64  # noqa: F401
 from .farm import MidBatchEvaluator  # noqa: F401
 from .model import ExactLFM  # noqa: F401
-from .objectives import CustomConjMLL  # noqa: F401
+from .objectives import CustomConjLOOCV, CustomConjMLL  # noqa: F401
 from .predict import BatchPredictor, MidBatchPredictor, Posterior  # noqa: F401
 from .trainer import MidBatchTrainer  # noqa: F401
 
 __all__ = [
     "BatchPredictor",
+    "CustomConjLOOCV",
     "CustomConjMLL",
     "Dataset",
     "ExactLFM",

@@ -127,6 +127,10 @@ PRODUCT_SIGNATURES = [
     ("lfm_mll_f64", c_int, [_c_ctx, _dptr, _dptr, c_int64, POINTER(LfmHyp), c_int, _dptr]),
     ("lfm_mll_grad_f64", c_int,
      [_c_ctx, _dptr, _dptr, c_int64, POINTER(LfmHyp), c_int, _dptr, _dptr]),
+    ("lfm_loocv_f64", c_int,
+     [_c_ctx, _dptr, _dptr, c_int64, POINTER(LfmHyp), c_int, _dptr, _dptr, _dptr]),
+    ("lfm_loocv_grad_f64", c_int,
+     [_c_ctx, _dptr, _dptr, c_int64, POINTER(LfmHyp), c_int, _dptr, _dptr]),
     ("lfm_posterior_f64", c_int,
      [_c_ctx, _dptr, _dptr, c_int64, _dptr, c_double, _dptr, c_int64, POINTER(LfmHyp), _dptr,
       _dptr]),
@@ -222,6 +226,8 @@ KCLASSES = ["tables", "gram_grid", "gram_direct", "augment", "potrf", "trsm", "s
             "mid_pairs", "mid_finish"]
 # ... and the joint samples' two (lfm_sample.hip), entries 22 and 23 of that order
 SAMPLE_KCLASSES = ["sample_randn", "sample_trmm"]
+# ... and the leave-one-out gradient's product (lfm_loo.hip), entry 24
+LOO_KCLASSES = ["loo_product"]
 
 _lib = None
 _diag = None
@@ -373,7 +379,7 @@ class Context:
         if classes is not None:
             mask = 0
             for c in classes:
-                mask |= 1 << (KCLASSES + SAMPLE_KCLASSES).index(c)
+                mask |= 1 << (KCLASSES + SAMPLE_KCLASSES + LOO_KCLASSES).index(c)
             self.check(self.lib.lfm_profile_classes(self.handle, mask))
         else:
             self.check(self.lib.lfm_profile_classes(self.handle, 0xFFFFFFFF))

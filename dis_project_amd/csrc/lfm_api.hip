@@ -1,5 +1,6 @@
 // lfm_api.hip — the large-N entry points of include/lfm.h: input staging, x-layout detection,
-// mean / h / cross-covariance / gram / MLL / gradient / posterior / log_prob / joint samples,
+// mean / h / cross-covariance / gram / MLL / gradient / leave-one-out CV / posterior / log_prob /
+// joint samples,
 // resident data, the C3 restart pipeline and the dispatch of lfm_mll_batch_f64.
 //
 // Every entry point binds the ctx's device, enqueues on the ctx's stream and is
@@ -283,6 +284,67 @@ void twins_drop(lfm_ctx* ctx) {
   ctx->ovl_stream = nullptr;
 }
 
+// lfm_loocv_f64 (grad NULL) and lfm_loocv_grad_f64 (loo_mean, loo_var NULL), arguments checked:
+// lfm_mll_grad_f64's route to the bordered factor, then the leave-one-out terms off its bottom
+// block and, for the gradient, W_loo inside the same matrix (LooPlan) and the gradient's own
+// reductions over it.
+int loo_blocked(lfm_ctx* ctx, const double* x, const double* y, int64_t n, const lfm_hyp* hyp,
+                int negative, double* value, double* loo_mean, double* loo_var, double* grad) {
+  const LooPlan P = plan_loo(n);
+  if (P.reject) return set_err(ctx, LFM_E_ARG, P.why);
+  DeviceGuard g(ctx->device);
+  Staged st;
+  int r = stage_hyp(ctx, hyp, x, n, true, &st);
+  if (r) return r;
+  r = ctx->xin.reserve(ctx, (size_t)n * 4 * 8);
+  if (r) return r;
+  const double* d_x = ctx->xin;
+  const double* d_y = ctx->xin + 3 * n;
+  Copies up{ctx};
+  up_xy(up, x, y, n);
+  r = up.done("upload x / y");
+  if (!r) r = ctx->A.reserve(ctx, P.mat_bytes);
+  // gacc: the gradient's accumulators and output (as lfm_mll_grad_f64), then the plan's vectors
+  const int64_t G = hyp->num_genes;
+  const size_t nacc = (size_t)(5 * G + 3), ng = grad ? (size_t)(3 * G + 2) : 0;
+  if (!r) r = ctx->gacc.reserve(ctx, nacc * sizeof(double) + P.vec_bytes);
+  if (r) return r;
+  DeviceTenancy tenancy(ctx, s3_on(ctx));  // held to the final synchronise (finish)
+  return with_s3_fallback(ctx, [&]() -> int {
+    int r = factor_sigma(ctx, st, d_x, d_y, nullptr, n, hyp, negative, P.ld, CHOL_INVERSE);
+    if (r) return r;
+    double* vec = ctx->gacc + nacc;
+    double* d_out = ctx->gacc + 2 * G + 1;
+    r = launch_loo_terms(ctx, P, ctx->A, d_y, negative, vec);
+    // a failed factor is known only on the device: the weights and the reductions run regardless,
+    // on what may be NaN or Inf, and every output is NaN-filled below (lfm_loo.hip's header)
+    if (!r && grad) r = launch_loo_weights(ctx, P, ctx->A, vec);
+    if (!r && grad)
+      r = launch_grad_loo(ctx, st.h, d_x, n, ctx->A + P.w, P.ld, vec + P.u, hyp->obs_stddev,
+                          negative, ctx->gacc, d_out, &st.lay, st.d_times, st.d_bg);
+    if (r) return r;
+    r = ctx->hpin.reserve(ctx, (ng + 1 + 16) * sizeof(double));
+    if (r) return r;
+    Copies c{ctx};
+    if (grad) c.down(ctx->hpin, d_out, ng * sizeof(double));
+    c.down(ctx->hpin + ng, vec + P.val, sizeof(double));
+    if (loo_mean) c.down(loo_mean, vec + P.mu, n * 8);
+    if (loo_var) c.down(loo_var, vec + P.var, n * 8);
+    r = result_tail(c, "download the leave-one-out results");
+    if (r == LFM_OK) {
+      *value = ctx->hpin[ng];
+      if (grad) std::memcpy(grad, ctx->hpin, ng * sizeof(double));
+    } else if (status_failed(r)) {
+      const double nan = std::nan("");
+      *value = nan;
+      if (grad) std::fill(grad, grad + ng, nan);
+      if (loo_mean) std::fill(loo_mean, loo_mean + n, nan);
+      if (loo_var) std::fill(loo_var, loo_var + n, nan);
+    }
+    return r;
+  });
+}
+
 int sample_finish(lfm_ctx* ctx, const SamplePlan& P, const double* X, double* out, double* mean) {
   Copies c{ctx};
   c.down(out, X, P.x_bytes);
@@ -463,6 +525,20 @@ int lfm_mll_grad_f64(lfm_ctx* ctx, const double* x, const double* y, int64_t n,
     }
     return r;
   });
+}
+
+int lfm_loocv_f64(lfm_ctx* ctx, const double* x, const double* y, int64_t n, const lfm_hyp* hyp,
+                  int negative, double* value, double* loo_mean, double* loo_var) {
+  int r = check_problem(ctx, x, n, y && value, "y / value is NULL", hyp);
+  if (r) return r;
+  return loo_blocked(ctx, x, y, n, hyp, negative, value, loo_mean, loo_var, nullptr);
+}
+
+int lfm_loocv_grad_f64(lfm_ctx* ctx, const double* x, const double* y, int64_t n,
+                       const lfm_hyp* hyp, int negative, double* value, double* grad) {
+  int r = check_problem(ctx, x, n, y && value && grad, "y / value / grad is NULL", hyp);
+  if (r) return r;
+  return loo_blocked(ctx, x, y, n, hyp, negative, value, nullptr, nullptr, grad);
 }
 
 int lfm_posterior_f64(lfm_ctx* ctx, const double* x, const double* y, int64_t n,

@@ -175,7 +175,8 @@ const char* const kClassName[K_NCLASS] = {"tables",   "gram_grid", "gram_direct"
                                           "syrk_side", "small_grad", "small_post",
                                           "post_panel", "post_update", "mid_fill",
                                           "mid_column", "mid_inverse", "mid_pairs",
-                                          "mid_finish", "sample_randn", "sample_trmm"};
+                                          "mid_finish", "sample_randn", "sample_trmm",
+                                          "loo_product"};
 
 int set_err(lfm_ctx* ctx, int code, const std::string& msg) {
   if (ctx) ctx->err = msg;

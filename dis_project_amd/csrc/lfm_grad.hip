@@ -22,9 +22,41 @@
 //   functions per pair; W is read once (8 B per pair).
 // grad_finish_kernel: tr(W), the mean terms of m_i = (B/D)[i // (n/G)] flag_i
 //   (model.py:124-149), the sign of CustomConjMLL(negative) and NaN on a failed factor.
+//
+// The three reductions take W and the mean terms' vector from a policy: MllWeight forms
+// W = Bt + 2 a a^T inline and uses a; LooWeight reads the finished W_loo of lfm_loo.hip and uses
+// u = S^{-1} b (the leave-one-out objective's gradient has the same shape).
 #include "lfm_dual.h"
 
 namespace lfm {
+
+// ---------------------------------------------------------------- weights
+// col(c): what at() needs of column c, read once per thread; at(i, c, col(c)): W[i][c], c <= i;
+// diag(i): W[i][i]; mean(i): the vector v of the mean terms v^T dm.
+struct MllWeight {
+  const double* __restrict__ Bt;
+  int64_t ldb;
+  const double* __restrict__ al;
+  __device__ __forceinline__ double col(int64_t c) const { return al[c]; }
+  __device__ __forceinline__ double at(int64_t i, int64_t c, double ac) const {
+    return Bt[i * ldb + c] + 2.0 * al[i] * ac;
+  }
+  __device__ __forceinline__ double diag(int64_t i) const {
+    return Bt[i * ldb + i] + 2.0 * al[i] * al[i];
+  }
+  __device__ __forceinline__ double mean(int64_t i) const { return al[i]; }
+};
+struct LooWeight {
+  const double* __restrict__ W;
+  int64_t ldw;
+  const double* __restrict__ u;
+  __device__ __forceinline__ double col(int64_t) const { return 0.0; }
+  __device__ __forceinline__ double at(int64_t i, int64_t c, double) const {
+    return W[i * ldw + c];
+  }
+  __device__ __forceinline__ double diag(int64_t i) const { return W[i * ldw + i]; }
+  __device__ __forceinline__ double mean(int64_t i) const { return u[i]; }
+};
 
 // ---------------------------------------------------------------- kernels
 // Bottom rows of the bordered matrix: row Mp + i = e_i in the first Mp columns, 0 after.
@@ -38,9 +70,9 @@ __global__ void border_init_kernel(double* __restrict__ A, int64_t lda, int64_t 
 
 // acc layout: [0,G) dD  [G,2G) dS  [2G] dl   (kernel terms of 1/2 tr(W dK))
 constexpr int GR = 32;
+template <class WP>
 __global__ __launch_bounds__(256) void grad_pairs_kernel(HypDev p, const double* __restrict__ x,
-                                                         int64_t n, const double* __restrict__ Bt,
-                                                         int64_t ldb, const double* __restrict__ al,
+                                                         int64_t n, WP wp,
                                                          double* __restrict__ acc) {
   const int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x;
   const int64_t r0 = (int64_t)blockIdx.y * GR;
@@ -51,7 +83,7 @@ __global__ __launch_bounds__(256) void grad_pairs_kernel(HypDev p, const double*
   const int64_t cc = cv ? c : n - 1;
   const double tb = x[cc * 3], gb = x[cc * 3 + 1], fb = x[cc * 3 + 2];
   const int k = gene_index(gb, G);
-  const double ac = al[cc];
+  const double ac = wp.col(cc);
   double cD = 0.0, cS = 0.0, rD = 0.0, rS = 0.0, sl = 0.0;
   int jcur = -1;
   const int64_t rend = min(r0 + GR, n);
@@ -70,7 +102,7 @@ __global__ __launch_bounds__(256) void grad_pairs_kernel(HypDev p, const double*
       jcur = j;
     }
     if (!cv || c > i) continue;
-    double wgt = Bt[i * ldb + c] + 2.0 * al[i] * ac;
+    double wgt = wp.at(i, c, ac);
     if (c == i) wgt *= 0.5;
     PairGrad o{0.0, 0.0, 0.0, 0.0, 0.0};
     kernel_grad(p, ta, ga, fa, tb, gb, fb, wgt, o);
@@ -105,23 +137,24 @@ __global__ __launch_bounds__(256) void grad_pairs_kernel(HypDev p, const double*
 
 // One workgroup: tr(W), mean terms, sign, NaN on a failed factor.
 // out: [0,G) d  [G,2G) s  [2G,3G) b  [3G] l  [3G+1] obs_stddev.
+template <class WP>
 __global__ __launch_bounds__(1024) void grad_finish_kernel(
-    HypDev p, const double* __restrict__ x, int64_t n, const double* __restrict__ Bt, int64_t ldb,
-    const double* __restrict__ al, const double* __restrict__ acc, double obs_stddev,
-    const double* __restrict__ result, int negative, double* __restrict__ out) {
+    HypDev p, const double* __restrict__ x, int64_t n, WP wp, const double* __restrict__ acc,
+    double obs_stddev, const double* __restrict__ result, int negative,
+    double* __restrict__ out) {
   __shared__ double red[16];
   const int tid = threadIdx.x, G = p.G;
   const bool failed = (int)result[3] != INT_MAX;
   const double sign = negative ? -1.0 : 1.0;
   double tr = 0.0;
-  for (int64_t i = tid; i < n; i += 1024) tr += Bt[i * ldb + i] + 2.0 * al[i] * al[i];
+  for (int64_t i = tid; i < n; i += 1024) tr += wp.diag(i);
   tr = wave_sum(tr);
   if ((tid & 63) == 0) red[tid >> 6] = tr;
   const int64_t bs = n / G;
   for (int g = tid; g < G; g += 1024) {
     double af = 0.0;  // sum over mean block g of a_i flag_i (model.py:145-149)
     for (int64_t i = (int64_t)g * bs; i < (int64_t)(g + 1) * bs; ++i)
-      af += al[i] * (double)flag_int(x[i * 3 + 2]);
+      af += wp.mean(i) * (double)flag_int(x[i * 3 + 2]);
     const double D = p.D[g], B = p.B[g];
     const double gd = acc[g] - B / (D * D) * af;
     const double nan = __builtin_nan("");
@@ -156,10 +189,10 @@ __global__ void grad_tables_kernel(HypDev p, int T, double dt, const double* __r
 // constant Cm = S_j S_k l sqrt(pi)/2 / (D_j + D_k) is applied once per tile to the
 // W-weighted sums, which go out as five atomics per workgroup.
 // acc layout as grad_pairs_kernel: [0,G) dD  [G,2G) dS  [2G] dl.
+template <class WP>
 __global__ __launch_bounds__(256) void grad_grid_kernel(HypDev p, const double* __restrict__ tab,
                                                         int Tn, const int* __restrict__ bg,
-                                                        int64_t n, const double* __restrict__ Bt,
-                                                        int64_t ldb, const double* __restrict__ al,
+                                                        int64_t n, WP wp,
                                                         double* __restrict__ acc) {
   constexpr int R = 64, C = 256, WIN = C + R - 1;
   __shared__ double sT[12][WIN];   // k-side tables at d, j-side tables at -d
@@ -204,10 +237,9 @@ __global__ __launch_bounds__(256) void grad_grid_kernel(HypDev p, const double* 
   const double Ek = Pt[3 * nT + kc], EkD = Pt[4 * nT + kc];
   const double Qk = Pt[5 * nT + kc], QkD = Pt[6 * nT + kc], Qkl = Pt[7 * nT + kc];
   const int64_t c = c0 + tid;
-  const double ac = al[c];
+  const double ac = wp.col(c);
   __syncthreads();
   double sV = 0.0, sVj = 0.0, sVk = 0.0, sVl = 0.0;
-  const double* bp = Bt + r0 * ldb + c;
 #pragma unroll 4
   for (int i = 0; i < R; ++i) {
     const int64_t row = r0 + i;
@@ -224,7 +256,7 @@ __global__ __launch_bounds__(256) void grad_grid_kernel(HypDev p, const double* 
     const double Vk = WkD - XkD * Pk - Xk * PkD - EkD * Ej * QQ - EE * QkD;
     const double Vj = WjD - XjD * Pj - Xj * PjD - Ek * EjD * QQ - EE * QjD;
     const double Vl = Wkl - Xkl * Pk - Xk * Pkl + Wjl - Xjl * Pj - Xj * Pjl - EE * (Qkl + Qjl);
-    double w = bp[(int64_t)i * ldb] + 2.0 * al[row] * ac;
+    double w = wp.at(row, c, ac);
     if (row == c) w *= 0.5;
     sV += w * V;
     sVj += w * Vj;
@@ -266,11 +298,12 @@ int launch_border_init(lfm_ctx* ctx, double* A, int64_t lda, int64_t Mp) {
   return hip_fail(ctx, hipGetLastError(), "border_init_kernel");
 }
 
-int launch_grad(lfm_ctx* ctx, const HypDev& h, const double* d_x, int64_t n, const double* A,
-                int64_t lda, int64_t Mp, double obs_stddev, int negative, double* acc,
-                double* d_out, const GridLayout* lay, const double* d_times, const int* d_bg) {
-  const double* Bt = A + Mp * lda + Mp;
-  const double* al = Bt + n * lda;
+namespace {
+// The reductions of 1/2 tr(W dS) + v^T dm over the weights wp
+template <class WP>
+int launch_grad_with(lfm_ctx* ctx, const HypDev& h, const double* d_x, int64_t n, const WP& wp,
+                     double obs_stddev, int negative, double* acc, double* d_out,
+                     const GridLayout* lay, const double* d_times, const int* d_bg) {
   hipMemsetAsync(acc, 0, (size_t)(2 * h.G + 1) * sizeof(double), ctx->stream);
   // the table path on the aligned grid layout (T % 256 == 0, the C2-C4 shape), else the
   // general per-pair dual-number path (LFM_GRAD_DIRECT=1 forces it: a test's cross-check)
@@ -284,19 +317,36 @@ int launch_grad(lfm_ctx* ctx, const HypDev& h, const double* d_x, int64_t n, con
     hipLaunchKernelGGL(grad_tables_kernel, dim3((unsigned)std::min<size_t>((nt + 255) / 256, 4096)),
                        dim3(256), 0, ctx->stream, h, lay->T, lay->dt, d_times, ctx->gtab);
     const int64_t Q = n / 256;
-    hipLaunchKernelGGL(grad_grid_kernel, dim3((unsigned)(2 * Q * (Q + 1))), dim3(256), 0,
-                       ctx->stream, h, ctx->gtab, lay->T, d_bg, n, Bt, lda, al, acc);
+    hipLaunchKernelGGL(grad_grid_kernel<WP>, dim3((unsigned)(2 * Q * (Q + 1))), dim3(256), 0,
+                       ctx->stream, h, ctx->gtab, lay->T, d_bg, n, wp, acc);
   } else {
     dim3 grid2((unsigned)((n + 255) / 256), (unsigned)((n + GR - 1) / GR));
-    hipLaunchKernelGGL(grad_pairs_kernel, grid2, dim3(256), 0, ctx->stream, h, d_x, n, Bt, lda,
-                       al, acc);
+    hipLaunchKernelGGL(grad_pairs_kernel<WP>, grid2, dim3(256), 0, ctx->stream, h, d_x, n, wp,
+                       acc);
   }
   prof_end(ctx, K_GRAD, ev, 0, (double)n * (n + 1) / 2 * 8);
   int r = hip_fail(ctx, hipGetLastError(), "grad kernel");
   if (r) return r;
-  hipLaunchKernelGGL(grad_finish_kernel, dim3(1), dim3(1024), 0, ctx->stream, h, d_x, n, Bt, lda,
-                     al, acc, obs_stddev, ctx->result, negative, d_out);
+  hipLaunchKernelGGL(grad_finish_kernel<WP>, dim3(1), dim3(1024), 0, ctx->stream, h, d_x, n, wp,
+                     acc, obs_stddev, ctx->result, negative, d_out);
   return hip_fail(ctx, hipGetLastError(), "grad_finish_kernel");
+}
+}  // namespace
+
+int launch_grad(lfm_ctx* ctx, const HypDev& h, const double* d_x, int64_t n, const double* A,
+                int64_t lda, int64_t Mp, double obs_stddev, int negative, double* acc,
+                double* d_out, const GridLayout* lay, const double* d_times, const int* d_bg) {
+  const double* Bt = A + Mp * lda + Mp;
+  return launch_grad_with(ctx, h, d_x, n, MllWeight{Bt, lda, Bt + n * lda}, obs_stddev, negative,
+                          acc, d_out, lay, d_times, d_bg);
+}
+
+int launch_grad_loo(lfm_ctx* ctx, const HypDev& h, const double* d_x, int64_t n, const double* W,
+                    int64_t ldw, const double* u, double obs_stddev, int negative, double* acc,
+                    double* d_out, const GridLayout* lay, const double* d_times,
+                    const int* d_bg) {
+  return launch_grad_with(ctx, h, d_x, n, LooWeight{W, ldw, u}, obs_stddev, negative, acc, d_out,
+                          lay, d_times, d_bg);
 }
 
 }  // namespace lfm

@@ -649,6 +649,48 @@ PostLogpPlan plan_post_logp(int64_t n, int64_t G, int64_t m, int64_t k, int64_t 
   return P;
 }
 
+// ------------------------------ leave-one-out CV (lfm_loo.hip)
+LooPlan plan_loo(int64_t n) {
+  LooPlan P;
+  P.n = n;
+  auto rejected = [&](int code, const std::string& why) {
+    P = LooPlan();
+    P.n = n;
+    P.reject = code;
+    P.why = why;
+    return P;
+  };
+  if (n < 1 || n > (int64_t)1 << 30) return rejected(LooPlan::BAD_N, "n must be in [1, 2^30]");
+  P.Np = (n + 127) / 128 * 128;
+  P.Mp = (n + 1 + 127) / 128 * 128;
+  P.ld = 2 * P.Mp;
+  P.tiles = P.Np / 128;
+  // ld^2 doubles within size_t (and ptrdiff_t), the product's 1-D grid within a launch's 2^31 - 1
+  // and the scale kernel's grid rows within 65535
+  const uint64_t ld = (uint64_t)P.ld, cap = (uint64_t)INT64_MAX / sizeof(double);
+  if (ld > cap / ld || P.tiles * (P.tiles + 1) / 2 > (int64_t)INT32_MAX || P.Np / 64 > 65535)
+    return rejected(LooPlan::TOO_LARGE,
+                    "n = " + std::to_string(n) + " is too large for the bordered matrix of the "
+                    "leave-one-out call");
+  P.mat_bytes = (size_t)(ld * ld) * sizeof(double);
+  P.bt = P.Mp * P.ld + P.Mp;
+  P.a = P.bt + n * P.ld;
+  P.bs = 0;
+  P.w = P.Mp;
+  P.mu = 0;
+  P.var = P.Np;
+  P.sc = 2 * P.Np;
+  P.b = 3 * P.Np;
+  P.u = 4 * P.Np;
+  P.val = 5 * P.Np;
+  P.vec = 5 * P.Np + 2;
+  P.vec_bytes = (size_t)P.vec * sizeof(double);
+  P.product_grid = P.tiles * (P.tiles + 1) / 2;
+  P.scale_tiles = P.Np / 64;
+  P.u_grid = (n + 63) / 64;
+  return P;
+}
+
 // ------------------- mid-size resident batch (lfm_mbatch.hip; its kernels: lfm_mid.hip)
 namespace {
 // a region's size rounded up to 16 bytes: in doubles, and in bytes

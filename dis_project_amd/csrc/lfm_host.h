@@ -8,7 +8,9 @@
 // lfm_post.hip and lfm_post_api.hip only read); with lfm_mid_plan.h the
 // mid-size resident batch's arenas and launch plans (plan_mid, plan_mid_post, plan_mid_fit,
 // plan_mid_draw, which lfm_mbatch.hip and lfm_mid.hip only read); and
-// the joint samples' generator and launch plan (plan_sample, which lfm_sample.hip only reads).
+// the joint samples' generator and launch plan (plan_sample, which lfm_sample.hip only reads); and
+// the leave-one-out calls' map of the bordered matrix and their grids (plan_loo, which lfm_loo.hip
+// and lfm_api.hip only read).
 // Plain C++ (no HIP types), so lfm_host.cpp also builds into the host sanitizer check
 // (tests/native, `make -C tests/native asan`) with g++ -fsanitize=address,undefined.
 #pragma once
@@ -346,6 +348,43 @@ struct PostLogpPlan {
 // Rejections in order: plan_post's with the covariance (m < 1 or m % G != 0; m above the chunk; a
 // bad chunk); k < 1; k above LOGP_MAX_K.
 PostLogpPlan plan_post_logp(int64_t n, int64_t G, int64_t m, int64_t k, int64_t chunk);
+
+// ------------------------------ leave-one-out CV (lfm_loo.hip)
+// lfm_loocv_f64 / lfm_loocv_grad_f64 work inside the gradient call's bordered matrix A (2Mp x 2Mp
+// at stride ld = 2Mp, Mp = round_up(n + 1, 128)). After the bordered elimination the bottom-right
+// block holds Bt (lower-stored, n x n) and the row a; the top-left block (the factor, read by
+// nobody after the factorisation's reduction) takes Bs = S^{-1} diag(sqrt c), Np x Np dense and
+// zero-padded (Np = round_up(n, 128) <= Mp), and the top-right block (never written by either
+// schedule) takes W_loo's lower triangle, n x n. Offsets are in doubles from A. The O(n) vectors
+// (mu, var, sqrt c, b, u: Np doubles each, then the value and a^T b) live in scratch the context
+// owns, at `vec` doubles from its start.
+struct LooPlan {
+  enum Reject { OK = 0, BAD_N, TOO_LARGE };
+  int reject = OK;
+  std::string why;           // the message of a rejection
+  int64_t n = 0, Np = 0, Mp = 0, ld = 0;
+  int64_t bt = 0, a = 0;     // Bt's first element and the row a
+  int64_t bs = 0, w = 0;     // Bs and W_loo
+  size_t mat_bytes = 0;      // ld x ld doubles
+  int64_t mu = 0, var = 0, sc = 0, b = 0, u = 0, val = 0;  // from the scratch's start
+  int64_t vec = 0;           // doubles of scratch: 5 Np + 2
+  size_t vec_bytes = 0;
+  int64_t tiles = 0;         // Np / 128
+  int64_t product_grid = 0;  // loo_product_kernel: the lower 128 x 128 tiles, tiles (tiles + 1) / 2
+  int64_t scale_tiles = 0;   // loo_scale_kernel: grid (scale_tiles, scale_tiles) of 64 x 64 tiles
+  int64_t u_grid = 0;        // loo_u_kernel: strips of 64 rows
+};
+// Lower tile b of the product's grid: row tile ti, column tile tj <= ti, row-major over the
+// triangle (b = ti (ti + 1) / 2 + tj).
+LFM_HD inline void loo_tile(int64_t b, int64_t* ti, int64_t* tj) {
+  int64_t q = (int64_t)((sqrt(8.0 * (double)b + 1.0) - 1.0) * 0.5);
+  while ((q + 1) * (q + 2) / 2 <= b) ++q;
+  while (q * (q + 1) / 2 > b) --q;
+  *ti = q;
+  *tj = b - q * (q + 1) / 2;
+}
+// Rejections in order: n < 1 or above 2^30; a matrix or a grid beyond what size_t / a launch holds.
+LooPlan plan_loo(int64_t n);
 
 // Readers-writer lock over one GPU's library work (lfm_ctx.hip DeviceTenancy: a schedule-3
 // factorisation exclusive, all other GPU work shared). In-process a std::shared_mutex; across

@@ -42,6 +42,7 @@ enum KClass {
   K_MID_FINISH,   // mid-size batch: the values / the gradients joined in a fixed order
   K_SAMPLE_RANDN, // joint samples: the counter-based normal generator
   K_SAMPLE_TRMM,  // joint samples: X = loc + Z L^T per 128 x 128 tile (fp64 MFMA)
+  K_LOO_PRODUCT,  // leave-one-out gradient: M = Bs Bs^T per lower 128 x 128 tile (fp64 MFMA)
   K_NCLASS
 };
 
@@ -379,6 +380,18 @@ int launch_grad(lfm_ctx* ctx, const HypDev& h, const double* d_x, int64_t n, con
                 int64_t lda, int64_t Mp, double obs_stddev, int negative, double* acc,
                 double* d_out, const GridLayout* lay = nullptr, const double* d_times = nullptr,
                 const int* d_bg = nullptr);
+// The same reductions over the leave-one-out weights: W (lower-stored, stride ldw) = W_loo and
+// u in the mean terms (lfm_loo.hip computes both)
+int launch_grad_loo(lfm_ctx* ctx, const HypDev& h, const double* d_x, int64_t n, const double* W,
+                    int64_t ldw, const double* u, double obs_stddev, int negative, double* acc,
+                    double* d_out, const GridLayout* lay = nullptr,
+                    const double* d_times = nullptr, const int* d_bg = nullptr);
+// leave-one-out CV (lfm_loo.hip) on the bordered factor in A (P = plan_loo(n)); vec: P.vec doubles
+// of scratch. launch_loo_terms: mu, var, sqrt c, b and the signed value (vec + P.val; NaN on a
+// failed factor). launch_loo_weights: u, Bs and the product, W_loo into A + P.w.
+int launch_loo_terms(lfm_ctx* ctx, const LooPlan& P, const double* A, const double* d_y,
+                     int negative, double* vec);
+int launch_loo_weights(lfm_ctx* ctx, const LooPlan& P, double* A, double* vec);
 // A resident batch small enough to travel in the kernel arguments (small_mll_kernel_args)
 constexpr int SMALL_ARG_PROBS = 16, SMALL_ARG_HYP = 320;
 struct SmallArgs {

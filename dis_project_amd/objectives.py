@@ -8,6 +8,11 @@ into ``liblfm.so`` (``lfm_mll_f64``); only the fp64 scalar comes back.
 
 Like the reference's JAX path, a Sigma that is not positive definite yields NaN
 rather than an exception.
+
+``CustomConjLOOCV`` is the sibling the module the reference modifies has beside its MLL (gpjax
+0.8.2 ``ConjugateLOOCV``): the leave-one-out predictive log probability of the same model, its
+gradient and the per-observation LOO mean and variance (``lfm_loocv_f64`` /
+``lfm_loocv_grad_f64``).
 """
 
 from __future__ import annotations
@@ -100,3 +105,83 @@ class CustomConjMLL:
                                        dptr(out), st)
         ctx.check(rc, allow_not_pd=True)
         return out
+
+
+def _xy(train_data: Dataset):
+    """(x [n, 3], y [n]) of a dataset, checked before any device call."""
+    x = as_f64(train_data.X)
+    if x.ndim != 2 or x.shape[1] != 3 or x.shape[0] < 1:
+        raise ValueError("X must be [n, 3] with n >= 1")
+    y = as_f64(train_data.y).reshape(-1)
+    if y.shape[0] != x.shape[0]:
+        raise ValueError("X and y must have the same number of rows")
+    return x, y
+
+
+@dataclass
+class CustomConjLOOCV:
+    """gpjax 0.8.2 ``ConjugateLOOCV`` for ``ExactLFM`` (the reference's ``CustomConjMLL`` is that
+    module's ``ConjugateMLL`` opened to a custom model; this is its sibling): with
+    ``S = K + (jitter + obs_stddev^2) I`` and ``a = S^{-1} (y - m)``,
+    ``constant * sum_i log N(y_i; y_i - a_i / [S^{-1}]_ii, 1 / [S^{-1}]_ii)``
+    (Rasmussen & Williams 5.4.2). ``JaxTrainer`` trains on it unchanged."""
+
+    negative: bool = False
+
+    @property
+    def constant(self) -> float:
+        return -1.0 if self.negative else 1.0
+
+    def __call__(self, model: ExactLFM, train_data: Dataset) -> float:
+        return self.step(model, train_data)
+
+    @staticmethod
+    def _check(model: ExactLFM, x: np.ndarray):
+        if x.shape[0] % int(model.num_genes) != 0:
+            raise ValueError("the number of rows must be a multiple of num_genes "
+                             "(mean_function, model.py:145-149)")
+
+    def step(self, model: ExactLFM, train_data: Dataset) -> float:
+        """ConjugateLOOCV.step: one ``lfm_loocv_f64`` call; NaN where Sigma is not PD."""
+        x, y = _xy(train_data)
+        self._check(model, x)
+        out = np.empty(1)
+        hp = model.hyp()
+        ctx = model.ctx
+        rc = ctx.lib.lfm_loocv_f64(ctx.handle, dptr(x), dptr(y), x.shape[0], hp.ref,
+                                   int(self.negative), dptr(out), None, None)
+        ctx.check(rc, allow_not_pd=True)
+        return float(out[0])
+
+    def pointwise(self, model: ExactLFM, train_data: Dataset):
+        """``(value, loo_mean [n], loo_var [n])``: the value of ``step`` and each observation's
+        leave-one-out predictive mean and variance (they do not depend on ``negative``). NaN
+        everywhere where Sigma is not PD."""
+        x, y = _xy(train_data)
+        self._check(model, x)
+        out, mean, var = np.empty(1), np.empty(x.shape[0]), np.empty(x.shape[0])
+        hp = model.hyp()
+        ctx = model.ctx
+        rc = ctx.lib.lfm_loocv_f64(ctx.handle, dptr(x), dptr(y), x.shape[0], hp.ref,
+                                   int(self.negative), dptr(out), dptr(mean), dptr(var))
+        ctx.check(rc, allow_not_pd=True)
+        return float(out[0]), mean, var
+
+    def value_and_grad(self, model: ExactLFM, train_data: Dataset):
+        """Value and gradient of ``step`` with respect to the constrained parameters, in
+        ``CustomConjMLL.value_and_grad``'s form: one ``lfm_loocv_grad_f64`` call. A Sigma that is
+        not PD gives NaN everywhere, like JAX."""
+        x, y = _xy(train_data)
+        self._check(model, x)
+        G = int(model.num_genes)
+        val = np.empty(1)
+        g = np.empty(3 * G + 2)
+        hp = model.hyp()
+        ctx = model.ctx
+        rc = ctx.lib.lfm_loocv_grad_f64(ctx.handle, dptr(x), dptr(y), x.shape[0], hp.ref,
+                                        int(self.negative), dptr(val), dptr(g))
+        ctx.check(rc, allow_not_pd=True)
+        grads = {"true_d": g[:G].copy(), "true_s": g[G:2 * G].copy(),
+                 "true_b": g[2 * G:3 * G].copy(), "l": float(g[3 * G]),
+                 "obs_stddev": float(g[3 * G + 1])}
+        return float(val[0]), grads

@@ -463,6 +463,44 @@ int lfm_mbatch_fit_f64(lfm_ctx* ctx, lfm_mbatch* batch, const lfm_adam* opt, int
 int lfm_mll_grad_f64(lfm_ctx* ctx, const double* x, const double* y, int64_t n,
                      const lfm_hyp* hyp, int negative, double* value, double* grad);
 
+/* gpjax 0.8.2 ConjugateLOOCV.step for ExactLFM: the leave-one-out predictive log probability
+ * (Rasmussen & Williams 5.4.2) of the model CustomConjMLL.step scores. With
+ * S = K(x,x) + (jitter + obs_stddev^2) I (exactly what lfm_mll_f64 factors), r = y - m(x),
+ * a = S^{-1} r and k_i = [S^{-1}]_ii:
+ *   loo_mean[i] = y_i - a_i / k_i,   loo_var[i] = 1 / k_i,
+ *   value = constant * sum_i log N(y_i; loo_mean[i], loo_var[i]),  constant = -1 if negative
+ *           else +1.
+ * loo_mean and loo_var (n doubles each) may each be NULL; they do not depend on negative, and
+ * leaving either out changes no bit of the others. Any n >= 1 with n % num_genes == 0.
+ * Not PD: LFM_E_NOT_PD, value and the per-point arrays NaN. k_i comes off the bordered factor as
+ * -Bt_ii - a_i^2; should rounding leave a k_i <= 0 on a factor that is
+ * PD, it propagates as IEEE NaN into its own mean and variance and into the value, with LFM_OK —
+ * gpjax's sqrt of a negative. The value is summed in a fixed order: the same inputs give the same
+ * bits, from either call.
+ * Cost: the bordered factorisation of lfm_mll_grad_f64 (N^3 flops) and O(n) more. Measured on an
+ * MI355X on the C2 grid layout (scripts/loo_rate.py,
+ * profiles/loo_rate.json): 0.70 ms at N = 1024, 2.60 ms at N = 4096, 74.3 ms at N = 16384
+ * (lfm_mll_grad_f64 on the same problems: 0.75, 2.61, 74.6 ms). The route without this call,
+ * lfm_gram_f64 to the host and scipy's cho_factor / cho_solve(I) there, takes 1.70 s at N = 4096.
+ * NULL ctx: LFM_E_ARG. NULL x / y / value / hyp or a bad n: LFM_E_ARG with a message, no caller
+ * buffer touched. */
+int lfm_loocv_f64(lfm_ctx* ctx, const double* x, const double* y, int64_t n, const lfm_hyp* hyp,
+                  int negative, double* value, double* loo_mean /* [n], may be NULL */,
+                  double* loo_var /* [n], may be NULL */);
+/* Its value and gradient with respect to the constrained parameters, grad[3G + 2] in
+ * lfm_mll_grad_f64's layout (jitter gets none):
+ *   d value / d theta = constant * (1/2 tr(W_loo dS/dtheta) + u^T dm/dtheta),
+ *   W_loo = -2 S^{-1} diag(c) S^{-1} + u a^T + a u^T,  c_i = (1 + a_i^2 / k_i) / (2 k_i),
+ *   u = S^{-1} b,  b_i = a_i / k_i.
+ * value has the bits lfm_loocv_f64 returns. Not PD: LFM_E_NOT_PD, value and grad NaN.
+ * Cost: the bordered factorisation plus one more N^3 product on the fp64 MFMA (S^{-1} diag(c)
+ * S^{-1}, lower triangle), then lfm_mll_grad_f64's reductions; no memory beyond that call's
+ * 2Mp x 2Mp matrix and O(n) doubles. Measured as above: 1.04 ms at N = 1024, 4.77 ms at
+ * N = 4096, 150.5 ms at N = 16384, of which the product launch 0.18, 1.72 and 71.4 ms (0.08, 0.51
+ * and 0.78 of the 78.6 TFLOP/s fp64 matrix spec on its n^3 flops). */
+int lfm_loocv_grad_f64(lfm_ctx* ctx, const double* x, const double* y, int64_t n,
+                       const lfm_hyp* hyp, int negative, double* value, double* grad /* [3G+2] */);
+
 /* ------------- posterior at test inputs (latent_predict / multi_gene_predict) */
 /* mean[m] = m(t) + K(t,x) S^{-1} (y - m(x)),  cov[m x m] = K(t,t) - K(t,x) S^{-1} K(x,t),
  * S = K(x,x) + diag(diag_vec) + diag_add I (diag_vec [n] may be NULL); model.py:420-514.
